@@ -24,6 +24,9 @@ Prints one JSON line (rank 0).  Extra objects:
   cpu_baseline  oracle/gin_torch_cpu.py (torch-CPU restatement with the reference's own ATen operators, all host
                 cores; pinned to the reference's golden vectors) timed on this host on config C1 (B = 32 of the same
                 graphs), rank 0, N = 1 only; the numpy oracle's time next to it.
+
+--dump-outputs DIR writes what the last timed step computed (loss, parameter gradients, BatchNorm running
+statistics) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments compare file by file.
 """
 import argparse
 import json
@@ -122,6 +125,41 @@ def csrc_sha256(csrc_dir):
             h.update(f.encode())
             h.update(open(os.path.join(csrc_dir, f), "rb").read())
     return h.hexdigest()
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def step_outputs(model, loss):
+    """What one training step hands its caller, as host float32 arrays: the loss, the gradient of every parameter
+    (views of the flat gradient buffer) and the BatchNorm running statistics the step updated."""
+    out = {"loss": np.asarray(loss.detach().float().cpu().numpy(), dtype=np.float32)}
+    for name, p in model.named_parameters():
+        if p.grad is not None:
+            out["grad." + name] = p.grad.detach().float().cpu().numpy()
+    for name, b in model.named_buffers():
+        if b.is_floating_point():
+            out["buffer." + name] = b.detach().float().cpu().numpy()
+    return out
+
+
+def write_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES):
+    """DIR/<name>.npy for every array.  Over the budget, every array is cut to the same fraction of its elements: a
+    fixed (seeded, sorted) sample of its flattened entries, so two runs keep the same positions.  (256 bytes per
+    file are held back for the .npy header and the one element every array keeps.)"""
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, (budget - 256 * len(arrays)) / float(total)) if total else 1.0
+    sampled = []
+    for name, a in sorted(arrays.items()):
+        if frac < 1.0 and a.size > 1:
+            k = max(1, int(a.size * frac))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[idx]
+            sampled.append(name)
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float32))
+    print("bench: wrote %d arrays to %s%s" % (len(arrays), outdir,
+                                              " (sampled: %s)" % ", ".join(sampled) if sampled else ""), file=sys.stderr)
 
 
 def usable_cpus():
@@ -284,7 +322,13 @@ def main():
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--time-all-kernels", action="store_true",
                     help="HIP events around every launch (default: only the two kernels the rooflines are quoted on)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller (the loss, every "
+                         "parameter gradient, the BatchNorm running statistics) as DIR/<name>.npy, float32, at most "
+                         "64 MB in all (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(self_launch(args))                 # no launcher around us: be the launcher (nothing touched the GPU yet)
@@ -549,6 +593,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # before anything below launches more work on the model (the eager roofline steps overwrite the gradients)
+        write_outputs(args.dump_outputs, step_outputs(model, loss))
     loss_val = float(loss.item())
     rank_check = None
     if multi:

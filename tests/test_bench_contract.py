@@ -36,3 +36,47 @@ def test_bench_line_has_the_contract_fields():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1
+
+
+def _bench_module():
+    """bench.py imported in-process for its host helpers (the environment it sets at import is put back)"""
+    import importlib.util
+    env = dict(os.environ)
+    spec = importlib.util.spec_from_file_location("gnm_bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    try:
+        spec.loader.exec_module(mod)
+    finally:
+        os.environ.clear()
+        os.environ.update(env)
+    return mod
+
+
+def test_dump_outputs_writes_every_array_whole_under_the_budget(tmp_path):
+    import numpy as np
+    bench = _bench_module()
+    arrays = {"loss": np.asarray(0.75, dtype=np.float32), "grad.w": np.arange(12, dtype=np.float32).reshape(3, 4)}
+    bench.write_outputs(str(tmp_path), arrays)
+    assert sorted(os.listdir(tmp_path)) == ["grad.w.npy", "loss.npy"]
+    for name, a in arrays.items():
+        b = np.load(tmp_path / (name + ".npy"))
+        assert b.dtype == np.float32 and b.shape == a.shape and np.array_equal(a, b)
+
+
+def test_dump_outputs_samples_a_fixed_subset_over_the_budget(tmp_path):
+    import numpy as np
+    bench = _bench_module()
+    arrays = {"loss": np.asarray(0.75, dtype=np.float32), "grad.big": np.arange(20000, dtype=np.float32),
+              "grad.small": np.arange(500, dtype=np.float32).reshape(20, 25)}
+    budget = 16384
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays, budget=budget)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["grad.big.npy", "grad.small.npy", "loss.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= budget
+    for f in os.listdir(tmp_path / "a"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)          # the same positions every run
+    big = np.load(tmp_path / "a" / "grad.big.npy")
+    assert 0 < big.size < 20000 and np.all(np.diff(big) > 0)            # a sorted sample of the real entries
+    assert np.load(tmp_path / "a" / "loss.npy") == np.float32(0.75)

@@ -77,3 +77,38 @@ def test_bench_rccl_path_at_world_size_one():
     assert set(cc["launch_mode_trial_ms"]) >= {"graph", "eager"}, cc
     assert out["value"] > 0 and out["final_loss"] == out["final_loss"]
     print("collective:", json.dumps(cc))
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss, parameter gradients and BatchNorm statistics as float32 .npy
+    files; the same arguments give bitwise the same files, and --steps decides which step that is"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+
+    def run(tag, steps):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "16", "--pool", "64",
+                            "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == steps
+        files = sorted(os.listdir(d))
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 1000 * 1000
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert float(arrays["loss"]) == np.float32(out["final_loss"])
+        return arrays
+
+    a, b, c = run("a", 3), run("b", 3), run("c", 4)
+    assert sorted(a) == sorted(b) == sorted(c)
+    grads = [k for k in a if k.startswith("grad.")]
+    assert "grad.eps" in grads and "grad.mlps.0.linears.0.weight" in grads and len(grads) > 20, sorted(a)
+    assert any(k.startswith("buffer.") and k.endswith("running_mean") for k in a), sorted(a)
+    assert any(np.abs(a[k]).max() > 0 for k in grads)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert not all(np.array_equal(a[k], c[k]) for k in grads), "--steps 4 dumped the same step as --steps 3"
