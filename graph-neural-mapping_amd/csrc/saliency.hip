@@ -1,0 +1,377 @@
+// Eval-mode input saliency, batched: d score[b, cls] / d X for every graph b of a batch (/root/reference
+// models/graphcnn.py:254-266, called per graph and class from main.py:60-68).  The gradient mirror of evallayer.hip:
+// one launch per GIN layer from the top layer down, one workgroup (4 waves) per (graph, 32-row block), then one launch
+// that forms dX.
+//
+// In eval mode the chain is linear: BatchNorm on its running statistics is a per-column scale (gamma * rstd, the
+// `scale` vector the forward's gnm_bn_finalize wrote), ReLU a fixed mask (z * scale + shift > 0, the test norm.hip and
+// agg.hip apply in their backwards), the aggregation its transpose, a Linear dX = dZ W.  Per workgroup of layer l:
+//   A. the transposed aggregation of the layer above's gradient (l < L - 1): Y = Adj^T S over the block's 32 rows,
+//      S = dpooled_{l+1} / deg (written so by the launch above), as evallayer.hip's stage A with the TRANSPOSED bit
+//      matrix (three exact bf16 planes of S times the 0/1 bits, fp32 accumulation); the self term (S for self loops,
+//      (1 + eps_{l+1}) dpooled_{l+1} otherwise) is added in the combine pass;
+//   B. plus the head term linears_prediction[l].weight[cls] (x 1/n under average graph pooling), then the outer
+//      BatchNorm + ReLU: dZ = mask * scale;
+//   C. the MLP backward, Linear m-1 down to 1 (down to 0 for l > 0): dX_k = dZ_k W_k with W in torch layout [out, in]
+//      read as the B operand (the six-term split-precision product of evallayer.hip), the inner BatchNorm's mask and
+//      scale between Linears;
+//   D. the block's rows of S_l = g / deg (and of g itself where the self term needs it), g = dpooled_l -- or, for
+//      l = 0, the gradient at the first Linear's OUTPUT: by linearity (Adj^T + (1+e) I)(dZ W0) = ((Adj^T + (1+e) I) dZ) W0,
+//      so the final launch aggregates at width H and multiplies by W0 last, instead of aggregating F0-wide rows.
+// The masks come from the pre-BatchNorm outputs z of every Linear, which the eval forward (gnm/core.py encoder_forward)
+// leaves in memory anyway.
+#include "gnm_common.h"
+#include <string.h>
+
+typedef __bf16 sl_bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int sl_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int sl_u32x2 __attribute__((ext_vector_type(2)));
+
+static constexpr int kSlMaxN = 416;               // as evallayer.hip: a block's bit rows fit 8 words per lane
+static constexpr int kSlMaxH = 128;
+static constexpr int kSlLinWords = 6;             // per (layer, Linear): W, ld W, z, ld z, scale, shift
+static constexpr int kSlTS = kSlMaxH + 4;         // row stride of the LDS tiles (floats)
+
+extern "C" int gnm_linear_max_k(int H);
+
+struct SlArgs {
+    const uint32_t* adj_bits; const int64_t* b_tbits_off; const int32_t* node_off;
+    const int32_t* rowptr; const int64_t* b_rp_off;
+    int B, wmax, L, m, l, H, F0, cls;
+    int average, self_loop, graph_avg;
+    const float* eps;                             // [L] on the device, or null (learn_eps False)
+    const long long* table;                       // gnm_saliency_table_words(L, m) words
+    const float* Sin; const float* Rin;           // the layer above's S = dpooled / deg and dpooled (Rin: average with
+                                                  // learned eps only); null for the top layer
+    float* Sout; float* Rout;                     // this layer's (l > 0: of dpooled_l; l = 0: of the first Linear's dZ)
+    int lds;                                      // leading dimension of S / R
+    float* out; int ldo;                          // the final launch: dX [N, F0]
+    int final_launch;
+};
+
+__device__ __forceinline__ void sl_split8(const float* f, sl_bf16x8& p1, sl_bf16x8& p2, sl_bf16x8& p3) {
+    unsigned a1[8], a2[8], a3[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        a1[j] = __float_as_uint(f[j]) & 0xFFFF0000u;
+        const float r1 = f[j] - __uint_as_float(a1[j]);
+        a2[j] = __float_as_uint(r1) & 0xFFFF0000u;
+        a3[j] = __float_as_uint(r1 - __uint_as_float(a2[j]));
+    }
+    sl_u32x4 q1, q2, q3;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        q1[j] = __builtin_amdgcn_perm(a1[2 * j + 1], a1[2 * j], 0x07060302u);
+        q2[j] = __builtin_amdgcn_perm(a2[2 * j + 1], a2[2 * j], 0x07060302u);
+        q3[j] = __builtin_amdgcn_perm(a3[2 * j + 1], a3[2 * j], 0x07060302u);
+    }
+    p1 = __builtin_bit_cast(sl_bf16x8, q1); p2 = __builtin_bit_cast(sl_bf16x8, q2); p3 = __builtin_bit_cast(sl_bf16x8, q3);
+}
+
+// acc += T[32 x 16 s ..] x W[16 s .., col], the split-precision product of evallayer.hip (A from the LDS tile, row i of
+// the lane; B = 8 consecutive rows k of W's column `col`, already in fb)
+__device__ __forceinline__ void sl_step(f32x16& acc, const float* T, int i, int h, int s, const float (&fb)[8]) {
+    const int k0 = 16 * s + 8 * h;
+    float fa[8];
+    const float4 v0 = *reinterpret_cast<const float4*>(T + i * kSlTS + k0);
+    const float4 v1 = *reinterpret_cast<const float4*>(T + i * kSlTS + k0 + 4);
+    fa[0] = v0.x; fa[1] = v0.y; fa[2] = v0.z; fa[3] = v0.w; fa[4] = v1.x; fa[5] = v1.y; fa[6] = v1.z; fa[7] = v1.w;
+    sl_bf16x8 a1, a2, a3, b1, b2, b3;
+    sl_split8(fa, a1, a2, a3);
+    sl_split8(fb, b1, b2, b3);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc, 0, 0, 0);      // small terms first
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
+}
+
+__global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p) {
+    __shared__ __attribute__((aligned(16))) float T0[32 * kSlTS];
+    __shared__ __attribute__((aligned(16))) float T1[32 * kSlTS];
+    __shared__ __attribute__((aligned(16))) float part[4][32][33];
+    __shared__ __attribute__((aligned(16))) char lut[128];
+    __shared__ unsigned bitsw[8][256];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 31, h = lane >> 5;
+    const int b = blockIdx.x / p.wmax, rb = blockIdx.x - b * p.wmax;
+    const int row0 = p.node_off[b];
+    const int n = p.node_off[b + 1] - row0;
+    const int W = (n + 31) >> 5;
+    if (rb >= W) return;                          // (also an empty graph)
+    const int H = p.H, l = p.l;
+    const int ksteps = (n + 15) >> 4;
+    if (tid < 16) {            // nibble e -> bf16 (bit 0, bit 1, bit 2, bit 3) as two words
+        const unsigned one = 0x3F80u;
+        sl_u32x2 v;
+        v.x = ((tid & 1) ? one : 0u) | ((tid & 2) ? one << 16 : 0u);
+        v.y = ((tid & 4) ? one : 0u) | ((tid & 8) ? one << 16 : 0u);
+        *reinterpret_cast<sl_u32x2*>(lut + 8 * tid) = v;
+    }
+    // the combine passes: 8 threads per tile row
+    const int row = tid >> 3, c8 = tid & 7;
+    const int vr = min(rb * 32 + row, n - 1);
+    const int grow = row0 + vr;
+    const bool vrow = rb * 32 + row < n;
+    const float deg = p.average ? (float)(p.rowptr[p.b_rp_off[b] + vr + 1] - p.rowptr[p.b_rp_off[b] + vr] + p.self_loop)
+                                : 1.f;
+    const int NCT = H >> 5, KSB = 4 / NCT;
+    // ---- A. Y = Adj^T S over the block's rows (the layer above's gradient, or layer 0's for the final launch) -----
+    const bool agg = p.Sin != nullptr;
+    if (agg) {
+        const int ct = wave % NCT, kh = wave / NCT;
+        const int HPW = (((W + 1) >> 1) + 3) & ~3;
+        {
+            const uint32_t* gbits = p.adj_bits + p.b_tbits_off[b];
+            const sl_u32x4* rp = reinterpret_cast<const sl_u32x4*>(gbits + (size_t)(rb * 32 + i) * (2 * HPW) + h * HPW);
+            const sl_u32x4 z4 = {0u, 0u, 0u, 0u};
+            const sl_u32x4 a0 = rp[0];
+            const sl_u32x4 a1 = HPW > 4 ? rp[1] : z4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { bitsw[j][tid] = a0[j]; bitsw[4 + j][tid] = a1[j]; }
+        }
+        // rows past n read zero: the row offset travels in the VECTOR offset, which the descriptor's range check covers
+        const unsigned sbytes = (unsigned)(((size_t)(n - 1) * p.lds + H) * 4);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(p.Sin) + (size_t)row0 * p.lds, 0, (int)sbytes, 0x00020000);
+        const unsigned svo = (unsigned)((8 * h * p.lds + 32 * ct + i) * 4);
+        const unsigned srow = (unsigned)(p.lds * 4);
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        __syncthreads();                                          // the table
+        auto request = [&](float (&d)[8], int s) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                d[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, svo + (unsigned)(16 * s + j) * srow, 0, 0));
+        };
+        auto multiply = [&](const float (&d)[8], int s) {
+            sl_bf16x8 a1, a2, a3;
+            sl_split8(d, a1, a2, a3);
+            const unsigned pkw = bitsw[s >> 2][tid];
+            const unsigned byte3 = ((pkw >> (8 * (s & 3))) & 0xFFu) << 3;
+            const unsigned lo = byte3 & 0x78u, hi = (byte3 >> 4) & 0x78u;
+            const sl_u32x2 l2 = *reinterpret_cast<const sl_u32x2*>(lut + lo);
+            const sl_u32x2 h2 = *reinterpret_cast<const sl_u32x2*>(lut + hi);
+            const sl_u32x4 q = {l2.x, l2.y, h2.x, h2.y};
+            const sl_bf16x8 bq = __builtin_bit_cast(sl_bf16x8, q);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, bq, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bq, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bq, acc, 0, 0, 0);
+        };
+        float hb0[8], hb1[8], hb2[8], hb3[8];
+        request(hb0, kh); request(hb1, kh + KSB); request(hb2, kh + 2 * KSB);
+#pragma nounroll
+        for (int s = kh; s < ksteps; s += 4 * KSB) {              // wave-uniform
+            request(hb3, s + 3 * KSB);
+            multiply(hb0, s);
+            if (s + KSB < ksteps) { request(hb0, s + 4 * KSB); multiply(hb1, s + KSB); }
+            if (s + 2 * KSB < ksteps) { request(hb1, s + 5 * KSB); multiply(hb2, s + 2 * KSB); }
+            if (s + 3 * KSB < ksteps) { request(hb2, s + 6 * KSB); multiply(hb3, s + 3 * KSB); }
+        }
+        // accumulator (r, lane): column 32 ct + (r & 3) + 8 (r >> 2) + 4 h of S, output row i
+#pragma unroll
+        for (int r = 0; r < 16; ++r) part[wave][i][(r & 3) + 8 * (r >> 2) + 4 * h] = acc[r];
+    }
+    __syncthreads();
+    // ---- B. gradient at h_l (or, final launch, at pooled_0 before W0) -> T0 --------------------------------------
+    {
+        const int le = p.final_launch ? 0 : l + 1;               // the aggregation that read this layer's output
+        const float selfw = p.eps ? 1.f + p.eps[le] : 1.f;       // graphcnn.py:161 (1 + eps[layer]) h
+        const long long* te = p.table + (size_t)(l * p.m + p.m - 1) * kSlLinWords;
+        const float* zo = reinterpret_cast<const float*>(te[2]);
+        const float* sco = reinterpret_cast<const float*>(te[4]);
+        const float* sho = reinterpret_cast<const float*>(te[5]);
+        const int ldz = (int)te[3];
+        const long long* th = p.table + (size_t)p.L * p.m * kSlLinWords + 2 * l;
+        const float* wpred = reinterpret_cast<const float*>(th[0]) + (size_t)p.cls * th[1];
+        const float inv_n = p.graph_avg ? 1.0f / (float)n : 1.f;  // the readout's fp32 1/n (graphcnn.py:123,130)
+        for (int c = c8; c < H; c += 8) {
+            float g = 0.f;
+            if (agg) {
+                float v = 0.f;
+                for (int q = 0; q < KSB; ++q) v += part[(c >> 5) + NCT * q][row][c & 31];
+                const float s = p.Sin[(size_t)grow * p.lds + c];
+                if (p.self_loop) v += s;
+                else v += selfw * (p.Rin ? p.Rin[(size_t)grow * p.lds + c] : s);
+                g = v;
+            }
+            if (!p.final_launch) {
+                g += wpred[c] * inv_n;                             // graphcnn.py:228-231, eval: no dropout
+                const float z = zo[(size_t)grow * ldz + c], sc = sco[c];
+                g = (z * sc + sho[c] > 0.f) ? g * sc : 0.f;        // outer BatchNorm + ReLU (graphcnn.py:163-166)
+            }
+            T0[row * kSlTS + c] = vrow ? g : 0.f;
+        }
+    }
+    // ---- C. the MLP backward: dX_k = dZ_k W_k (W [out, in] as the B operand), inner BatchNorm + ReLU between -------
+    float* Tin = T0;
+    float* Tout = T1;
+    const int kstop = l == 0 ? 1 : 0;
+    if (!p.final_launch) {
+        const int ct = wave % NCT, kh = wave / NCT;
+        const int ncol = 32 * ct + i;
+        const int nst = H >> 4;
+        for (int k = p.m - 1; k >= kstop; --k) {                 // workgroup-uniform
+            const long long* te = p.table + (size_t)(l * p.m + k) * kSlLinWords;
+            const float* Wk = reinterpret_cast<const float*>(te[0]);
+            const int ldw = (int)te[1];
+            __syncthreads();                                      // the input tile complete
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma nounroll
+            for (int s = kh; s < nst; s += KSB) {
+                const int k0 = 16 * s + 8 * h;
+                float fb[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) fb[j] = Wk[(size_t)(k0 + j) * ldw + ncol];
+                sl_step(acc, Tin, i, h, s, fb);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) part[wave][(r & 3) + 8 * (r >> 2) + 4 * h][i] = acc[r];
+            __syncthreads();
+            const float* zp = nullptr; const float* scp = nullptr; const float* shp = nullptr;
+            int ldz = 0;
+            if (k > 0) {                                          // the inner BatchNorm + ReLU of Linear k - 1 (mlp.py:48)
+                const long long* tp = p.table + (size_t)(l * p.m + k - 1) * kSlLinWords;
+                zp = reinterpret_cast<const float*>(tp[2]); ldz = (int)tp[3];
+                scp = reinterpret_cast<const float*>(tp[4]); shp = reinterpret_cast<const float*>(tp[5]);
+            }
+            for (int c = c8; c < H; c += 8) {
+                float v = 0.f;
+                for (int q = 0; q < KSB; ++q) v += part[(c >> 5) + NCT * q][row][c & 31];
+                if (k > 0) {
+                    const float z = zp[(size_t)grow * ldz + c], sc = scp[c];
+                    v = (z * sc + shp[c] > 0.f) ? v * sc : 0.f;
+                }
+                Tout[row * kSlTS + c] = vrow ? v : 0.f;
+            }
+            float* t = Tin; Tin = Tout; Tout = t;
+        }
+        // ---- D. S = g / deg (and g where the self term of the launch below needs it) -------------------------
+        __syncthreads();
+        if (vrow) {
+            for (int c = c8; c < H; c += 8) {
+                const float g = Tin[row * kSlTS + c];
+                p.Sout[(size_t)grow * p.lds + c] = p.average ? g / deg : g;
+                if (p.Rout) p.Rout[(size_t)grow * p.lds + c] = g;
+            }
+        }
+        return;
+    }
+    // ---- the final launch: dX = Y W0 over F0 columns, W0 [H, F0] as the B operand --------------------------------
+    __syncthreads();
+    const long long* t0 = p.table;
+    const float* W0 = reinterpret_cast<const float*>(t0[0]);
+    const int ldw0 = (int)t0[1];
+    const int F0 = p.F0;
+    const int NCO = (F0 + 31) >> 5;
+    const int nst = H >> 4;
+    if (NCO >= 4) {                               // a wave per column tile, whole contraction, straight to memory
+        for (int ct = wave; ct < NCO; ct += 4) {  // wave-uniform
+            const int ncol = 32 * ct + i;
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma nounroll
+            for (int s = 0; s < nst; ++s) {
+                const int k0 = 16 * s + 8 * h;
+                float fb[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) fb[j] = ncol < F0 ? W0[(size_t)(k0 + j) * ldw0 + ncol] : 0.f;
+                sl_step(acc, Tin, i, h, s, fb);
+            }
+            if (ncol < F0) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int rr = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    if (rr < n) p.out[(size_t)(row0 + rr) * p.ldo + ncol] = acc[r];
+                }
+            }
+        }
+        return;
+    }
+    {                                             // 1..3 column tiles: the waves split the contraction
+        const int KS = 4 / NCO;
+        const int ct = wave % NCO, kh = wave / NCO;
+        const int ncol = 32 * ct + i;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        if (ct < NCO && kh < KS) {                // (NCO = 3: the fourth wave idles)
+#pragma nounroll
+            for (int s = kh; s < nst; s += KS) {
+                const int k0 = 16 * s + 8 * h;
+                float fb[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) fb[j] = ncol < F0 ? W0[(size_t)(k0 + j) * ldw0 + ncol] : 0.f;
+                sl_step(acc, Tin, i, h, s, fb);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) part[wave][(r & 3) + 8 * (r >> 2) + 4 * h][i] = acc[r];
+        __syncthreads();
+        if (vrow) {
+            for (int c = c8; c < F0; c += 8) {
+                float v = 0.f;
+                for (int q = 0; q < KS; ++q) v += part[(c >> 5) + NCO * q][row][c & 31];
+                p.out[(size_t)grow * p.ldo + c] = v;
+            }
+        }
+    }
+}
+
+// Words of the device parameter table gnm_saliency reads (see include/gnm_hip.h).
+extern "C" long long gnm_saliency_table_words(int L, int m) { return (long long)L * m * kSlLinWords + 2LL * L; }
+
+// Floats of scratch gnm_saliency needs for N rows of hidden width H: two (S, R) pairs, one per parity of the layer.
+extern "C" long long gnm_saliency_scratch_floats(long long N, int H) { return 4 * N * (long long)H; }
+
+extern "C" int gnm_saliency(const uint32_t* adj_bits, const int64_t* b_tbits_off, const int32_t* node_off,
+                            const int32_t* rowptr, const int64_t* b_rp_off, int B, int n_max, long long N, int F0, int H,
+                            int L, int m, int C, int cls, int average, int self_loop, int graph_avg,
+                            const long long* table, const float* eps, float* scratch, float* dX, int ldx, void* stream) {
+    if (B <= 0) return GNM_OK;
+    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || F0 < 1 || F0 > gnm_linear_max_k(H) ||
+        n_max < 1 || n_max > kSlMaxN || C < 1)
+        return GNM_ERR_UNSUPPORTED;
+    if (cls < 0 || cls >= C || N < 1 || ldx < F0) return GNM_ERR_BAD_ARG;
+    if (!adj_bits || !b_tbits_off || !node_off || !rowptr || !b_rp_off || !table || !scratch || !dX) return GNM_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(adj_bits) & 15) return GNM_ERR_UNSUPPORTED;
+    if ((long long)(n_max + 128) * H * 4 >= (1LL << 31) || N * (long long)(ldx > H ? ldx : H) >= (1LL << 40))
+        return GNM_ERR_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int wmax = (n_max + 31) / 32;
+    const bool need_r = average && !self_loop;    // (1 + eps) dpooled: the undivided gradient too
+    float* S[2] = {scratch, scratch + 2 * N * H};
+    float* R[2] = {scratch + N * H, scratch + 3 * N * H};
+    SlArgs a;
+    memset(&a, 0, sizeof(a));
+    a.adj_bits = adj_bits; a.b_tbits_off = b_tbits_off; a.node_off = node_off; a.rowptr = rowptr; a.b_rp_off = b_rp_off;
+    a.B = B; a.wmax = wmax; a.L = L; a.m = m; a.H = H; a.F0 = F0; a.cls = cls;
+    a.average = average; a.self_loop = self_loop; a.graph_avg = graph_avg;
+    a.eps = eps; a.table = table; a.lds = H;
+    for (int l = L - 1; l >= 0; --l) {
+        const int wr = l & 1, rd = wr ^ 1;
+        a.l = l;
+        a.Sin = l < L - 1 ? S[rd] : nullptr;
+        a.Rin = l < L - 1 && need_r ? R[rd] : nullptr;
+        a.Sout = S[wr];
+        a.Rout = need_r ? R[wr] : nullptr;
+        a.out = nullptr; a.ldo = 0; a.final_launch = 0;
+        hipLaunchKernelGGL(gnm_saliency_layer_kernel, dim3(B * wmax), dim3(256), 0, s, a);
+        GNM_CHECK_LAUNCH();
+    }
+    a.l = 0;
+    a.Sin = S[0];
+    a.Rin = need_r ? R[0] : nullptr;
+    a.Sout = nullptr; a.Rout = nullptr;
+    a.out = dX; a.ldo = ldx; a.final_launch = 1;
+    hipLaunchKernelGGL(gnm_saliency_layer_kernel, dim3(B * wmax), dim3(256), 0, s, a);
+    GNM_CHECK_LAUNCH();
+    return GNM_OK;
+}

@@ -657,6 +657,72 @@ def eval_forward_fused(spec, batch, perm, P, X, want_disc, mode=True):
     return c_logit, d_logit, g_f
 
 
+def saliency_hip_ok(spec, batch, X, P):
+    """can csrc/saliency.hip (gnm_saliency) take this batch?  Else GIN_InfoMaxReg.saliency() differentiates the whole
+    batch through GinInfoMaxFn instead."""
+    if spec.n_max or spec.sync_bn is not None or not X.is_cuda:
+        return False
+    if not getattr(batch, "has_bits", False) or batch.B < 1 or batch.n_max > 416:
+        return False
+    if spec.n_avg and spec.learn_eps and getattr(batch, "iso", False):
+        return False            # the 0/0 row of an isolated node: the autograd path's NaN semantics, not re-derived here
+    H = P["batch_norms.0.weight"].shape[0]
+    return (H in (32, 64, 128) and 1 <= spec.m <= 3 and spec.L <= 16
+            and 1 <= X.shape[1] <= int(lib.gnm_linear_max_k(H)))
+
+
+def saliency_hip(spec, batch, X, P, classes, outs=None):
+    """d score[:, c] / d X (graphcnn.py:254-266 for a whole batch in eval mode) for every c in `classes`: ONE eval
+    forward through the training kernels (encoder_forward, BatchNorm on its running statistics; it leaves every
+    Linear's pre-BatchNorm output z, which give the ReLU masks), then L + 1 launches of gnm_saliency per class.
+    Parameters, buffers and the numpy RNG are not touched.  Returns a list of [N, F0] tensors, one per class (written
+    into `outs` when given: row-contiguous [N, F0] destinations)."""
+    dev = launch_device(X, P["eps"])
+    L, m = spec.L, spec.m
+    N, B = batch.N, batch.B
+    H = P["batch_norms.0.weight"].shape[0]
+    Cn = P["linears_prediction.0.weight"].shape[0]
+    F0 = X.shape[1]
+    f32 = dict(dtype=torch.float32, device=dev)
+    X = X.contiguous()
+    a = batch.arena
+    res = []
+    with torch.no_grad(), _stream_scope(dev):
+        _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
+        words = []
+        for l in range(L):
+            for k in range(m):
+                wn = f"mlps.{l}.linear" if m == 1 else f"mlps.{l}.linears.{k}"
+                W = P[wn + ".weight"]
+                sv = saved[l][2][k]
+                if W.stride(1) != 1 or sv.z.stride(1) != 1:
+                    raise GnmError("Linear weights and outputs must be row-contiguous")
+                words += [W.data_ptr(), W.stride(0), sv.z.data_ptr(), sv.z.stride(0), sv.scale.data_ptr(),
+                          sv.shift.data_ptr()]
+        for l in range(L):
+            wp = P[f"linears_prediction.{l}.weight"]
+            if wp.stride(1) != 1:
+                raise GnmError("classifier weights must be row-contiguous")
+            words += [wp.data_ptr(), wp.stride(0)]
+        assert len(words) == int(lib.gnm_saliency_table_words(L, m))
+        table = torch.tensor(words, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        scratch = torch.empty(int(lib.gnm_saliency_scratch_floats(N, H)), **f32)
+        for ci, c in enumerate(classes):
+            dX = outs[ci] if outs is not None else torch.empty((N, F0), **f32)
+            if dX.shape != (N, F0) or dX.stride(1) != 1:
+                raise GnmError("saliency output must be a row-contiguous [%d, %d] array" % (N, F0))
+            with _timed("saliency_hip", B=B, N=N, F0=F0, H=H):
+                check(lib.gnm_saliency(a.bits.buf.data_ptr(), batch.t_bits_off.data_ptr(), batch.node_off.data_ptr(),
+                                       a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(), B, batch.n_max, N, F0, H, L, m,
+                                       Cn, int(c), int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg),
+                                       table.data_ptr(), P["eps"].data_ptr() if spec.learn_eps else None,
+                                       scratch.data_ptr(), dX.data_ptr(), dX.stride(0), _stream()), "gnm_saliency")
+            res.append(dX)
+    # (the forward's arrays and the table are freed here with launches still queued: the caching allocator hands
+    # their memory only to later work on the same stream)
+    return res
+
+
 class GinInfoMaxFn(torch.autograd.Function):
     """(P0, X, *params) -> (c_logit [B,C], d_logit [2N,1], g_f [B,L*H])."""
 

@@ -33,7 +33,7 @@ from mlp import MLP  # noqa: E402
 from discriminator import Discriminator  # noqa: E402
 from gnm.arena import GraphArena  # noqa: E402
 from gnm.core import (DISC_UNIT, DiscUnit, GinInfoMaxFn, GinSpec, eval_forward_fused,  # noqa: E402
-                      eval_fused_ok)
+                      eval_fused_ok, saliency_hip, saliency_hip_ok)
 
 __all__ = ["GIN_InfoMaxReg", "GraphCNN", "MLP", "Discriminator"]
 
@@ -277,6 +277,121 @@ class GIN_InfoMaxReg(nn.Module):
             return torch.cat(out, 0) if out else torch.zeros((0, 0), device=self.eps.device)
         finally:
             self.train(was_training)
+
+    def saliency(self, graphs, cls, batch_size=256):
+        """Input saliency of many graphs in batches: what main.py:60-68 builds from one compute_saliency([g], c) call
+        per graph and class (not in the reference).  Eval mode -- BatchNorm on its running statistics, no dropout --
+        so graphs do not interact and a batch gives each graph's per-graph result (to fp32 rounding).
+
+        cls: an int, or a sequence of ints such as (0, 1); the forward pass of a batch is shared by all of them.
+        Returns a float32 device tensor [len(graphs), n, F0] for an int `cls` and [len(cls), len(graphs), n, F0] for a
+        sequence -- np.stack of compute_saliency's results.  Graphs of different node counts are allowed (no
+        discriminator is involved); the result is then a list of [n_g, F0] tensors (a list of such lists for a
+        sequence `cls`).
+
+        Unlike compute_saliency, which leaves the model in eval mode and zeroes and then fills every parameter's .grad,
+        this computes only the input gradient: no .grad is touched, BatchNorm buffers and the numpy RNG are left alone,
+        and the model's train / eval mode is restored on exit.  The route each batch took ("hip": csrc/saliency.hip;
+        "autograd": the whole batch differentiated through GinInfoMaxFn, for shapes the kernel declines -- max
+        neighbour pooling, graphs over 416 nodes or without a bit adjacency, H outside {32, 64, 128}, ...) is left in
+        self.saliency_routes.  A graph with a non-finite feature takes the autograd route on its own (one more
+        "autograd" entry), so its NaN / inf pattern is compute_saliency's."""
+        single = isinstance(cls, (int, np.integer))
+        classes = [int(cls)] if single else [int(c) for c in cls]
+        n_cls = self.linears_prediction[0].out_features
+        if len(graphs) == 0:
+            raise ValueError("saliency: empty list of graphs")
+        if not classes:
+            raise ValueError("saliency: empty sequence of classes")
+        for c in classes:
+            if not 0 <= c < n_cls:
+                raise ValueError("saliency: class %d out of range for a %d-class model" % (c, n_cls))
+        if batch_size < 1:
+            raise ValueError("saliency: batch_size must be positive")
+        was_training = self.training
+        self.eval()
+        try:
+            names, tensors, buffers = self._param_lists()
+            P = dict(zip(names, tensors))
+            P.update(buffers)
+            ns = [len(g.g) for g in graphs]
+            ragged = any(k != ns[0] for k in ns)
+            F0 = self.mlps[0].linear.in_features if self.num_mlp_layers == 1 else self.mlps[0].linears[0].in_features
+            dev = self.eps.device
+            full = None if ragged else torch.empty((len(classes), len(graphs), ns[0], F0), dtype=torch.float32,
+                                                   device=dev)
+            per_graph = [[] for _ in classes]
+            routes = []
+            for i0 in range(0, len(graphs), batch_size):
+                chunk = graphs[i0:i0 + batch_size]
+                batch = self._batch_of(chunk)
+                dst = None if full is None else [full[ci, i0:i0 + len(chunk)].view(-1, F0) for ci in range(len(classes))]
+                res = self._saliency_batch(chunk, batch, P, classes, dst, routes)
+                if full is None:
+                    offs = np.asarray(batch.node_off_host)
+                    for ci, r in enumerate(res):
+                        per_graph[ci] += [r[offs[j]:offs[j + 1]] for j in range(len(chunk))]
+            self.saliency_routes = routes
+            if full is not None:
+                return full[0] if single else full
+            return per_graph[0] if single else per_graph
+        finally:
+            self.train(was_training)
+
+    def _saliency_batch(self, chunk, batch, P, classes, dst, routes):
+        """saliency() of one batch: a list of [N, F0] tensors (written into dst when given), one per class"""
+        X = batch.arena.features(batch)
+        if not saliency_hip_ok(self._spec, batch, X, P):
+            routes.append("autograd")
+            res = self._saliency_autograd(batch, classes)
+        elif bool(torch.isfinite(X).all()):
+            routes.append("hip")
+            return saliency_hip(self._spec, batch, X.detach(), P, classes, outs=dst)
+        else:
+            # a graph with a non-finite feature: its saliency is whatever compute_saliency's backward makes of the
+            # NaN / inf (the kernel's masks would quietly turn it into zeros), so such a graph takes the autograd route
+            # on its own -- exactly compute_saliency's kernels -- and the others stay on the kernel
+            B = batch.B
+            counts = torch.as_tensor(np.diff(batch.node_off_host), device=X.device)
+            gid = torch.repeat_interleave(torch.arange(B, device=X.device), counts)
+            bad = torch.zeros(B, dtype=torch.int32, device=X.device).index_add_(
+                0, gid, (~torch.isfinite(X).all(1)).to(torch.int32)).cpu().numpy() > 0
+            parts = [None] * B
+            good = [j for j in range(B) if not bad[j]]
+            if good:
+                sub = self._batch_of([chunk[j] for j in good])
+                routes.append("hip")
+                r = saliency_hip(self._spec, sub, sub.arena.features(sub).detach(), P, classes)
+                for k, j in enumerate(good):
+                    parts[j] = [x[sub.node_off_host[k]:sub.node_off_host[k + 1]] for x in r]
+            for j in range(B):
+                if bad[j]:
+                    routes.append("autograd")
+                    parts[j] = self._saliency_autograd(self._batch_of([chunk[j]]), classes)
+            res = [torch.cat([parts[j][ci] for j in range(B)], 0) for ci in range(len(classes))]
+        if dst is not None:
+            for d, r in zip(dst, res):
+                d.copy_(r)
+        return res
+
+    def _saliency_autograd(self, batch, classes):
+        """saliency()'s route for every shape csrc/saliency.hip declines: d score[:, c] / d X of the whole batch through
+        GinInfoMaxFn's backward (exact: graphs are independent in eval mode), one forward per class.  torch.autograd.grad
+        with inputs=X leaves every parameter's .grad alone; a gradient sink (data-parallel training) is set aside."""
+        sink, self._spec.grad_sink = self._spec.grad_sink, None
+        try:
+            out = []
+            for c in classes:
+                X = batch.arena.features(batch).detach().requires_grad_()
+                with torch.enable_grad():
+                    score, _, _ = self._run(batch, X, np.arange(batch.B, dtype=np.int64), want_disc=False)
+                    seed = torch.zeros_like(score)
+                    seed[:, c] = 1
+                    (g,) = torch.autograd.grad(score, X, seed)
+                out.append(g)
+            return out
+        finally:
+            self._spec.grad_sink = sink
 
     # ------------------------------------------------------------------ evaluation replay
     EVAL_REPLAY_MAX_B = 64          # larger eval batches are GPU-bound anyway (and hold more captured activations)

@@ -310,6 +310,27 @@ int gnm_eval_layers(const uint32_t* adj_bits, const int64_t* b_bits_off, const i
                     float* hidden, long long hidden_stride, int ldh, float* scratch, float* g_f, int ldgf, float* c_sig,
                     float* c_logit, int ldc, void* stream);
 
+/* ---- Eval-mode input saliency (graphcnn.py:254-299 compute_saliency, main.py:60-68) ---------------------------
+ * d score[b, cls] / d X for every graph b of a batch in eval mode (BatchNorm on its running statistics, no dropout):
+ * L launches from the top GIN layer down, a workgroup per (graph, 32-row block), and one that forms dX.  The masks and
+ * BatchNorm scales come from the eval forward's per-Linear outputs (gnm_linear_fwd z, gnm_bn_finalize scale / shift);
+ * only the input gradient is computed -- no weight, BatchNorm or head gradient.
+ * table: gnm_saliency_table_words(L, m) DEVICE words: per layer l and Linear k (l-major) 6 words (weight [out, in]
+ * row-major, its leading dimension, the forward's pre-BatchNorm output z [N, out], z's leading dimension, the folded
+ * scale gamma * rstd and shift of the BatchNorm behind the Linear), then per layer 2 words (classifier weight [C, H],
+ * its leading dimension).  b_tbits_off: the TRANSPOSED bit matrices (equal to the forward ones for symmetric graphs);
+ * rowptr / b_rp_off: the forward CSR (degrees under neighbour "average").  eps: [L] or NULL (self loops).
+ * scratch: gnm_saliency_scratch_floats(N, H) floats.  dX: OUTPUT [N, F0], leading dimension ldx.
+ * GNM_ERR_UNSUPPORTED (nothing launched): H not in {32, 64, 128}, m outside 1..3, L > 16, F0 > gnm_linear_max_k(H),
+ * a graph of more than 416 nodes (every graph needs a bit adjacency).  GNM_ERR_BAD_ARG: cls outside [0, C).
+ * Arithmetic: three-plane bf16 splits with fp32 accumulation; agrees with the autograd path to fp32 rounding. */
+long long gnm_saliency_table_words(int L, int m);
+long long gnm_saliency_scratch_floats(long long N, int H);
+int gnm_saliency(const uint32_t* adj_bits, const int64_t* b_tbits_off, const int32_t* node_off, const int32_t* rowptr,
+                 const int64_t* b_rp_off, int B, int n_max, long long N, int F0, int H, int L, int m, int C, int cls,
+                 int average, int self_loop, int graph_avg, const long long* table, const float* eps, float* scratch,
+                 float* dX, int ldx, void* stream);
+
 /* ---- Infomax discriminator (discriminator.py:19-38, graphcnn.py:233-246) ------------
  * hptrs_host: HOST array of L device pointers to the per-layer [N,H] hidden states
  * (n_f is never concatenated).  A layer may instead be given as the pre-BatchNorm output Z_l of its last Linear
