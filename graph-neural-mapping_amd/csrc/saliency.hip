@@ -20,6 +20,8 @@
 //      so the final launch aggregates at width H and multiplies by W0 last, instead of aggregating F0-wide rows.
 // The masks come from the pre-BatchNorm outputs z of every Linear, which the eval forward (gnm/core.py encoder_forward)
 // leaves in memory anyway.
+// gnm_saliency_maps runs the same layer launches (kMaps = true) to form the gradient class activation map
+// sum_l <dscore/dh_l[v], h_l[v]> in stage B instead of dX: L launches, no final one.
 #include "gnm_common.h"
 #include <string.h>
 
@@ -47,6 +49,7 @@ struct SlArgs {
     int lds;                                      // leading dimension of S / R
     float* out; int ldo;                          // the final launch: dX [N, F0]
     int final_launch;
+    float* gcam;                                  // gnm_saliency_maps: OUTPUT [N], the gradient class activation map
 };
 
 __device__ __forceinline__ void sl_split8(const float* f, sl_bf16x8& p1, sl_bf16x8& p2, sl_bf16x8& p3) {
@@ -87,6 +90,10 @@ __device__ __forceinline__ void sl_step(f32x16& acc, const float* T, int i, int 
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
 }
 
+// kMaps (gnm_saliency_maps): stage B also forms the row's gradient class activation <dscore/dh_l[v], h_l[v]>
+// (graphcnn.py:284,289) and stores (top layer) or adds it to p.gcam[v]; layer 0 stops there.  kMaps = false is
+// gnm_saliency's kernel, whose code the other form leaves as it was.
+template <bool kMaps>
 __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p) {
     __shared__ __attribute__((aligned(16))) float T0[32 * kSlTS];
     __shared__ __attribute__((aligned(16))) float T1[32 * kSlTS];
@@ -189,6 +196,7 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
         const long long* th = p.table + (size_t)p.L * p.m * kSlLinWords + 2 * l;
         const float* wpred = reinterpret_cast<const float*>(th[0]) + (size_t)p.cls * th[1];
         const float inv_n = p.graph_avg ? 1.0f / (float)n : 1.f;  // the readout's fp32 1/n (graphcnn.py:123,130)
+        float dot = 0.f;                                          // (kMaps) this lane's part of <g, h_l> for the row
         for (int c = c8; c < H; c += 8) {
             float g = 0.f;
             if (agg) {
@@ -202,9 +210,18 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
             if (!p.final_launch) {
                 g += wpred[c] * inv_n;                             // graphcnn.py:228-231, eval: no dropout
                 const float z = zo[(size_t)grow * ldz + c], sc = sco[c];
-                g = (z * sc + sho[c] > 0.f) ? g * sc : 0.f;        // outer BatchNorm + ReLU (graphcnn.py:163-166)
+                const float y = z * sc + sho[c];
+                if constexpr (kMaps) dot += g * gnm_relu(y);       // g = dscore / dh_l, before the mask
+                g = (y > 0.f) ? g * sc : 0.f;                      // outer BatchNorm + ReLU (graphcnn.py:163-166)
             }
             T0[row * kSlTS + c] = vrow ? g : 0.f;
+        }
+        if constexpr (kMaps) {                                    // the row's 8 lanes: a fixed butterfly
+            dot += __shfl_xor(dot, 4, 8);
+            dot += __shfl_xor(dot, 2, 8);
+            dot += __shfl_xor(dot, 1, 8);
+            if (c8 == 0 && vrow) p.gcam[grow] = l == p.L - 1 ? dot : p.gcam[grow] + dot;   // layers L-1 .. 0, in order
+            if (l == 0) return;                                   // layer 0's map term needs no gradient below it
         }
     }
     // ---- C. the MLP backward: dX_k = dZ_k W_k (W [out, in] as the B operand), inner BatchNorm + ReLU between -------
@@ -363,7 +380,7 @@ extern "C" int gnm_saliency(const uint32_t* adj_bits, const int64_t* b_tbits_off
         a.Sout = S[wr];
         a.Rout = need_r ? R[wr] : nullptr;
         a.out = nullptr; a.ldo = 0; a.final_launch = 0;
-        hipLaunchKernelGGL(gnm_saliency_layer_kernel, dim3(B * wmax), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(gnm_saliency_layer_kernel<false>, dim3(B * wmax), dim3(256), 0, s, a);
         GNM_CHECK_LAUNCH();
     }
     a.l = 0;
@@ -371,7 +388,45 @@ extern "C" int gnm_saliency(const uint32_t* adj_bits, const int64_t* b_tbits_off
     a.Rin = need_r ? R[0] : nullptr;
     a.Sout = nullptr; a.Rout = nullptr;
     a.out = dX; a.ldo = ldx; a.final_launch = 1;
-    hipLaunchKernelGGL(gnm_saliency_layer_kernel, dim3(B * wmax), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(gnm_saliency_layer_kernel<false>, dim3(B * wmax), dim3(256), 0, s, a);
     GNM_CHECK_LAUNCH();
+    return GNM_OK;
+}
+
+// The gradient class activation map of class cls (graphcnn.py:284,288-289): gcam[v] = sum_l <dscore/dh_l[v], h_l[v]>.
+// gnm_saliency's layer launches with the map formed in stage B; no dX launch, and layer 0 stops after stage B.
+extern "C" int gnm_saliency_maps(const uint32_t* adj_bits, const int64_t* b_tbits_off, const int32_t* node_off,
+                                 const int32_t* rowptr, const int64_t* b_rp_off, int B, int n_max, long long N, int H,
+                                 int L, int m, int C, int cls, int average, int self_loop, int graph_avg,
+                                 const long long* table, const float* eps, float* scratch, float* gcam, void* stream) {
+    if (B <= 0) return GNM_OK;
+    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || n_max < 1 || n_max > kSlMaxN || C < 1)
+        return GNM_ERR_UNSUPPORTED;
+    if (cls < 0 || cls >= C || N < 1) return GNM_ERR_BAD_ARG;
+    if (!adj_bits || !b_tbits_off || !node_off || !rowptr || !b_rp_off || !table || !scratch || !gcam)
+        return GNM_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(adj_bits) & 15) return GNM_ERR_UNSUPPORTED;
+    if ((long long)(n_max + 128) * H * 4 >= (1LL << 31) || N * (long long)H >= (1LL << 40)) return GNM_ERR_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int wmax = (n_max + 31) / 32;
+    const bool need_r = average && !self_loop;
+    float* S[2] = {scratch, scratch + 2 * N * H};
+    float* R[2] = {scratch + N * H, scratch + 3 * N * H};
+    SlArgs a;
+    memset(&a, 0, sizeof(a));
+    a.adj_bits = adj_bits; a.b_tbits_off = b_tbits_off; a.node_off = node_off; a.rowptr = rowptr; a.b_rp_off = b_rp_off;
+    a.B = B; a.wmax = wmax; a.L = L; a.m = m; a.H = H; a.F0 = 0; a.cls = cls;
+    a.average = average; a.self_loop = self_loop; a.graph_avg = graph_avg;
+    a.eps = eps; a.table = table; a.lds = H; a.gcam = gcam;
+    for (int l = L - 1; l >= 0; --l) {
+        const int wr = l & 1, rd = wr ^ 1;
+        a.l = l;
+        a.Sin = l < L - 1 ? S[rd] : nullptr;
+        a.Rin = l < L - 1 && need_r ? R[rd] : nullptr;
+        a.Sout = S[wr];
+        a.Rout = need_r ? R[wr] : nullptr;
+        hipLaunchKernelGGL(gnm_saliency_layer_kernel<true>, dim3(B * wmax), dim3(256), 0, s, a);
+        GNM_CHECK_LAUNCH();
+    }
     return GNM_OK;
 }

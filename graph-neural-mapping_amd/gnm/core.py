@@ -671,6 +671,28 @@ def saliency_hip_ok(spec, batch, X, P):
             and 1 <= X.shape[1] <= int(lib.gnm_linear_max_k(H)))
 
 
+def _saliency_table_words(spec, P, saved):
+    """gnm_saliency's / gnm_saliency_maps' parameter table (include/gnm_hip.h) over an eval forward's `saved`"""
+    L, m = spec.L, spec.m
+    words = []
+    for l in range(L):
+        for k in range(m):
+            wn = f"mlps.{l}.linear" if m == 1 else f"mlps.{l}.linears.{k}"
+            W = P[wn + ".weight"]
+            sv = saved[l][2][k]
+            if W.stride(1) != 1 or sv.z.stride(1) != 1:
+                raise GnmError("Linear weights and outputs must be row-contiguous")
+            words += [W.data_ptr(), W.stride(0), sv.z.data_ptr(), sv.z.stride(0), sv.scale.data_ptr(),
+                      sv.shift.data_ptr()]
+    for l in range(L):
+        wp = P[f"linears_prediction.{l}.weight"]
+        if wp.stride(1) != 1:
+            raise GnmError("classifier weights must be row-contiguous")
+        words += [wp.data_ptr(), wp.stride(0)]
+    assert len(words) == int(lib.gnm_saliency_table_words(L, m))
+    return words
+
+
 def saliency_hip(spec, batch, X, P, classes, outs=None):
     """d score[:, c] / d X (graphcnn.py:254-266 for a whole batch in eval mode) for every c in `classes`: ONE eval
     forward through the training kernels (encoder_forward, BatchNorm on its running statistics; it leaves every
@@ -689,23 +711,8 @@ def saliency_hip(spec, batch, X, P, classes, outs=None):
     res = []
     with torch.no_grad(), _stream_scope(dev):
         _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
-        words = []
-        for l in range(L):
-            for k in range(m):
-                wn = f"mlps.{l}.linear" if m == 1 else f"mlps.{l}.linears.{k}"
-                W = P[wn + ".weight"]
-                sv = saved[l][2][k]
-                if W.stride(1) != 1 or sv.z.stride(1) != 1:
-                    raise GnmError("Linear weights and outputs must be row-contiguous")
-                words += [W.data_ptr(), W.stride(0), sv.z.data_ptr(), sv.z.stride(0), sv.scale.data_ptr(),
-                          sv.shift.data_ptr()]
-        for l in range(L):
-            wp = P[f"linears_prediction.{l}.weight"]
-            if wp.stride(1) != 1:
-                raise GnmError("classifier weights must be row-contiguous")
-            words += [wp.data_ptr(), wp.stride(0)]
-        assert len(words) == int(lib.gnm_saliency_table_words(L, m))
-        table = torch.tensor(words, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        table = torch.tensor(_saliency_table_words(spec, P, saved), dtype=torch.int64).pin_memory().to(
+            dev, non_blocking=True)
         scratch = torch.empty(int(lib.gnm_saliency_scratch_floats(N, H)), **f32)
         for ci, c in enumerate(classes):
             dX = outs[ci] if outs is not None else torch.empty((N, F0), **f32)
@@ -721,6 +728,91 @@ def saliency_hip(spec, batch, X, P, classes, outs=None):
     # (the forward's arrays and the table are freed here with launches still queued: the caching allocator hands
     # their memory only to later work on the same stream)
     return res
+
+
+def class_activation_hip(spec, batch, X, P, classes):
+    """The per-node class activation maps cam[v] = p_g sum_l <h_l[v], linears_prediction[l].weight[c]> of a whole batch
+    (graphcnn.py:288 class_activation) for every c in `classes`: ONE eval forward through the training kernels
+    (encoder_forward, BatchNorm on its running statistics), then gnm_class_activation, which re-forms each h_l from the
+    layer's z, scale and shift.  Any neighbour pooling or adjacency form.  Parameters, buffers and the numpy RNG are not
+    touched.  Returns a float32 [len(classes), N] tensor."""
+    dev = launch_device(X, P["eps"])
+    L, m = spec.L, spec.m
+    N, B = batch.N, batch.B
+    H = P["batch_norms.0.weight"].shape[0]
+    Cn = P["linears_prediction.0.weight"].shape[0]
+    X = X.contiguous()
+    out = torch.empty((len(classes), N), dtype=torch.float32, device=dev)
+    with torch.no_grad(), _stream_scope(dev):
+        _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
+        words = []
+        for l in range(L):
+            sv = saved[l][2][m - 1]
+            wp = P[f"linears_prediction.{l}.weight"]
+            if sv.z.stride(1) != 1 or wp.stride(1) != 1:
+                raise GnmError("layer outputs and classifier weights must be row-contiguous")
+            words += [sv.z.data_ptr(), sv.z.stride(0), sv.scale.data_ptr(), sv.shift.data_ptr(), wp.data_ptr(),
+                      wp.stride(0)]
+        assert len(words) == int(lib.gnm_class_activation_table_words(L))
+        table = torch.tensor(words, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        step = int(lib.gnm_class_activation_max_classes())
+        for j0 in range(0, len(classes), step):
+            cls = [int(c) for c in classes[j0:j0 + step]]
+            dst = out[j0:j0 + len(cls)]
+            with _timed("class_activation_hip", B=B, N=N, H=H, C=len(cls)):
+                check(lib.gnm_class_activation(batch.node_off.data_ptr(), B, batch.n_max, N, H, L, Cn,
+                                               (C.c_int * len(cls))(*cls), len(cls), int(spec.g_avg),
+                                               table.data_ptr(), dst.data_ptr(), dst.stride(0), _stream()),
+                      "gnm_class_activation")
+    return out
+
+
+def saliency_maps_decline(spec, batch, X, P):
+    """None if gnm_saliency_maps takes this batch, else the condition it declines (the shapes saliency_hip_ok takes,
+    the input width aside: the gradient maps never form dX)."""
+    H = P["batch_norms.0.weight"].shape[0]
+    if spec.n_max:
+        return "max neighbour pooling"
+    if not getattr(batch, "has_bits", False) or batch.n_max > 416:
+        return "a graph of more than 416 nodes or without a bit adjacency"
+    if H not in (32, 64, 128):
+        return "hidden_dim %d not in {32, 64, 128}" % H
+    if spec.n_avg and spec.learn_eps and getattr(batch, "iso", False):
+        return "average neighbour pooling with learned eps and an isolated node"
+    if not 1 <= spec.m <= 3 or spec.L > 16:
+        return "num_mlp_layers outside 1..3 or more than 16 layers"
+    if spec.sync_bn is not None:
+        return "synchronised BatchNorm"
+    return None
+
+
+def saliency_maps_hip(spec, batch, X, P, classes):
+    """The gradient class activation maps gcam[v] = sum_l <d score[:, c] / d h_l[v], h_l[v]> of a whole batch
+    (graphcnn.py:284,289 grad_class_activation: h.grad on the retained hidden_rep[l] of compute_saliency) for every c
+    in `classes`: one eval forward (encoder_forward), then L launches of gnm_saliency_maps per class.  Parameters,
+    buffers and the numpy RNG are not touched.  Returns a float32 [len(classes), N] tensor."""
+    dev = launch_device(X, P["eps"])
+    L, m = spec.L, spec.m
+    N, B = batch.N, batch.B
+    H = P["batch_norms.0.weight"].shape[0]
+    Cn = P["linears_prediction.0.weight"].shape[0]
+    X = X.contiguous()
+    a = batch.arena
+    out = torch.empty((len(classes), N), dtype=torch.float32, device=dev)
+    with torch.no_grad(), _stream_scope(dev):
+        _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
+        table = torch.tensor(_saliency_table_words(spec, P, saved), dtype=torch.int64).pin_memory().to(
+            dev, non_blocking=True)
+        scratch = torch.empty(int(lib.gnm_saliency_scratch_floats(N, H)), dtype=torch.float32, device=dev)
+        for ci, c in enumerate(classes):
+            with _timed("saliency_maps_hip", B=B, N=N, H=H):
+                check(lib.gnm_saliency_maps(a.bits.buf.data_ptr(), batch.t_bits_off.data_ptr(),
+                                            batch.node_off.data_ptr(), a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(),
+                                            B, batch.n_max, N, H, L, m, Cn, int(c), int(spec.n_avg),
+                                            int(not spec.learn_eps), int(spec.g_avg), table.data_ptr(),
+                                            P["eps"].data_ptr() if spec.learn_eps else None, scratch.data_ptr(),
+                                            out[ci].data_ptr(), _stream()), "gnm_saliency_maps")
+    return out
 
 
 class GinInfoMaxFn(torch.autograd.Function):

@@ -32,8 +32,9 @@ for _p in (_PKG, _HERE):
 from mlp import MLP  # noqa: E402
 from discriminator import Discriminator  # noqa: E402
 from gnm.arena import GraphArena  # noqa: E402
-from gnm.core import (DISC_UNIT, DiscUnit, GinInfoMaxFn, GinSpec, eval_forward_fused,  # noqa: E402
-                      eval_fused_ok, saliency_hip, saliency_hip_ok)
+from gnm.core import (DISC_UNIT, DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip,  # noqa: E402
+                      eval_forward_fused, eval_fused_ok, launch_device, saliency_hip, saliency_hip_ok, saliency_maps_decline,
+                      saliency_maps_hip)
 
 __all__ = ["GIN_InfoMaxReg", "GraphCNN", "MLP", "Discriminator"]
 
@@ -392,6 +393,95 @@ class GIN_InfoMaxReg(nn.Module):
             return out
         finally:
             self._spec.grad_sink = sink
+
+    CAM_KINDS = ("activation", "gradient")
+
+    def class_activation(self, graphs, cls, kind="activation", batch_size=256):
+        """Per-node class activation maps of many graphs in batches: the two [n] vectors compute_saliency allocates
+        (graphcnn.py:284,288-289) and never fills, plotted as method 'cam' by evaluate/visualize_saliency.py:33.  Eval
+        mode -- BatchNorm on its running statistics, no dropout -- so a batch gives each graph's per-graph result.
+
+        kind="activation" (class_activation): cam[v] = p_g sum_l <h_l[v], linears_prediction[l].weight[c]>, p_g = 1 for
+        sum graph pooling and the fp32 1/n_g for average; sum_v cam[v] + sum_l linears_prediction[l].bias[c] is the eval
+        logit.  Every neighbour pooling and graph size the forward takes (csrc/cam.hip).
+        kind="gradient" (grad_class_activation): gcam[v] = sum_l <d score_c / d h_l[v], h_l[v]>, the full gradient at
+        h_l -- the h.grad compute_saliency([g], c) leaves on its retained hidden_rep[l] (csrc/saliency.hip,
+        gnm_saliency_maps).  The shapes saliency()'s kernel takes; any other batch raises ValueError naming the
+        condition (max pooling, n > 416 or no bit adjacency, hidden_dim not in {32, 64, 128}, average pooling with
+        learned eps and an isolated node).  A graph with a non-finite feature gets an all-NaN map.
+
+        cls: an int, or a sequence of ints; one forward per batch serves all of them.  Returns a float32 device tensor
+        [len(graphs), n] for an int `cls` and [len(cls), len(graphs), n] for a sequence; for graphs of different node
+        counts a list of [n_g] tensors (a list of such lists for a sequence `cls`).  No parameter .grad, BatchNorm
+        buffer or numpy RNG state is touched, and the train / eval mode is restored on exit."""
+        single = isinstance(cls, (int, np.integer))
+        classes = [int(cls)] if single else [int(c) for c in cls]
+        n_cls = self.linears_prediction[0].out_features
+        if kind not in self.CAM_KINDS:
+            raise ValueError("class_activation: kind must be one of %s, not %r" % (self.CAM_KINDS, kind))
+        if len(graphs) == 0:
+            raise ValueError("class_activation: empty list of graphs")
+        if not classes:
+            raise ValueError("class_activation: empty sequence of classes")
+        for c in classes:
+            if not 0 <= c < n_cls:
+                raise ValueError("class_activation: class %d out of range for a %d-class model" % (c, n_cls))
+        if batch_size < 1:
+            raise ValueError("class_activation: batch_size must be positive")
+        was_training = self.training
+        self.eval()
+        try:
+            names, tensors, buffers = self._param_lists()
+            P = dict(zip(names, tensors))
+            P.update(buffers)
+            ns = [len(g.g) for g in graphs]
+            ragged = any(k != ns[0] for k in ns)
+            full = None if ragged else torch.empty((len(classes), len(graphs), ns[0]), dtype=torch.float32,
+                                                   device=self.eps.device)
+            per_graph = [[] for _ in classes]
+            for i0 in range(0, len(graphs), batch_size):
+                chunk = graphs[i0:i0 + batch_size]
+                batch = self._batch_of(chunk)
+                res = self._cam_batch(chunk, batch, P, classes, kind)          # [len(classes), N]
+                if full is not None:
+                    full[:, i0:i0 + len(chunk)] = res.view(len(classes), len(chunk), ns[0])
+                else:
+                    offs = np.asarray(batch.node_off_host)
+                    for ci in range(len(classes)):
+                        per_graph[ci] += [res[ci, offs[j]:offs[j + 1]] for j in range(len(chunk))]
+            if full is not None:
+                return full[0] if single else full
+            return per_graph[0] if single else per_graph
+        finally:
+            self.train(was_training)
+
+    def _cam_batch(self, chunk, batch, P, classes, kind):
+        """class_activation() of one batch: [len(classes), N]"""
+        X = batch.arena.features(batch).detach()
+        launch_device(X, P["eps"])                          # no CPU fallback: GnmError before any shape question
+        if kind == "activation":
+            return class_activation_hip(self._spec, batch, X, P, classes)
+        why = saliency_maps_decline(self._spec, batch, X, P)
+        if why is not None:
+            raise ValueError("class_activation(kind='gradient') does not cover this batch: %s" % why)
+        if bool(torch.isfinite(X).all()):
+            return saliency_maps_hip(self._spec, batch, X, P, classes)
+        # a graph with a non-finite feature: an all-NaN map (its ReLU masks are meaningless); the others on a batch of
+        # their own, so their maps are those of a clean batch
+        B = batch.B
+        counts = torch.as_tensor(np.diff(batch.node_off_host), device=X.device)
+        gid = torch.repeat_interleave(torch.arange(B, device=X.device), counts)
+        bad = torch.zeros(B, dtype=torch.int32, device=X.device).index_add_(
+            0, gid, (~torch.isfinite(X).all(1)).to(torch.int32)).cpu().numpy() > 0
+        offs = np.asarray(batch.node_off_host)
+        out = torch.full((len(classes), batch.N), float("nan"), dtype=torch.float32, device=X.device)
+        good = [j for j in range(B) if not bad[j]]
+        if good:
+            sub = self._batch_of([chunk[j] for j in good])
+            r = saliency_maps_hip(self._spec, sub, sub.arena.features(sub).detach(), P, classes)
+            for k, j in enumerate(good):
+                out[:, offs[j]:offs[j + 1]] = r[:, sub.node_off_host[k]:sub.node_off_host[k + 1]]
+        return out
 
     # ------------------------------------------------------------------ evaluation replay
     EVAL_REPLAY_MAX_B = 64          # larger eval batches are GPU-bound anyway (and hold more captured activations)

@@ -331,6 +331,37 @@ int gnm_saliency(const uint32_t* adj_bits, const int64_t* b_tbits_off, const int
                  int average, int self_loop, int graph_avg, const long long* table, const float* eps, float* scratch,
                  float* dX, int ldx, void* stream);
 
+/* ---- Eval-mode per-node class activation maps (graphcnn.py:284,288-289; plotted as 'cam' by
+ * evaluate/visualize_saliency.py:33) --------------------------------------------------------------------------------
+ * The two [N] per-node vectors the reference's compute_saliency allocates (class_activation, grad_class_activation)
+ * and never fills, for every graph of a batch in eval mode (BatchNorm on its running statistics, no dropout).
+ *
+ * gnm_class_activation: out[j * ldo + v] = p_g * sum_l <h_l[v], W_l[cls[j]]> for j < ncls, h_l = relu(z_l * scale_l +
+ * shift_l) the output of GIN layer l, W_l = linears_prediction[l].weight, p_g = 1 or (graph_avg) the fp32 1 / n_g.
+ * An exact decomposition of the eval logit: sum_v out[v] + sum_l b_l[c] = c_logit[g, c].  One launch, a workgroup per
+ * (graph, 64-row block), fixed summation order (deterministic).  It reads only z, scale, shift, the classifier rows
+ * and node_off: any neighbour pooling or adjacency form.
+ * table: gnm_class_activation_table_words(L) DEVICE words, per layer l 6 words: the pre-BatchNorm output z [N, H] of
+ * layer l's last Linear, z's leading dimension, the folded scale gamma * rstd and shift of batch_norms[l], the
+ * classifier weight [C, H] and its leading dimension.  cls: HOST array of ncls class indices,
+ * 1 <= ncls <= gnm_class_activation_max_classes().  out: OUTPUT [ncls, ldo], ldo >= N.
+ * GNM_ERR_BAD_ARG (nothing launched): H not a multiple of 4 in [4, 128], L outside 1..16, a class outside [0, C),
+ * ncls out of range, ldo < N, a NULL array.
+ *
+ * gnm_saliency_maps: gcam[v] = sum_l <d score[g, cls] / d h_l[v], h_l[v]>, the full gradient at h_l (through every
+ * layer above), i.e. the h.grad compute_saliency([g], cls) leaves on its retained hidden_rep[l].  gnm_saliency's layer
+ * launches with the row dot formed in stage B (L launches; no dX launch); the arguments are gnm_saliency's, with the
+ * same table (gnm_saliency_table_words) and scratch (gnm_saliency_scratch_floats), minus F0 / dX / ldx, plus
+ * gcam: OUTPUT [N].  GNM_ERR_UNSUPPORTED / GNM_ERR_BAD_ARG as gnm_saliency (F0 aside). */
+long long gnm_class_activation_table_words(int L);
+int gnm_class_activation_max_classes(void);
+int gnm_class_activation(const int32_t* node_off, int B, int n_max, long long N, int H, int L, int C, const int* cls,
+                         int ncls, int graph_avg, const long long* table, float* out, long long ldo, void* stream);
+int gnm_saliency_maps(const uint32_t* adj_bits, const int64_t* b_tbits_off, const int32_t* node_off,
+                      const int32_t* rowptr, const int64_t* b_rp_off, int B, int n_max, long long N, int H, int L,
+                      int m, int C, int cls, int average, int self_loop, int graph_avg, const long long* table,
+                      const float* eps, float* scratch, float* gcam, void* stream);
+
 /* ---- Infomax discriminator (discriminator.py:19-38, graphcnn.py:233-246) ------------
  * hptrs_host: HOST array of L device pointers to the per-layer [N,H] hidden states
  * (n_f is never concatenated).  A layer may instead be given as the pre-BatchNorm output Z_l of its last Linear
