@@ -430,3 +430,59 @@ extern "C" int gnm_saliency_maps(const uint32_t* adj_bits, const int64_t* b_tbit
     }
     return GNM_OK;
 }
+
+extern "C" int gnm_edge_saliency_contract(const uint32_t* adj_bits, const int64_t* b_bits_off, const int32_t* node_off,
+                                          const int32_t* rowptr, const int64_t* b_rp_off, int B, int n_max, long long N,
+                                          int H, int L, int m, int average, int self_loop, const long long* table,
+                                          const float* S, const float* Y, int ldy, float* out, long long ldo,
+                                          hipStream_t s);
+
+// Floats of scratch gnm_edge_saliency needs: every layer's S_l (L x [N, H]) and one (R) pair.
+extern "C" long long gnm_edge_saliency_scratch_floats(long long N, int H, int L) {
+    return (long long)(L + 2) * N * (long long)H;
+}
+
+// The connectivity saliency of class cls (edgesal.hip): out[u, v] = d score / d A[u, v] over every node pair of each
+// graph.  gnm_saliency's layer launches with each layer's S_l in a buffer of its own (layer 0's: dZ_0 / deg) and no dX
+// launch, then one contraction launch.
+extern "C" int gnm_edge_saliency(const uint32_t* adj_bits, const int64_t* b_bits_off, const int64_t* b_tbits_off,
+                                 const int32_t* node_off, const int32_t* rowptr, const int64_t* b_rp_off, int B,
+                                 int n_max, long long N, int H, int L, int m, int C, int cls, int average,
+                                 int self_loop, int graph_avg, const long long* table, const float* eps,
+                                 float* scratch, const float* Y, int ldy, float* out, long long ldo, void* stream) {
+    if (B <= 0) return GNM_OK;
+    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || n_max < 1 || n_max > kSlMaxN || C < 1)
+        return GNM_ERR_UNSUPPORTED;
+    if (cls < 0 || cls >= C || N < 1 || ldy < H || ldo < n_max) return GNM_ERR_BAD_ARG;
+    if (!adj_bits || !b_bits_off || !b_tbits_off || !node_off || !rowptr || !b_rp_off || !table || !scratch || !Y ||
+        !out)
+        return GNM_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(adj_bits) & 15) || (reinterpret_cast<uintptr_t>(Y) & 15) || (ldy & 3))
+        return GNM_ERR_UNSUPPORTED;
+    if ((long long)(n_max + 128) * H * 4 >= (1LL << 31) || N * (long long)H * (L + 2) >= (1LL << 40) ||
+        N * ldo >= (1LL << 40))
+        return GNM_ERR_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int wmax = (n_max + 31) / 32;
+    const bool need_r = average && !self_loop;
+    float* R[2] = {scratch + (size_t)L * N * H, scratch + (size_t)(L + 1) * N * H};
+    SlArgs a;
+    memset(&a, 0, sizeof(a));
+    a.adj_bits = adj_bits; a.b_tbits_off = b_tbits_off; a.node_off = node_off; a.rowptr = rowptr; a.b_rp_off = b_rp_off;
+    a.B = B; a.wmax = wmax; a.L = L; a.m = m; a.H = H; a.F0 = 0; a.cls = cls;
+    a.average = average; a.self_loop = self_loop; a.graph_avg = graph_avg;
+    a.eps = eps; a.table = table; a.lds = H;
+    for (int l = L - 1; l >= 0; --l) {
+        const int wr = l & 1, rd = wr ^ 1;
+        a.l = l;
+        a.Sin = l < L - 1 ? scratch + (size_t)(l + 1) * N * H : nullptr;
+        a.Rin = l < L - 1 && need_r ? R[rd] : nullptr;
+        a.Sout = scratch + (size_t)l * N * H;
+        a.Rout = need_r && l > 0 ? R[wr] : nullptr;
+        a.out = nullptr; a.ldo = 0; a.final_launch = 0;
+        hipLaunchKernelGGL(gnm_saliency_layer_kernel<false>, dim3(B * wmax), dim3(256), 0, s, a);
+        GNM_CHECK_LAUNCH();
+    }
+    return gnm_edge_saliency_contract(adj_bits, b_bits_off, node_off, rowptr, b_rp_off, B, n_max, N, H, L, m, average,
+                                      self_loop, table, scratch, Y, ldy, out, ldo, s);
+}

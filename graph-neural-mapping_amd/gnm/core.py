@@ -815,6 +815,44 @@ def saliency_maps_hip(spec, batch, X, P, classes):
     return out
 
 
+def edge_saliency_hip(spec, batch, X, P, classes):
+    """The connectivity saliency d score[:, c] / d A[u, v] of a whole batch for every c in `classes` and every node
+    pair (u, v) of each graph, A the dense Adj_block of graphcnn.py:84-106 (see include/gnm_hip.h gnm_edge_saliency):
+    one eval forward (encoder_forward) and Y = X W0^T on the split-precision Linear per batch, then per class L layer
+    launches and one contraction launch of gnm_edge_saliency.  The shapes saliency_maps_decline takes.  Parameters,
+    buffers and the numpy RNG are not touched.  Returns a float32 [len(classes), N, n_max] tensor: graph b's map is
+    rows node_off[b] .. node_off[b + 1], columns 0 .. n_b."""
+    dev = launch_device(X, P["eps"])
+    L, m = spec.L, spec.m
+    N, B = batch.N, batch.B
+    H = P["batch_norms.0.weight"].shape[0]
+    Cn = P["linears_prediction.0.weight"].shape[0]
+    F0 = X.shape[1]
+    X = X.contiguous()
+    a = batch.arena
+    nm = int(batch.n_max)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = torch.empty((len(classes), N, nm), **f32)
+    with torch.no_grad(), _stream_scope(dev):
+        _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
+        table = torch.tensor(_saliency_table_words(spec, P, saved), dtype=torch.int64).pin_memory().to(
+            dev, non_blocking=True)
+        W0 = P["mlps.0.linear.weight" if m == 1 else "mlps.0.linears.0.weight"]
+        Y = torch.empty((N, H), **f32)
+        _linear(X, W0, 0, None, Y, N, F0, H, None, None)                  # layer 0's term at width H: <dZ0, X W0^T>
+        scratch = torch.empty(int(lib.gnm_edge_saliency_scratch_floats(N, H, L)), **f32)
+        for ci, c in enumerate(classes):
+            with _timed("edge_saliency_hip", B=B, N=N, H=H):
+                check(lib.gnm_edge_saliency(a.bits.buf.data_ptr(), batch.bits_off.data_ptr(),
+                                            batch.t_bits_off.data_ptr(), batch.node_off.data_ptr(),
+                                            a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(), B, nm, N, H, L, m, Cn,
+                                            int(c), int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg),
+                                            table.data_ptr(), P["eps"].data_ptr() if spec.learn_eps else None,
+                                            scratch.data_ptr(), Y.data_ptr(), Y.stride(0), out[ci].data_ptr(),
+                                            out.stride(1), _stream()), "gnm_edge_saliency")
+    return out
+
+
 class GinInfoMaxFn(torch.autograd.Function):
     """(P0, X, *params) -> (c_logit [B,C], d_logit [2N,1], g_f [B,L*H])."""
 

@@ -32,7 +32,7 @@ for _p in (_PKG, _HERE):
 from mlp import MLP  # noqa: E402
 from discriminator import Discriminator  # noqa: E402
 from gnm.arena import GraphArena  # noqa: E402
-from gnm.core import (DISC_UNIT, DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip,  # noqa: E402
+from gnm.core import (DISC_UNIT, DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, edge_saliency_hip,  # noqa: E402
                       eval_forward_fused, eval_fused_ok, launch_device, saliency_hip, saliency_hip_ok, saliency_maps_decline,
                       saliency_maps_hip)
 
@@ -481,6 +481,93 @@ class GIN_InfoMaxReg(nn.Module):
             r = saliency_maps_hip(self._spec, sub, sub.arena.features(sub).detach(), P, classes)
             for k, j in enumerate(good):
                 out[:, offs[j]:offs[j + 1]] = r[:, sub.node_off_host[k]:sub.node_off_host[k + 1]]
+        return out
+
+    def edge_saliency(self, graphs, cls, batch_size=64):
+        """Connectivity saliency of many graphs in batches: which CONNECTION matters for a class.  For graph g with n
+        nodes, out[u, v] = d score_c / d A[u, v] for ALL u, v < n, A the dense form of the reference's Adj_block
+        (graphcnn.py:84-106: 1 at every edge_mat pair, row u = destination, plus the diagonal when learn_eps is False),
+        which every layer's aggregation multiplies by and, under neighbour "average", also divides by (degree = A 1).
+        score_c is compute_saliency's eval logit (BatchNorm on running statistics, no dropout).  Entries where A is 0
+        are the sensitivity to adding that connection -- what a leaf adjacency's .grad holds in torch.
+
+        csrc/edgesal.hip over gnm_saliency's layer launches (include/gnm_hip.h gnm_edge_saliency).  The shapes
+        class_activation(kind="gradient") takes; any other batch raises ValueError naming the condition (max pooling,
+        n > 416 or no bit adjacency, hidden_dim not in {32, 64, 128}, average pooling with learned eps and an isolated
+        node, ...).  A graph with a non-finite feature gets an all-NaN map.
+
+        cls: an int, or a sequence of ints; one forward per batch serves all of them.  Returns a float32 device tensor
+        [len(graphs), n, n] for an int `cls` and [len(cls), len(graphs), n, n] for a sequence; for graphs of different
+        node counts a list of [n_g, n_g] tensors (a list of such lists for a sequence `cls`).  The output is n^2 per
+        graph and class, hence the smaller default batch.  No parameter .grad, BatchNorm buffer or numpy RNG state is
+        touched, and the train / eval mode is restored on exit."""
+        single = isinstance(cls, (int, np.integer))
+        classes = [int(cls)] if single else [int(c) for c in cls]
+        n_cls = self.linears_prediction[0].out_features
+        if len(graphs) == 0:
+            raise ValueError("edge_saliency: empty list of graphs")
+        if not classes:
+            raise ValueError("edge_saliency: empty sequence of classes")
+        for c in classes:
+            if not 0 <= c < n_cls:
+                raise ValueError("edge_saliency: class %d out of range for a %d-class model" % (c, n_cls))
+        if batch_size < 1:
+            raise ValueError("edge_saliency: batch_size must be positive")
+        was_training = self.training
+        self.eval()
+        try:
+            names, tensors, buffers = self._param_lists()
+            P = dict(zip(names, tensors))
+            P.update(buffers)
+            ns = [len(g.g) for g in graphs]
+            ragged = any(k != ns[0] for k in ns)
+            n0 = ns[0]
+            full = None if ragged else torch.empty((len(classes), len(graphs), n0, n0), dtype=torch.float32,
+                                                   device=self.eps.device)
+            per_graph = [[] for _ in classes]
+            for i0 in range(0, len(graphs), batch_size):
+                chunk = graphs[i0:i0 + batch_size]
+                batch = self._batch_of(chunk)
+                res = self._edge_saliency_batch(chunk, batch, P, classes)       # [len(classes), N, n_max]
+                offs = np.asarray(batch.node_off_host)
+                if full is not None:
+                    full[:, i0:i0 + len(chunk)] = res.view(len(classes), len(chunk), n0, n0)
+                else:
+                    for ci in range(len(classes)):
+                        per_graph[ci] += [res[ci, offs[j]:offs[j + 1], :offs[j + 1] - offs[j]]
+                                          for j in range(len(chunk))]
+            if full is not None:
+                return full[0] if single else full
+            return per_graph[0] if single else per_graph
+        finally:
+            self.train(was_training)
+
+    def _edge_saliency_batch(self, chunk, batch, P, classes):
+        """edge_saliency() of one batch: [len(classes), N, n_max]"""
+        X = batch.arena.features(batch).detach()
+        launch_device(X, P["eps"])                          # no CPU fallback: GnmError before any shape question
+        why = saliency_maps_decline(self._spec, batch, X, P)
+        if why is not None:
+            raise ValueError("edge_saliency does not cover this batch: %s" % why)
+        if bool(torch.isfinite(X).all()):
+            return edge_saliency_hip(self._spec, batch, X, P, classes)
+        # a graph with a non-finite feature: an all-NaN map; the others on a batch of their own, so their maps are
+        # those of a clean batch
+        B = batch.B
+        counts = torch.as_tensor(np.diff(batch.node_off_host), device=X.device)
+        gid = torch.repeat_interleave(torch.arange(B, device=X.device), counts)
+        bad = torch.zeros(B, dtype=torch.int32, device=X.device).index_add_(
+            0, gid, (~torch.isfinite(X).all(1)).to(torch.int32)).cpu().numpy() > 0
+        offs = np.asarray(batch.node_off_host)
+        out = torch.full((len(classes), batch.N, batch.n_max), float("nan"), dtype=torch.float32, device=X.device)
+        good = [j for j in range(B) if not bad[j]]
+        if good:
+            sub = self._batch_of([chunk[j] for j in good])
+            r = edge_saliency_hip(self._spec, sub, sub.arena.features(sub).detach(), P, classes)
+            so = np.asarray(sub.node_off_host)
+            for k, j in enumerate(good):
+                nj = int(so[k + 1] - so[k])
+                out[:, offs[j]:offs[j + 1], :nj] = r[:, so[k]:so[k + 1], :nj]
         return out
 
     # ------------------------------------------------------------------ evaluation replay

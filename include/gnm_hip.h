@@ -362,6 +362,27 @@ int gnm_saliency_maps(const uint32_t* adj_bits, const int64_t* b_tbits_off, cons
                       int m, int C, int cls, int average, int self_loop, int graph_avg, const long long* table,
                       const float* eps, float* scratch, float* gcam, void* stream);
 
+/* ---- Eval-mode connectivity saliency (graphcnn.py:84-106 Adj_block, :146-191 next_layer_eps / next_layer) ----------
+ * out[(node_off[b] + u) * ldo + v] = d score[b, cls] / d A[u, v] for every graph b and EVERY node pair u, v < n_b, A the
+ * dense n x n Adj_block (1 at each edge_mat pair, row = destination; plus the diagonal when self_loop, i.e. learn_eps
+ * False, :97-102), shared by all L layers and, under neighbour average, by the degree A 1 (:158-160, :182-184).  Eval
+ * mode (BatchNorm on its running statistics, no dropout).  With S_l = dscore/dpooled_l / deg (gnm_saliency's stage D)
+ * and E[u, v] = sum_l <S_l[u], h_{l-1}[v]> (h_{-1} W0^T = Y for l = 0): out = E under sum pooling, and
+ * out[u, v] = E[u, v] - (1 / d_u) sum_w A[u, w] E[u, w] under average.  Entries where A is 0 are included.
+ * gnm_saliency's L layer launches with each S_l kept (no dX launch), then one launch of edgesal.hip's contraction: a
+ * workgroup per (graph, 32-row block), split-bf16 MFMA with fp32 accumulation, no atomics (deterministic).
+ * Arguments as gnm_saliency_maps, plus b_bits_off (the FORWARD bit rows, read for the average pooling's row mean),
+ * Y = X W0^T [N, H] (16-byte aligned, ldy >= H a multiple of 4), out with ldo >= n_max.  table: gnm_saliency's
+ * (gnm_saliency_table_words).  scratch: gnm_edge_saliency_scratch_floats(N, H, L) floats.
+ * GNM_ERR_UNSUPPORTED / GNM_ERR_BAD_ARG (nothing launched) as gnm_saliency_maps; BAD_ARG also for ldy < H, ldo < n_max
+ * and NULL Y / out / b_bits_off. */
+long long gnm_edge_saliency_scratch_floats(long long N, int H, int L);
+int gnm_edge_saliency(const uint32_t* adj_bits, const int64_t* b_bits_off, const int64_t* b_tbits_off,
+                      const int32_t* node_off, const int32_t* rowptr, const int64_t* b_rp_off, int B, int n_max,
+                      long long N, int H, int L, int m, int C, int cls, int average, int self_loop, int graph_avg,
+                      const long long* table, const float* eps, float* scratch, const float* Y, int ldy, float* out,
+                      long long ldo, void* stream);
+
 /* ---- Infomax discriminator (discriminator.py:19-38, graphcnn.py:233-246) ------------
  * hptrs_host: HOST array of L device pointers to the per-layer [N,H] hidden states
  * (n_f is never concatenated).  A layer may instead be given as the pre-BatchNorm output Z_l of its last Linear
