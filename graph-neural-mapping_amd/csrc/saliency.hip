@@ -31,6 +31,7 @@ typedef unsigned int sl_u32x2 __attribute__((ext_vector_type(2)));
 
 static constexpr int kSlMaxN = 416;               // as evallayer.hip: a block's bit rows fit 8 words per lane
 static constexpr int kSlMaxH = 128;
+static constexpr int kSlMaxL = 16;              // layers (the S / R placement arrays of the launchers)
 static constexpr int kSlLinWords = 6;             // per (layer, Linear): W, ld W, z, ld z, scale, shift
 static constexpr int kSlTS = kSlMaxH + 4;         // row stride of the LDS tiles (floats)
 
@@ -348,47 +349,79 @@ extern "C" long long gnm_saliency_table_words(int L, int m) { return (long long)
 // Floats of scratch gnm_saliency needs for N rows of hidden width H: two (S, R) pairs, one per parity of the layer.
 extern "C" long long gnm_saliency_scratch_floats(long long N, int H) { return 4 * N * (long long)H; }
 
+// The checks gnm_saliency, gnm_saliency_maps and gnm_edge_saliency share, then the SlArgs all their launches share
+// (F0 = 0, gcam = null).  The steps run in one order -- shape (UNSUPPORTED), arguments and null pointers (BAD_ARG),
+// alignment, sizes (UNSUPPORTED) -- and an entry's own conditions join the step they belong to (bad_shape, bad_arg,
+// null_arg, misaligned), so an input gets the same code from every entry.  row_floats: the widest row, in floats, of
+// the entry's N-row arrays.
+static int sl_setup(SlArgs& a, const uint32_t* adj_bits, const int64_t* b_tbits_off, const int32_t* node_off,
+                    const int32_t* rowptr, const int64_t* b_rp_off, int B, int n_max, long long N, int H, int L, int m,
+                    int C, int cls, int average, int self_loop, int graph_avg, const long long* table, const float* eps,
+                    const float* scratch, bool bad_shape, bool bad_arg, bool null_arg, bool misaligned,
+                    long long row_floats) {
+    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > kSlMaxL || n_max < 1 || n_max > kSlMaxN ||
+        C < 1 || bad_shape)
+        return GNM_ERR_UNSUPPORTED;
+    if (cls < 0 || cls >= C || N < 1 || bad_arg) return GNM_ERR_BAD_ARG;
+    if (!adj_bits || !b_tbits_off || !node_off || !rowptr || !b_rp_off || !table || !scratch || null_arg)
+        return GNM_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(adj_bits) & 15) || misaligned) return GNM_ERR_UNSUPPORTED;
+    if ((long long)(n_max + 128) * H * 4 >= (1LL << 31) || N * row_floats >= (1LL << 40)) return GNM_ERR_UNSUPPORTED;
+    memset(&a, 0, sizeof(a));
+    a.adj_bits = adj_bits; a.b_tbits_off = b_tbits_off; a.node_off = node_off; a.rowptr = rowptr; a.b_rp_off = b_rp_off;
+    a.B = B; a.wmax = (n_max + 31) / 32; a.L = L; a.m = m; a.H = H; a.cls = cls;
+    a.average = average; a.self_loop = self_loop; a.graph_avg = graph_avg;
+    a.eps = eps; a.table = table; a.lds = H;
+    return GNM_OK;
+}
+
+// gnm_saliency's scratch placement: two (S, R) pairs, layer l on pair l & 1.  R only where average pooling without
+// self loops needs the undivided gradient (1 + eps) dpooled.
+static void sl_pingpong(float** S, float** R, float* scratch, long long N, int H, int L, bool need_r) {
+    for (int l = 0; l < L; ++l) {
+        S[l] = scratch + 2 * (l & 1) * N * H;
+        R[l] = need_r ? scratch + (2 * (l & 1) + 1) * N * H : nullptr;
+    }
+}
+
+// The L layer launches from the top layer down: layer l reads the layer above's S[l + 1] / R[l + 1] (none for the top
+// layer) and writes its own to S[l] / R[l] (null: not kept).
+template <bool kMaps>
+static int sl_layers(SlArgs& a, float* const* S, float* const* R, hipStream_t s) {
+    for (int l = a.L - 1; l >= 0; --l) {
+        a.l = l;
+        a.Sin = l < a.L - 1 ? S[l + 1] : nullptr;
+        a.Rin = l < a.L - 1 ? R[l + 1] : nullptr;
+        a.Sout = S[l];
+        a.Rout = R[l];
+        hipLaunchKernelGGL(gnm_saliency_layer_kernel<kMaps>, dim3(a.B * a.wmax), dim3(256), 0, s, a);
+        GNM_CHECK_LAUNCH();
+    }
+    return GNM_OK;
+}
+
 extern "C" int gnm_saliency(const uint32_t* adj_bits, const int64_t* b_tbits_off, const int32_t* node_off,
                             const int32_t* rowptr, const int64_t* b_rp_off, int B, int n_max, long long N, int F0, int H,
                             int L, int m, int C, int cls, int average, int self_loop, int graph_avg,
                             const long long* table, const float* eps, float* scratch, float* dX, int ldx, void* stream) {
     if (B <= 0) return GNM_OK;
-    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || F0 < 1 || F0 > gnm_linear_max_k(H) ||
-        n_max < 1 || n_max > kSlMaxN || C < 1)
-        return GNM_ERR_UNSUPPORTED;
-    if (cls < 0 || cls >= C || N < 1 || ldx < F0) return GNM_ERR_BAD_ARG;
-    if (!adj_bits || !b_tbits_off || !node_off || !rowptr || !b_rp_off || !table || !scratch || !dX) return GNM_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(adj_bits) & 15) return GNM_ERR_UNSUPPORTED;
-    if ((long long)(n_max + 128) * H * 4 >= (1LL << 31) || N * (long long)(ldx > H ? ldx : H) >= (1LL << 40))
-        return GNM_ERR_UNSUPPORTED;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int wmax = (n_max + 31) / 32;
-    const bool need_r = average && !self_loop;    // (1 + eps) dpooled: the undivided gradient too
-    float* S[2] = {scratch, scratch + 2 * N * H};
-    float* R[2] = {scratch + N * H, scratch + 3 * N * H};
     SlArgs a;
-    memset(&a, 0, sizeof(a));
-    a.adj_bits = adj_bits; a.b_tbits_off = b_tbits_off; a.node_off = node_off; a.rowptr = rowptr; a.b_rp_off = b_rp_off;
-    a.B = B; a.wmax = wmax; a.L = L; a.m = m; a.H = H; a.F0 = F0; a.cls = cls;
-    a.average = average; a.self_loop = self_loop; a.graph_avg = graph_avg;
-    a.eps = eps; a.table = table; a.lds = H;
-    for (int l = L - 1; l >= 0; --l) {
-        const int wr = l & 1, rd = wr ^ 1;
-        a.l = l;
-        a.Sin = l < L - 1 ? S[rd] : nullptr;
-        a.Rin = l < L - 1 && need_r ? R[rd] : nullptr;
-        a.Sout = S[wr];
-        a.Rout = need_r ? R[wr] : nullptr;
-        a.out = nullptr; a.ldo = 0; a.final_launch = 0;
-        hipLaunchKernelGGL(gnm_saliency_layer_kernel<false>, dim3(B * wmax), dim3(256), 0, s, a);
-        GNM_CHECK_LAUNCH();
-    }
-    a.l = 0;
+    int rc = sl_setup(a, adj_bits, b_tbits_off, node_off, rowptr, b_rp_off, B, n_max, N, H, L, m, C, cls, average,
+                      self_loop, graph_avg, table, eps, scratch, F0 < 1 || F0 > gnm_linear_max_k(H), ldx < F0, !dX,
+                      false, ldx > H ? ldx : H);
+    if (rc != GNM_OK) return rc;
+    a.F0 = F0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float* S[kSlMaxL];
+    float* R[kSlMaxL];
+    sl_pingpong(S, R, scratch, N, H, L, average && !self_loop);
+    if ((rc = sl_layers<false>(a, S, R, s)) != GNM_OK) return rc;
+    a.l = 0;                                      // the final launch: dX from layer 0's S (and R)
     a.Sin = S[0];
-    a.Rin = need_r ? R[0] : nullptr;
+    a.Rin = R[0];
     a.Sout = nullptr; a.Rout = nullptr;
     a.out = dX; a.ldo = ldx; a.final_launch = 1;
-    hipLaunchKernelGGL(gnm_saliency_layer_kernel<false>, dim3(B * wmax), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(gnm_saliency_layer_kernel<false>, dim3(B * a.wmax), dim3(256), 0, s, a);
     GNM_CHECK_LAUNCH();
     return GNM_OK;
 }
@@ -400,35 +433,15 @@ extern "C" int gnm_saliency_maps(const uint32_t* adj_bits, const int64_t* b_tbit
                                  int L, int m, int C, int cls, int average, int self_loop, int graph_avg,
                                  const long long* table, const float* eps, float* scratch, float* gcam, void* stream) {
     if (B <= 0) return GNM_OK;
-    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || n_max < 1 || n_max > kSlMaxN || C < 1)
-        return GNM_ERR_UNSUPPORTED;
-    if (cls < 0 || cls >= C || N < 1) return GNM_ERR_BAD_ARG;
-    if (!adj_bits || !b_tbits_off || !node_off || !rowptr || !b_rp_off || !table || !scratch || !gcam)
-        return GNM_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(adj_bits) & 15) return GNM_ERR_UNSUPPORTED;
-    if ((long long)(n_max + 128) * H * 4 >= (1LL << 31) || N * (long long)H >= (1LL << 40)) return GNM_ERR_UNSUPPORTED;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int wmax = (n_max + 31) / 32;
-    const bool need_r = average && !self_loop;
-    float* S[2] = {scratch, scratch + 2 * N * H};
-    float* R[2] = {scratch + N * H, scratch + 3 * N * H};
     SlArgs a;
-    memset(&a, 0, sizeof(a));
-    a.adj_bits = adj_bits; a.b_tbits_off = b_tbits_off; a.node_off = node_off; a.rowptr = rowptr; a.b_rp_off = b_rp_off;
-    a.B = B; a.wmax = wmax; a.L = L; a.m = m; a.H = H; a.F0 = 0; a.cls = cls;
-    a.average = average; a.self_loop = self_loop; a.graph_avg = graph_avg;
-    a.eps = eps; a.table = table; a.lds = H; a.gcam = gcam;
-    for (int l = L - 1; l >= 0; --l) {
-        const int wr = l & 1, rd = wr ^ 1;
-        a.l = l;
-        a.Sin = l < L - 1 ? S[rd] : nullptr;
-        a.Rin = l < L - 1 && need_r ? R[rd] : nullptr;
-        a.Sout = S[wr];
-        a.Rout = need_r ? R[wr] : nullptr;
-        hipLaunchKernelGGL(gnm_saliency_layer_kernel<true>, dim3(B * wmax), dim3(256), 0, s, a);
-        GNM_CHECK_LAUNCH();
-    }
-    return GNM_OK;
+    const int rc = sl_setup(a, adj_bits, b_tbits_off, node_off, rowptr, b_rp_off, B, n_max, N, H, L, m, C, cls, average,
+                            self_loop, graph_avg, table, eps, scratch, false, false, !gcam, false, H);
+    if (rc != GNM_OK) return rc;
+    a.gcam = gcam;
+    float* S[kSlMaxL];
+    float* R[kSlMaxL];
+    sl_pingpong(S, R, scratch, N, H, L, average && !self_loop);
+    return sl_layers<true>(a, S, R, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int gnm_edge_saliency_contract(const uint32_t* adj_bits, const int64_t* b_bits_off, const int32_t* node_off,
@@ -451,38 +464,21 @@ extern "C" int gnm_edge_saliency(const uint32_t* adj_bits, const int64_t* b_bits
                                  int self_loop, int graph_avg, const long long* table, const float* eps,
                                  float* scratch, const float* Y, int ldy, float* out, long long ldo, void* stream) {
     if (B <= 0) return GNM_OK;
-    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || n_max < 1 || n_max > kSlMaxN || C < 1)
-        return GNM_ERR_UNSUPPORTED;
-    if (cls < 0 || cls >= C || N < 1 || ldy < H || ldo < n_max) return GNM_ERR_BAD_ARG;
-    if (!adj_bits || !b_bits_off || !b_tbits_off || !node_off || !rowptr || !b_rp_off || !table || !scratch || !Y ||
-        !out)
-        return GNM_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(adj_bits) & 15) || (reinterpret_cast<uintptr_t>(Y) & 15) || (ldy & 3))
-        return GNM_ERR_UNSUPPORTED;
-    if ((long long)(n_max + 128) * H * 4 >= (1LL << 31) || N * (long long)H * (L + 2) >= (1LL << 40) ||
-        N * ldo >= (1LL << 40))
-        return GNM_ERR_UNSUPPORTED;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int wmax = (n_max + 31) / 32;
-    const bool need_r = average && !self_loop;
-    float* R[2] = {scratch + (size_t)L * N * H, scratch + (size_t)(L + 1) * N * H};
     SlArgs a;
-    memset(&a, 0, sizeof(a));
-    a.adj_bits = adj_bits; a.b_tbits_off = b_tbits_off; a.node_off = node_off; a.rowptr = rowptr; a.b_rp_off = b_rp_off;
-    a.B = B; a.wmax = wmax; a.L = L; a.m = m; a.H = H; a.F0 = 0; a.cls = cls;
-    a.average = average; a.self_loop = self_loop; a.graph_avg = graph_avg;
-    a.eps = eps; a.table = table; a.lds = H;
-    for (int l = L - 1; l >= 0; --l) {
-        const int wr = l & 1, rd = wr ^ 1;
-        a.l = l;
-        a.Sin = l < L - 1 ? scratch + (size_t)(l + 1) * N * H : nullptr;
-        a.Rin = l < L - 1 && need_r ? R[rd] : nullptr;
-        a.Sout = scratch + (size_t)l * N * H;
-        a.Rout = need_r && l > 0 ? R[wr] : nullptr;
-        a.out = nullptr; a.ldo = 0; a.final_launch = 0;
-        hipLaunchKernelGGL(gnm_saliency_layer_kernel<false>, dim3(B * wmax), dim3(256), 0, s, a);
-        GNM_CHECK_LAUNCH();
+    int rc = sl_setup(a, adj_bits, b_tbits_off, node_off, rowptr, b_rp_off, B, n_max, N, H, L, m, C, cls, average,
+                      self_loop, graph_avg, table, eps, scratch, false, ldy < H || ldo < n_max, !b_bits_off || !Y || !out,
+                      (reinterpret_cast<uintptr_t>(Y) & 15) || (ldy & 3), (long long)H * (L + 2));
+    if (rc != GNM_OK) return rc;
+    if (N * ldo >= (1LL << 40)) return GNM_ERR_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool need_r = average && !self_loop;
+    float* S[kSlMaxL];
+    float* R[kSlMaxL];
+    for (int l = 0; l < L; ++l) {                 // R: one pair after the L S_l; layer 0 writes none (no layer below)
+        S[l] = scratch + (size_t)l * N * H;
+        R[l] = need_r && l > 0 ? scratch + (size_t)(L + (l & 1)) * N * H : nullptr;
     }
+    if ((rc = sl_layers<false>(a, S, R, s)) != GNM_OK) return rc;
     return gnm_edge_saliency_contract(adj_bits, b_bits_off, node_off, rowptr, b_rp_off, B, n_max, N, H, L, m, average,
                                       self_loop, table, scratch, Y, ldy, out, ldo, s);
 }

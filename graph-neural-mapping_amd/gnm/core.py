@@ -11,8 +11,10 @@ tiny [B, .] dense ops (classifier Linear(H, C), U = sigmoid(g_f) W^T).
 Every N-sized array op runs in libgnm_hip.so.  There is no CPU or eager-PyTorch fallback
 for the sum/average path: on a non-GPU tensor the calls raise.
 """
+import contextlib
 import ctypes as C
 import os
+import types
 
 import numpy as np
 
@@ -657,18 +659,28 @@ def eval_forward_fused(spec, batch, perm, P, X, want_disc, mode=True):
     return c_logit, d_logit, g_f
 
 
-def saliency_hip_ok(spec, batch, X, P):
-    """can csrc/saliency.hip (gnm_saliency) take this batch?  Else GIN_InfoMaxReg.saliency() differentiates the whole
-    batch through GinInfoMaxFn instead."""
-    if spec.n_max or spec.sync_bn is not None or not X.is_cuda:
-        return False
-    if not getattr(batch, "has_bits", False) or batch.B < 1 or batch.n_max > 416:
-        return False
-    if spec.n_avg and spec.learn_eps and getattr(batch, "iso", False):
-        return False            # the 0/0 row of an isolated node: the autograd path's NaN semantics, not re-derived here
+def saliency_decline(spec, batch, X, P, dx):
+    """None if csrc/saliency.hip takes this batch, else the condition it declines.  dx: the input width must fit
+    gnm_saliency's dX launch (GIN_InfoMaxReg.saliency(); the gradient class activation and edge maps never form dX)."""
     H = P["batch_norms.0.weight"].shape[0]
-    return (H in (32, 64, 128) and 1 <= spec.m <= 3 and spec.L <= 16
-            and 1 <= X.shape[1] <= int(lib.gnm_linear_max_k(H)))
+    if spec.n_max:
+        return "max neighbour pooling"
+    if not getattr(batch, "has_bits", False) or batch.n_max > 416:
+        return "a graph of more than 416 nodes or without a bit adjacency"
+    if H not in (32, 64, 128):
+        return "hidden_dim %d not in {32, 64, 128}" % H
+    if spec.n_avg and spec.learn_eps and getattr(batch, "iso", False):
+        # the 0/0 row of an isolated node: the autograd path's NaN semantics, not re-derived here
+        return "average neighbour pooling with learned eps and an isolated node"
+    if not 1 <= spec.m <= 3 or spec.L > 16:
+        return "num_mlp_layers outside 1..3 or more than 16 layers"
+    if spec.sync_bn is not None:
+        return "synchronised BatchNorm"
+    if not X.is_cuda or batch.B < 1:
+        return "an empty batch or one off the GPU"
+    if dx and not 1 <= X.shape[1] <= int(lib.gnm_linear_max_k(H)):
+        return "input width %d outside 1..%d" % (X.shape[1], int(lib.gnm_linear_max_k(H)))
+    return None
 
 
 def _saliency_table_words(spec, P, saved):
@@ -693,56 +705,71 @@ def _saliency_table_words(spec, P, saved):
     return words
 
 
-def saliency_hip(spec, batch, X, P, classes, outs=None):
-    """d score[:, c] / d X (graphcnn.py:254-266 for a whole batch in eval mode) for every c in `classes`: ONE eval
-    forward through the training kernels (encoder_forward, BatchNorm on its running statistics; it leaves every
-    Linear's pre-BatchNorm output z, which give the ReLU masks), then L + 1 launches of gnm_saliency per class.
-    Parameters, buffers and the numpy RNG are not touched.  Returns a list of [N, F0] tensors, one per class (written
-    into `outs` when given: row-contiguous [N, F0] destinations)."""
+def _out_array(out, shape, dev):
+    """`out`, a float32 destination of `shape` on `dev` whose rows are contiguous, or a new array of that shape"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if tuple(out.shape) != tuple(shape) or out.stride(-1) != 1 or out.dtype != torch.float32 or out.device != dev:
+        raise GnmError("output must be a float32 %s array on %s with contiguous rows" % (list(shape), dev))
+    return out
+
+
+@contextlib.contextmanager
+def _saliency_launch(spec, batch, X, P, scratch_floats):
+    """What saliency_hip, saliency_maps_hip and edge_saliency_hip share, as the scope of their launches (no autograd,
+    the tensors' device and its stream): the dimensions, ONE eval forward through the training kernels (encoder_forward,
+    BatchNorm on its running statistics; it leaves every Linear's pre-BatchNorm output z, which give the ReLU masks),
+    gnm_saliency's parameter table over it on the device, and scratch_floats(N, H) floats of scratch."""
     dev = launch_device(X, P["eps"])
-    L, m = spec.L, spec.m
-    N, B = batch.N, batch.B
-    H = P["batch_norms.0.weight"].shape[0]
-    Cn = P["linears_prediction.0.weight"].shape[0]
-    F0 = X.shape[1]
-    f32 = dict(dtype=torch.float32, device=dev)
-    X = X.contiguous()
-    a = batch.arena
-    res = []
+    k = types.SimpleNamespace(dev=dev, N=batch.N, B=batch.B, F0=X.shape[1], H=P["batch_norms.0.weight"].shape[0],
+                              Cn=P["linears_prediction.0.weight"].shape[0], X=X.contiguous(),
+                              eps=P["eps"].data_ptr() if spec.learn_eps else None)
     with torch.no_grad(), _stream_scope(dev):
-        _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
-        table = torch.tensor(_saliency_table_words(spec, P, saved), dtype=torch.int64).pin_memory().to(
+        _, _, saved = encoder_forward(spec, batch, k.X, P, training=False, update_running=False)
+        k.table = torch.tensor(_saliency_table_words(spec, P, saved), dtype=torch.int64).pin_memory().to(
             dev, non_blocking=True)
-        scratch = torch.empty(int(lib.gnm_saliency_scratch_floats(N, H)), **f32)
-        for ci, c in enumerate(classes):
-            dX = outs[ci] if outs is not None else torch.empty((N, F0), **f32)
-            if dX.shape != (N, F0) or dX.stride(1) != 1:
-                raise GnmError("saliency output must be a row-contiguous [%d, %d] array" % (N, F0))
-            with _timed("saliency_hip", B=B, N=N, F0=F0, H=H):
-                check(lib.gnm_saliency(a.bits.buf.data_ptr(), batch.t_bits_off.data_ptr(), batch.node_off.data_ptr(),
-                                       a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(), B, batch.n_max, N, F0, H, L, m,
-                                       Cn, int(c), int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg),
-                                       table.data_ptr(), P["eps"].data_ptr() if spec.learn_eps else None,
-                                       scratch.data_ptr(), dX.data_ptr(), dX.stride(0), _stream()), "gnm_saliency")
-            res.append(dX)
+        k.scratch = torch.empty(int(scratch_floats(k.N, k.H)), dtype=torch.float32, device=dev)
+        yield k
     # (the forward's arrays and the table are freed here with launches still queued: the caching allocator hands
     # their memory only to later work on the same stream)
+
+
+def saliency_hip(spec, batch, X, P, classes, outs=None):
+    """d score[:, c] / d X (graphcnn.py:254-266 for a whole batch in eval mode) for every c in `classes`: one eval
+    forward (_saliency_launch), then L + 1 launches of gnm_saliency per class.  Parameters, buffers and the numpy RNG
+    are not touched.  Returns a list of [N, F0] tensors, one per class (written into `outs` when given: row-contiguous
+    [N, F0] destinations)."""
+    res = []
+    with _saliency_launch(spec, batch, X, P, lib.gnm_saliency_scratch_floats) as k:
+        a = batch.arena
+        N, F0 = k.N, k.F0
+        for ci, c in enumerate(classes):
+            dX = outs[ci] if outs is not None else torch.empty((N, F0), dtype=torch.float32, device=k.dev)
+            if dX.shape != (N, F0) or dX.stride(1) != 1:
+                raise GnmError("saliency output must be a row-contiguous [%d, %d] array" % (N, F0))
+            with _timed("saliency_hip", B=k.B, N=N, F0=F0, H=k.H):
+                check(lib.gnm_saliency(a.bits.buf.data_ptr(), batch.t_bits_off.data_ptr(), batch.node_off.data_ptr(),
+                                       a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(), k.B, batch.n_max, N, F0, k.H,
+                                       spec.L, spec.m, k.Cn, int(c), int(spec.n_avg), int(not spec.learn_eps),
+                                       int(spec.g_avg), k.table.data_ptr(), k.eps, k.scratch.data_ptr(), dX.data_ptr(),
+                                       dX.stride(0), _stream()), "gnm_saliency")
+            res.append(dX)
     return res
 
 
-def class_activation_hip(spec, batch, X, P, classes):
+def class_activation_hip(spec, batch, X, P, classes, out=None):
     """The per-node class activation maps cam[v] = p_g sum_l <h_l[v], linears_prediction[l].weight[c]> of a whole batch
     (graphcnn.py:288 class_activation) for every c in `classes`: ONE eval forward through the training kernels
     (encoder_forward, BatchNorm on its running statistics), then gnm_class_activation, which re-forms each h_l from the
     layer's z, scale and shift.  Any neighbour pooling or adjacency form.  Parameters, buffers and the numpy RNG are not
-    touched.  Returns a float32 [len(classes), N] tensor."""
+    touched.  Returns a float32 [len(classes), N] tensor (`out` when given)."""
     dev = launch_device(X, P["eps"])
     L, m = spec.L, spec.m
     N, B = batch.N, batch.B
     H = P["batch_norms.0.weight"].shape[0]
     Cn = P["linears_prediction.0.weight"].shape[0]
     X = X.contiguous()
-    out = torch.empty((len(classes), N), dtype=torch.float32, device=dev)
+    out = _out_array(out, (len(classes), N), dev)
     with torch.no_grad(), _stream_scope(dev):
         _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
         words = []
@@ -767,89 +794,48 @@ def class_activation_hip(spec, batch, X, P, classes):
     return out
 
 
-def saliency_maps_decline(spec, batch, X, P):
-    """None if gnm_saliency_maps takes this batch, else the condition it declines (the shapes saliency_hip_ok takes,
-    the input width aside: the gradient maps never form dX)."""
-    H = P["batch_norms.0.weight"].shape[0]
-    if spec.n_max:
-        return "max neighbour pooling"
-    if not getattr(batch, "has_bits", False) or batch.n_max > 416:
-        return "a graph of more than 416 nodes or without a bit adjacency"
-    if H not in (32, 64, 128):
-        return "hidden_dim %d not in {32, 64, 128}" % H
-    if spec.n_avg and spec.learn_eps and getattr(batch, "iso", False):
-        return "average neighbour pooling with learned eps and an isolated node"
-    if not 1 <= spec.m <= 3 or spec.L > 16:
-        return "num_mlp_layers outside 1..3 or more than 16 layers"
-    if spec.sync_bn is not None:
-        return "synchronised BatchNorm"
-    return None
-
-
-def saliency_maps_hip(spec, batch, X, P, classes):
+def saliency_maps_hip(spec, batch, X, P, classes, out=None):
     """The gradient class activation maps gcam[v] = sum_l <d score[:, c] / d h_l[v], h_l[v]> of a whole batch
     (graphcnn.py:284,289 grad_class_activation: h.grad on the retained hidden_rep[l] of compute_saliency) for every c
-    in `classes`: one eval forward (encoder_forward), then L launches of gnm_saliency_maps per class.  Parameters,
-    buffers and the numpy RNG are not touched.  Returns a float32 [len(classes), N] tensor."""
-    dev = launch_device(X, P["eps"])
-    L, m = spec.L, spec.m
-    N, B = batch.N, batch.B
-    H = P["batch_norms.0.weight"].shape[0]
-    Cn = P["linears_prediction.0.weight"].shape[0]
-    X = X.contiguous()
-    a = batch.arena
-    out = torch.empty((len(classes), N), dtype=torch.float32, device=dev)
-    with torch.no_grad(), _stream_scope(dev):
-        _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
-        table = torch.tensor(_saliency_table_words(spec, P, saved), dtype=torch.int64).pin_memory().to(
-            dev, non_blocking=True)
-        scratch = torch.empty(int(lib.gnm_saliency_scratch_floats(N, H)), dtype=torch.float32, device=dev)
+    in `classes`: one eval forward (_saliency_launch), then L launches of gnm_saliency_maps per class.  Parameters,
+    buffers and the numpy RNG are not touched.  Returns a float32 [len(classes), N] tensor (`out` when given)."""
+    with _saliency_launch(spec, batch, X, P, lib.gnm_saliency_scratch_floats) as k:
+        a = batch.arena
+        out = _out_array(out, (len(classes), k.N), k.dev)
         for ci, c in enumerate(classes):
-            with _timed("saliency_maps_hip", B=B, N=N, H=H):
+            with _timed("saliency_maps_hip", B=k.B, N=k.N, H=k.H):
                 check(lib.gnm_saliency_maps(a.bits.buf.data_ptr(), batch.t_bits_off.data_ptr(),
                                             batch.node_off.data_ptr(), a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(),
-                                            B, batch.n_max, N, H, L, m, Cn, int(c), int(spec.n_avg),
-                                            int(not spec.learn_eps), int(spec.g_avg), table.data_ptr(),
-                                            P["eps"].data_ptr() if spec.learn_eps else None, scratch.data_ptr(),
-                                            out[ci].data_ptr(), _stream()), "gnm_saliency_maps")
+                                            k.B, batch.n_max, k.N, k.H, spec.L, spec.m, k.Cn, int(c), int(spec.n_avg),
+                                            int(not spec.learn_eps), int(spec.g_avg), k.table.data_ptr(), k.eps,
+                                            k.scratch.data_ptr(), out[ci].data_ptr(), _stream()), "gnm_saliency_maps")
     return out
 
 
-def edge_saliency_hip(spec, batch, X, P, classes):
+def edge_saliency_hip(spec, batch, X, P, classes, out=None):
     """The connectivity saliency d score[:, c] / d A[u, v] of a whole batch for every c in `classes` and every node
     pair (u, v) of each graph, A the dense Adj_block of graphcnn.py:84-106 (see include/gnm_hip.h gnm_edge_saliency):
-    one eval forward (encoder_forward) and Y = X W0^T on the split-precision Linear per batch, then per class L layer
-    launches and one contraction launch of gnm_edge_saliency.  The shapes saliency_maps_decline takes.  Parameters,
-    buffers and the numpy RNG are not touched.  Returns a float32 [len(classes), N, n_max] tensor: graph b's map is
-    rows node_off[b] .. node_off[b + 1], columns 0 .. n_b."""
-    dev = launch_device(X, P["eps"])
-    L, m = spec.L, spec.m
-    N, B = batch.N, batch.B
-    H = P["batch_norms.0.weight"].shape[0]
-    Cn = P["linears_prediction.0.weight"].shape[0]
-    F0 = X.shape[1]
-    X = X.contiguous()
-    a = batch.arena
-    nm = int(batch.n_max)
-    f32 = dict(dtype=torch.float32, device=dev)
-    out = torch.empty((len(classes), N, nm), **f32)
-    with torch.no_grad(), _stream_scope(dev):
-        _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
-        table = torch.tensor(_saliency_table_words(spec, P, saved), dtype=torch.int64).pin_memory().to(
-            dev, non_blocking=True)
-        W0 = P["mlps.0.linear.weight" if m == 1 else "mlps.0.linears.0.weight"]
-        Y = torch.empty((N, H), **f32)
-        _linear(X, W0, 0, None, Y, N, F0, H, None, None)                  # layer 0's term at width H: <dZ0, X W0^T>
-        scratch = torch.empty(int(lib.gnm_edge_saliency_scratch_floats(N, H, L)), **f32)
+    one eval forward (_saliency_launch) and Y = X W0^T on the split-precision Linear per batch, then per class L layer
+    launches and one contraction launch of gnm_edge_saliency.  The shapes saliency_decline takes.  Parameters,
+    buffers and the numpy RNG are not touched.  Returns a float32 [len(classes), N, n_max] tensor (`out` when given):
+    graph b's map is rows node_off[b] .. node_off[b + 1], columns 0 .. n_b."""
+    L = spec.L
+    with _saliency_launch(spec, batch, X, P, lambda N, H: lib.gnm_edge_saliency_scratch_floats(N, H, L)) as k:
+        a = batch.arena
+        nm = int(batch.n_max)
+        out = _out_array(out, (len(classes), k.N, nm), k.dev)
+        W0 = P["mlps.0.linear.weight" if spec.m == 1 else "mlps.0.linears.0.weight"]
+        Y = torch.empty((k.N, k.H), dtype=torch.float32, device=k.dev)
+        _linear(k.X, W0, 0, None, Y, k.N, k.F0, k.H, None, None)          # layer 0's term at width H: <dZ0, X W0^T>
         for ci, c in enumerate(classes):
-            with _timed("edge_saliency_hip", B=B, N=N, H=H):
+            with _timed("edge_saliency_hip", B=k.B, N=k.N, H=k.H):
                 check(lib.gnm_edge_saliency(a.bits.buf.data_ptr(), batch.bits_off.data_ptr(),
                                             batch.t_bits_off.data_ptr(), batch.node_off.data_ptr(),
-                                            a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(), B, nm, N, H, L, m, Cn,
-                                            int(c), int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg),
-                                            table.data_ptr(), P["eps"].data_ptr() if spec.learn_eps else None,
-                                            scratch.data_ptr(), Y.data_ptr(), Y.stride(0), out[ci].data_ptr(),
-                                            out.stride(1), _stream()), "gnm_edge_saliency")
+                                            a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(), k.B, nm, k.N, k.H, L,
+                                            spec.m, k.Cn, int(c), int(spec.n_avg), int(not spec.learn_eps),
+                                            int(spec.g_avg), k.table.data_ptr(), k.eps, k.scratch.data_ptr(),
+                                            Y.data_ptr(), Y.stride(0), out[ci].data_ptr(), out.stride(1), _stream()),
+                      "gnm_edge_saliency")
     return out
 
 

@@ -16,6 +16,7 @@ csrc/maxpool.hip in place of the aggregation kernels (gnm/maxnb.py builds its ne
 lists from graph.neighbors, as graphcnn.py:55-81 does); only the hipGraph replays and the
 layer-0 cache are not offered for it.
 """
+import functools
 import os
 import sys
 
@@ -33,10 +34,19 @@ from mlp import MLP  # noqa: E402
 from discriminator import Discriminator  # noqa: E402
 from gnm.arena import GraphArena  # noqa: E402
 from gnm.core import (DISC_UNIT, DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, edge_saliency_hip,  # noqa: E402
-                      eval_forward_fused, eval_fused_ok, launch_device, saliency_hip, saliency_hip_ok, saliency_maps_decline,
-                      saliency_maps_hip)
+                      eval_forward_fused, eval_fused_ok, launch_device, saliency_decline, saliency_hip, saliency_maps_hip)
 
 __all__ = ["GIN_InfoMaxReg", "GraphCNN", "MLP", "Discriminator"]
+
+
+def _nonfinite_graphs(batch, X):
+    """None when every feature of the batch is finite, else per graph whether it has a non-finite feature (numpy)"""
+    if bool(torch.isfinite(X).all()):
+        return None
+    counts = torch.as_tensor(np.diff(batch.node_off_host), device=X.device)
+    gid = torch.repeat_interleave(torch.arange(batch.B, device=X.device), counts)
+    return torch.zeros(batch.B, dtype=torch.int32, device=X.device).index_add_(
+        0, gid, (~torch.isfinite(X).all(1)).to(torch.int32)).cpu().numpy() > 0
 
 
 class _LazyEvalGrad(torch.autograd.Function):
@@ -297,18 +307,32 @@ class GIN_InfoMaxReg(nn.Module):
         neighbour pooling, graphs over 416 nodes or without a bit adjacency, H outside {32, 64, 128}, ...) is left in
         self.saliency_routes.  A graph with a non-finite feature takes the autograd route on its own (one more
         "autograd" entry), so its NaN / inf pattern is compute_saliency's."""
+        F0 = self.mlps[0].linear.in_features if self.num_mlp_layers == 1 else self.mlps[0].linears[0].in_features
+        routes = []
+        out = self._interpret("saliency", graphs, cls, batch_size, (F0,), functools.partial(self._saliency_batch,
+                                                                                          routes=routes))
+        self.saliency_routes = routes
+        return out
+
+    def _interpret(self, name, graphs, cls, batch_size, tail, run_batch, square=False):
+        """The batching saliency(), class_activation() and edge_saliency() share (`name`, which prefixes the errors):
+        the argument checks, eval mode with the previous mode restored on exit, chunks of batch_size graphs, and the
+        result layout.  run_batch(chunk, batch, P, classes, dst) returns one batch's [len(classes), N, *tail] result
+        (or a list of per-class [N, *tail] tensors), written into dst when that is given: the batch's view of the dense
+        [len(classes), len(graphs), n, *tail] result.  Graphs of different node counts get per-graph lists instead;
+        square: an [n, n] map per graph (tail (n,), each graph's map cropped to its n_g columns)."""
         single = isinstance(cls, (int, np.integer))
         classes = [int(cls)] if single else [int(c) for c in cls]
         n_cls = self.linears_prediction[0].out_features
         if len(graphs) == 0:
-            raise ValueError("saliency: empty list of graphs")
+            raise ValueError("%s: empty list of graphs" % name)
         if not classes:
-            raise ValueError("saliency: empty sequence of classes")
+            raise ValueError("%s: empty sequence of classes" % name)
         for c in classes:
             if not 0 <= c < n_cls:
-                raise ValueError("saliency: class %d out of range for a %d-class model" % (c, n_cls))
+                raise ValueError("%s: class %d out of range for a %d-class model" % (name, c, n_cls))
         if batch_size < 1:
-            raise ValueError("saliency: batch_size must be positive")
+            raise ValueError("%s: batch_size must be positive" % name)
         was_training = self.training
         self.eval()
         try:
@@ -317,22 +341,22 @@ class GIN_InfoMaxReg(nn.Module):
             P.update(buffers)
             ns = [len(g.g) for g in graphs]
             ragged = any(k != ns[0] for k in ns)
-            F0 = self.mlps[0].linear.in_features if self.num_mlp_layers == 1 else self.mlps[0].linears[0].in_features
-            dev = self.eps.device
-            full = None if ragged else torch.empty((len(classes), len(graphs), ns[0], F0), dtype=torch.float32,
-                                                   device=dev)
+            if square:
+                tail = (ns[0],)
+            full = None if ragged else torch.empty((len(classes), len(graphs), ns[0]) + tail, dtype=torch.float32,
+                                                   device=self.eps.device)
             per_graph = [[] for _ in classes]
-            routes = []
             for i0 in range(0, len(graphs), batch_size):
                 chunk = graphs[i0:i0 + batch_size]
                 batch = self._batch_of(chunk)
-                dst = None if full is None else [full[ci, i0:i0 + len(chunk)].view(-1, F0) for ci in range(len(classes))]
-                res = self._saliency_batch(chunk, batch, P, classes, dst, routes)
-                if full is None:
-                    offs = np.asarray(batch.node_off_host)
-                    for ci, r in enumerate(res):
-                        per_graph[ci] += [r[offs[j]:offs[j + 1]] for j in range(len(chunk))]
-            self.saliency_routes = routes
+                if full is not None:
+                    run_batch(chunk, batch, P, classes, full[:, i0:i0 + len(chunk)].view(len(classes), -1, *tail))
+                    continue
+                res = run_batch(chunk, batch, P, classes, None)
+                offs = np.asarray(batch.node_off_host)
+                for ci in range(len(classes)):
+                    per_graph[ci] += [res[ci][offs[j]:offs[j + 1], :offs[j + 1] - offs[j]] if square
+                                      else res[ci][offs[j]:offs[j + 1]] for j in range(len(chunk))]
             if full is not None:
                 return full[0] if single else full
             return per_graph[0] if single else per_graph
@@ -342,21 +366,18 @@ class GIN_InfoMaxReg(nn.Module):
     def _saliency_batch(self, chunk, batch, P, classes, dst, routes):
         """saliency() of one batch: a list of [N, F0] tensors (written into dst when given), one per class"""
         X = batch.arena.features(batch)
-        if not saliency_hip_ok(self._spec, batch, X, P):
+        if saliency_decline(self._spec, batch, X, P, dx=True) is not None:
             routes.append("autograd")
             res = self._saliency_autograd(batch, classes)
-        elif bool(torch.isfinite(X).all()):
-            routes.append("hip")
-            return saliency_hip(self._spec, batch, X.detach(), P, classes, outs=dst)
         else:
+            bad = _nonfinite_graphs(batch, X)
+            if bad is None:
+                routes.append("hip")
+                return saliency_hip(self._spec, batch, X.detach(), P, classes, outs=dst)
             # a graph with a non-finite feature: its saliency is whatever compute_saliency's backward makes of the
             # NaN / inf (the kernel's masks would quietly turn it into zeros), so such a graph takes the autograd route
             # on its own -- exactly compute_saliency's kernels -- and the others stay on the kernel
             B = batch.B
-            counts = torch.as_tensor(np.diff(batch.node_off_host), device=X.device)
-            gid = torch.repeat_interleave(torch.arange(B, device=X.device), counts)
-            bad = torch.zeros(B, dtype=torch.int32, device=X.device).index_add_(
-                0, gid, (~torch.isfinite(X).all(1)).to(torch.int32)).cpu().numpy() > 0
             parts = [None] * B
             good = [j for j in range(B) if not bad[j]]
             if good:
@@ -414,74 +435,25 @@ class GIN_InfoMaxReg(nn.Module):
         [len(graphs), n] for an int `cls` and [len(cls), len(graphs), n] for a sequence; for graphs of different node
         counts a list of [n_g] tensors (a list of such lists for a sequence `cls`).  No parameter .grad, BatchNorm
         buffer or numpy RNG state is touched, and the train / eval mode is restored on exit."""
-        single = isinstance(cls, (int, np.integer))
-        classes = [int(cls)] if single else [int(c) for c in cls]
-        n_cls = self.linears_prediction[0].out_features
         if kind not in self.CAM_KINDS:
             raise ValueError("class_activation: kind must be one of %s, not %r" % (self.CAM_KINDS, kind))
-        if len(graphs) == 0:
-            raise ValueError("class_activation: empty list of graphs")
-        if not classes:
-            raise ValueError("class_activation: empty sequence of classes")
-        for c in classes:
-            if not 0 <= c < n_cls:
-                raise ValueError("class_activation: class %d out of range for a %d-class model" % (c, n_cls))
-        if batch_size < 1:
-            raise ValueError("class_activation: batch_size must be positive")
-        was_training = self.training
-        self.eval()
-        try:
-            names, tensors, buffers = self._param_lists()
-            P = dict(zip(names, tensors))
-            P.update(buffers)
-            ns = [len(g.g) for g in graphs]
-            ragged = any(k != ns[0] for k in ns)
-            full = None if ragged else torch.empty((len(classes), len(graphs), ns[0]), dtype=torch.float32,
-                                                   device=self.eps.device)
-            per_graph = [[] for _ in classes]
-            for i0 in range(0, len(graphs), batch_size):
-                chunk = graphs[i0:i0 + batch_size]
-                batch = self._batch_of(chunk)
-                res = self._cam_batch(chunk, batch, P, classes, kind)          # [len(classes), N]
-                if full is not None:
-                    full[:, i0:i0 + len(chunk)] = res.view(len(classes), len(chunk), ns[0])
-                else:
-                    offs = np.asarray(batch.node_off_host)
-                    for ci in range(len(classes)):
-                        per_graph[ci] += [res[ci, offs[j]:offs[j + 1]] for j in range(len(chunk))]
-            if full is not None:
-                return full[0] if single else full
-            return per_graph[0] if single else per_graph
-        finally:
-            self.train(was_training)
+        return self._interpret("class_activation", graphs, cls, batch_size, (),
+                               functools.partial(self._cam_batch, kind=kind))
 
-    def _cam_batch(self, chunk, batch, P, classes, kind):
-        """class_activation() of one batch: [len(classes), N]"""
+    def _cam_batch(self, chunk, batch, P, classes, dst, kind):
+        """class_activation() of one batch: [len(classes), N] (dst when given)"""
         X = batch.arena.features(batch).detach()
         launch_device(X, P["eps"])                          # no CPU fallback: GnmError before any shape question
         if kind == "activation":
-            return class_activation_hip(self._spec, batch, X, P, classes)
-        why = saliency_maps_decline(self._spec, batch, X, P)
+            return class_activation_hip(self._spec, batch, X, P, classes, out=dst)
+        why = saliency_decline(self._spec, batch, X, P, dx=False)
         if why is not None:
             raise ValueError("class_activation(kind='gradient') does not cover this batch: %s" % why)
-        if bool(torch.isfinite(X).all()):
-            return saliency_maps_hip(self._spec, batch, X, P, classes)
-        # a graph with a non-finite feature: an all-NaN map (its ReLU masks are meaningless); the others on a batch of
-        # their own, so their maps are those of a clean batch
-        B = batch.B
-        counts = torch.as_tensor(np.diff(batch.node_off_host), device=X.device)
-        gid = torch.repeat_interleave(torch.arange(B, device=X.device), counts)
-        bad = torch.zeros(B, dtype=torch.int32, device=X.device).index_add_(
-            0, gid, (~torch.isfinite(X).all(1)).to(torch.int32)).cpu().numpy() > 0
-        offs = np.asarray(batch.node_off_host)
-        out = torch.full((len(classes), batch.N), float("nan"), dtype=torch.float32, device=X.device)
-        good = [j for j in range(B) if not bad[j]]
-        if good:
-            sub = self._batch_of([chunk[j] for j in good])
-            r = saliency_maps_hip(self._spec, sub, sub.arena.features(sub).detach(), P, classes)
-            for k, j in enumerate(good):
-                out[:, offs[j]:offs[j + 1]] = r[:, sub.node_off_host[k]:sub.node_off_host[k + 1]]
-        return out
+        bad = _nonfinite_graphs(batch, X)
+        if bad is None:
+            return saliency_maps_hip(self._spec, batch, X, P, classes, out=dst)
+        return self._clean_graphs_apart(chunk, batch, bad, dst, (len(classes), batch.N),
+                                        lambda sub, Xs: saliency_maps_hip(self._spec, sub, Xs, P, classes))
 
     def edge_saliency(self, graphs, cls, batch_size=64):
         """Connectivity saliency of many graphs in batches: which CONNECTION matters for a class.  For graph g with n
@@ -501,73 +473,36 @@ class GIN_InfoMaxReg(nn.Module):
         node counts a list of [n_g, n_g] tensors (a list of such lists for a sequence `cls`).  The output is n^2 per
         graph and class, hence the smaller default batch.  No parameter .grad, BatchNorm buffer or numpy RNG state is
         touched, and the train / eval mode is restored on exit."""
-        single = isinstance(cls, (int, np.integer))
-        classes = [int(cls)] if single else [int(c) for c in cls]
-        n_cls = self.linears_prediction[0].out_features
-        if len(graphs) == 0:
-            raise ValueError("edge_saliency: empty list of graphs")
-        if not classes:
-            raise ValueError("edge_saliency: empty sequence of classes")
-        for c in classes:
-            if not 0 <= c < n_cls:
-                raise ValueError("edge_saliency: class %d out of range for a %d-class model" % (c, n_cls))
-        if batch_size < 1:
-            raise ValueError("edge_saliency: batch_size must be positive")
-        was_training = self.training
-        self.eval()
-        try:
-            names, tensors, buffers = self._param_lists()
-            P = dict(zip(names, tensors))
-            P.update(buffers)
-            ns = [len(g.g) for g in graphs]
-            ragged = any(k != ns[0] for k in ns)
-            n0 = ns[0]
-            full = None if ragged else torch.empty((len(classes), len(graphs), n0, n0), dtype=torch.float32,
-                                                   device=self.eps.device)
-            per_graph = [[] for _ in classes]
-            for i0 in range(0, len(graphs), batch_size):
-                chunk = graphs[i0:i0 + batch_size]
-                batch = self._batch_of(chunk)
-                res = self._edge_saliency_batch(chunk, batch, P, classes)       # [len(classes), N, n_max]
-                offs = np.asarray(batch.node_off_host)
-                if full is not None:
-                    full[:, i0:i0 + len(chunk)] = res.view(len(classes), len(chunk), n0, n0)
-                else:
-                    for ci in range(len(classes)):
-                        per_graph[ci] += [res[ci, offs[j]:offs[j + 1], :offs[j + 1] - offs[j]]
-                                          for j in range(len(chunk))]
-            if full is not None:
-                return full[0] if single else full
-            return per_graph[0] if single else per_graph
-        finally:
-            self.train(was_training)
+        return self._interpret("edge_saliency", graphs, cls, batch_size, (), self._edge_saliency_batch, square=True)
 
-    def _edge_saliency_batch(self, chunk, batch, P, classes):
-        """edge_saliency() of one batch: [len(classes), N, n_max]"""
+    def _edge_saliency_batch(self, chunk, batch, P, classes, dst):
+        """edge_saliency() of one batch: [len(classes), N, n_max] (dst when given)"""
         X = batch.arena.features(batch).detach()
         launch_device(X, P["eps"])                          # no CPU fallback: GnmError before any shape question
-        why = saliency_maps_decline(self._spec, batch, X, P)
+        why = saliency_decline(self._spec, batch, X, P, dx=False)
         if why is not None:
             raise ValueError("edge_saliency does not cover this batch: %s" % why)
-        if bool(torch.isfinite(X).all()):
-            return edge_saliency_hip(self._spec, batch, X, P, classes)
-        # a graph with a non-finite feature: an all-NaN map; the others on a batch of their own, so their maps are
-        # those of a clean batch
-        B = batch.B
-        counts = torch.as_tensor(np.diff(batch.node_off_host), device=X.device)
-        gid = torch.repeat_interleave(torch.arange(B, device=X.device), counts)
-        bad = torch.zeros(B, dtype=torch.int32, device=X.device).index_add_(
-            0, gid, (~torch.isfinite(X).all(1)).to(torch.int32)).cpu().numpy() > 0
-        offs = np.asarray(batch.node_off_host)
-        out = torch.full((len(classes), batch.N, batch.n_max), float("nan"), dtype=torch.float32, device=X.device)
-        good = [j for j in range(B) if not bad[j]]
+        bad = _nonfinite_graphs(batch, X)
+        if bad is None:
+            return edge_saliency_hip(self._spec, batch, X, P, classes, out=dst)
+        return self._clean_graphs_apart(chunk, batch, bad, dst, (len(classes), batch.N, batch.n_max),
+                                        lambda sub, Xs: edge_saliency_hip(self._spec, sub, Xs, P, classes))
+
+    def _clean_graphs_apart(self, chunk, batch, bad, dst, shape, run):
+        """The gradient class activation and edge maps of a batch with non-finite graphs (`bad`): an all-NaN map for
+        each of those (its ReLU masks are meaningless), and the others run(sub, X) on a batch of their own, so their
+        maps are those of a clean batch, scattered into place.  Returns dst, or a new array of `shape`, [C, N, ...]."""
+        out = dst if dst is not None else torch.empty(shape, dtype=torch.float32, device=self.eps.device)
+        out.fill_(float("nan"))
+        good = [j for j in range(batch.B) if not bad[j]]
         if good:
             sub = self._batch_of([chunk[j] for j in good])
-            r = edge_saliency_hip(self._spec, sub, sub.arena.features(sub).detach(), P, classes)
-            so = np.asarray(sub.node_off_host)
+            r = run(sub, sub.arena.features(sub).detach())
+            offs, so = np.asarray(batch.node_off_host), np.asarray(sub.node_off_host)
             for k, j in enumerate(good):
                 nj = int(so[k + 1] - so[k])
-                out[:, offs[j]:offs[j + 1], :nj] = r[:, so[k]:so[k + 1], :nj]
+                # (the last axis cropped to the graph's n_j: an edge map's columns; a no-op for a [C, N] map)
+                out[:, offs[j]:offs[j + 1]][..., :nj] = r[:, so[k]:so[k + 1]][..., :nj]
         return out
 
     # ------------------------------------------------------------------ evaluation replay
