@@ -893,23 +893,8 @@ __global__ void __launch_bounds__(1024) gnm_agg_kernel(const AggArgs p) {
     } else if ((t) >= 1) {                    \
         GNM_D1(B)                             \
     }
-// 8 double steps = 16 reads in flight (64 registers: the forward kernel only)
-#define GNM_D8W(S)                                                                                  \
-    {                                                                                               \
-        const f32x4 a0_ = GNM_LO(S), b0_ = GNM_HI(S), a1_ = GNM_LO(S + 1), b1_ = GNM_HI(S + 1),     \
-                    a2_ = GNM_LO(S + 2), b2_ = GNM_HI(S + 2), a3_ = GNM_LO(S + 3), b3_ = GNM_HI(S + 3), \
-                    a4_ = GNM_LO(S + 4), b4_ = GNM_HI(S + 4), a5_ = GNM_LO(S + 5), b5_ = GNM_HI(S + 5), \
-                    a6_ = GNM_LO(S + 6), b6_ = GNM_HI(S + 6), a7_ = GNM_LO(S + 7), b7_ = GNM_HI(S + 7); \
-        acc4(acc, ((a0_ + b0_) + (a1_ + b1_)) + ((a2_ + b2_) + (a3_ + b3_)));                       \
-        acc4(acc, ((a4_ + b4_) + (a5_ + b5_)) + ((a6_ + b6_) + (a7_ + b7_)));                       \
-    }
-#ifndef GNM_LADDER_MODE
-#define GNM_LADDER_MODE 0
-#endif
-// nd in 0..16 double steps.  Mode 0: exactly nd, in blocks of 4 + a tail of 2 / 1.  Tuning variants: 1 = first 8 as
-// one 16-deep block; 2 = nd rounded up to whole blocks of 4 (padding reads the zero row: no tail pieces);
-// 3 = both.
-#define GNM_DLADDER_EXACT(nd)                             \
+// nd in 0..16 double steps: exactly nd, in blocks of 4 + a tail of 2 / 1.
+#define GNM_DLADDER(nd)                                   \
     if ((nd) >= 4) {                                      \
         GNM_D4(0)                                         \
         if ((nd) >= 8) {                                  \
@@ -930,55 +915,6 @@ __global__ void __launch_bounds__(1024) gnm_agg_kernel(const AggArgs p) {
     } else {                                              \
         GNM_DTAIL(0, nd)                                  \
     }
-#define GNM_DLADDER_D8(nd)                                \
-    if (!STATS && (nd) >= 8) {                            \
-        GNM_D8W(0)                                        \
-        if ((nd) >= 12) {                                 \
-            GNM_D4(8)                                     \
-            if ((nd) >= 16) {                             \
-                GNM_D4(12)                                \
-            } else {                                      \
-                GNM_DTAIL(12, (nd) - 12)                  \
-            }                                             \
-        } else {                                          \
-            GNM_DTAIL(8, (nd) - 8)                        \
-        }                                                 \
-    } else {                                              \
-        GNM_DLADDER_EXACT(nd)                             \
-    }
-#define GNM_DLADDER_PAD(nd)                               \
-    if ((nd) > 0) {                                       \
-        GNM_D4(0)                                         \
-        if ((nd) > 4) {                                   \
-            GNM_D4(4)                                     \
-            if ((nd) > 8) {                               \
-                GNM_D4(8)                                 \
-                if ((nd) > 12) GNM_D4(12)                 \
-            }                                             \
-        }                                                 \
-    }
-#define GNM_DLADDER_D8PAD(nd)                             \
-    if (!STATS && (nd) > 4) {                             \
-        GNM_D8W(0)                                        \
-        if ((nd) > 8) {                                   \
-            if ((nd) > 12) {                              \
-                GNM_D8W(8)                                \
-            } else {                                      \
-                GNM_D4(8)                                 \
-            }                                             \
-        }                                                 \
-    } else {                                              \
-        GNM_DLADDER_PAD(nd)                               \
-    }
-#if GNM_LADDER_MODE == 1
-#define GNM_DLADDER(nd) GNM_DLADDER_D8(nd)
-#elif GNM_LADDER_MODE == 2
-#define GNM_DLADDER(nd) GNM_DLADDER_PAD(nd)
-#elif GNM_LADDER_MODE == 3
-#define GNM_DLADDER(nd) GNM_DLADDER_D8PAD(nd)
-#else
-#define GNM_DLADDER(nd) GNM_DLADDER_EXACT(nd)
-#endif
 // single-register forms (ids fetched in place beyond the 128-id window: degree > 128)
 #define GNM_S1(S) acc4(acc, GNM_RD(S));
 #define GNM_S2(S)                                                \

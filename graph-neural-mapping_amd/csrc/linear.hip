@@ -22,8 +22,6 @@
 // tuning knobs, read once per process
 static bool lin_force_generic() { static const bool v = getenv("GNM_LIN_GENERIC") != nullptr; return v; }
 static bool lin_no_stream() { static const bool v = getenv("GNM_LIN_NO_STREAM") != nullptr; return v; }   // tuning: A/B
-static bool linbwd_no_pipe() { static const bool v = getenv("GNM_LINBWD_NO_PIPE") != nullptr; return v; }   // tuning: A/B
-static bool linbwd_no_samez() { static const bool v = getenv("GNM_LINBWD_NO_SAMEZ") != nullptr; return v; }
 
 struct LinArgs {
     const float* X;
@@ -1297,17 +1295,8 @@ static int launch_lin_split128(const LinArgs& a0, int grid, hipStream_t s) {
 }
 
 static bool lin_no_split() {
-#ifdef GNM_LIN_FORCE_NO_SPLIT          // variant builds for paired timing (tools/build_variant.py)
-    return true;
-#else
     static const bool v = gnm_env_int("GNM_LIN_NO_SPLIT", 0) != 0;     // A/B knob: keep the fp32 matrix instruction
     return v;
-#endif
-}
-// the fused backward kernels' products alone (GNM_LIN_NO_SPLIT covers them too)
-static bool linbwd_no_split() {
-    static const bool v = gnm_env_int("GNM_LINBWD_NO_SPLIT", 0) != 0;
-    return v || lin_no_split();
 }
 
 static size_t lin_lds_bytes(int K, int KC, int HT) {
@@ -2042,11 +2031,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
         for (int j = 0; j < NLD; ++j) {
             const int grow = min(r0 + lrow0 + j * RSTEP, nlast);
             g4[j] = *reinterpret_cast<const float4*>(p.G + (size_t)grow * p.ldg + 4 * c4);
-#ifdef GNM_EXP_NOZ          // timing experiment only (wrong results): what the kernel costs without the Z stream
-            z4[j] = g4[j];
-#else
             z4[j] = *reinterpret_cast<const float4*>(p.Z + (size_t)grow * p.ldz + 4 * c4);
-#endif
         }
         if constexpr (SAMEZ) {
             mu = *reinterpret_cast<const float4*>(p.mean + 4 * c4);
@@ -2424,11 +2409,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArg
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
             g4[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, gz_voff_g, j * gz_step_g, 0);
-#ifdef GNM_EXP_NOZ
-            z4[j] = g4[j];
-#else
             z4[j] = __builtin_amdgcn_raw_buffer_load_b128(rz, gz_voff_z, j * gz_step_z, 0);
-#endif
         }
     };
     auto do_tile = [&](int t, int t_next) {
@@ -2647,19 +2628,18 @@ static int launch_lb(const LbArgs& a, int grid, hipStream_t s) {
 //    layout too (4-byte loads, 128 contiguous bytes per half-wave) and dZ is formed there; the BatchNorm coefficients
 //    are per-lane scalars;
 //  * the weight-gradient product takes its dZ operand from those registers (no column reads of the LDS image) and its
-//    X operand from lane = column loads of the rows in the same order; WG16: both are split into three bf16 planes and
-//    the product runs as 48 bf16 instructions instead of 64 fp32 ones (a quarter of the matrix-pipe time);
+//    X operand from lane = column loads of the rows in the same order; both are split into three bf16 planes and the
+//    product runs as 48 bf16 instructions instead of 64 fp32 ones (a quarter of the matrix-pipe time);
 //  * only dgrad still needs the transpose: dZ goes through the wave's LDS image once, row-wise out;
 //  * G AND the row-wise X fragments of the wave's next tile are requested before the weight-gradient product (the
-//    registers Z used to occupy), in both forms -- the statistics form above had no room for that;
+//    registers Z used to occupy) -- the statistics form above had no room for that;
 //  * eight waves per workgroup share the two weight images (forward orientation for Z, k-major for dgrad: 48 KB) and the
 //    workgroup writes TWO rows of partials (waves 0-3, 4-7), so gnm_linear_bwd_grid(N) rows exist as before.
-// SAMEZ: the second Linear of an MLP (the lower BatchNorm's input is X, its affine the prologue) -- ReLU mask and that
-// BatchNorm's backward sums on the dX accumulators, as in gnm_linear_bwd_fused_kernel.  !SAMEZ: no lower statistics.
+// No lower BatchNorm statistics: the second Linear of an MLP keeps gnm_linear_bwd_fused_kernel (DESIGN_HISTORY.md,
+// "Retired variants").
 // ---------------------------------------------------------------------------------
 static constexpr int kRzWaves = 8;
 
-template <bool SAMEZ, bool WG16>
 __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const LbArgs p) {
     constexpr int KP = 64, HP = 64, XS = 68, EW = 512, NW = kRzWaves, NT = NW * 64, TILE = 16 * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2694,23 +2674,12 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
         psv[idx] = pro ? p.pro_scale[idx] : 1.f;
         psv[64 + idx] = pro ? p.pro_shift[idx] : 0.f;
     }
-    // SAMEZ: the lower BatchNorm's mean / rstd and the lane's running sums live in LDS too (with them and the prologue
-    // vectors in registers the statistics form spilled 126-191 registers; the plain form sits at 256 exactly)
-    float psc[2], psh[2];                                         // (plain form: registers -- from LDS it spilled 34)
+    // the wgrad prologue's per-lane scale / shift in registers (256 registers exactly; read from LDS it spilled 34)
+    float psc[2], psh[2];
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-        psc[b] = (pro && !SAMEZ) ? p.pro_scale[32 * b + i] : 1.f;
-        psh[b] = (pro && !SAMEZ) ? p.pro_shift[32 * b + i] : 0.f;
-    }
-    float* lstat = psv + 2 * 64;                                  // [2][64]: lower mean, rstd
-    float* lsum = lstat + 2 * 64 + wave * 4 * 64;                 // [NW][2 c][2][64 lanes]: this wave's sums
-    if constexpr (SAMEZ) {
-        for (int idx = tid; idx < 64; idx += NT) {
-            lstat[idx] = p.s_mean[idx];
-            lstat[64 + idx] = p.s_rstd[idx];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) lsum[q * 64 + lane] = 0.f;
+        psc[b] = pro ? p.pro_scale[32 * b + i] : 1.f;
+        psh[b] = pro ? p.pro_shift[32 * b + i] : 0.f;
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);           // vmcnt(0): nothing from the preamble is pending inside the tile loop
     __syncthreads();
@@ -2824,7 +2793,7 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // X in the accumulators' row order (wgrad operand; SAMEZ: the values under the dX accumulators): in flight
+        // X in the accumulators' row order (wgrad operand): in flight
         // during the dgrad MFMAs (cache hits: the tile was read row-wise for Z)
         float xv[16][2];
         {
@@ -2868,39 +2837,11 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();          // the dZ image has been read
         GNM_RSTAMP(5 + 6 * min(tk, 9))
-        // ---- dX out (SAMEZ: masked by the lower ReLU, and that BatchNorm's backward sums) ---------------------------
+        // ---- dX out ------------------------------------------------------------------------------------------------
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            // (read once per column block: between the image stores below the compiler cannot keep an LDS value)
-            const float esc = SAMEZ ? psv[32 * c + i] : 1.f, esh = SAMEZ ? psv[64 + 32 * c + i] : 0.f;
+        for (int c = 0; c < 2; ++c)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int lrow = (r & 3) + 8 * (r >> 2) + 4 * h;
-                float gg = dacc[c][r];
-                if constexpr (SAMEZ) {
-                    const float z = xv[r][c];
-                    if (!(z * esc + esh > 0.f)) gg = 0.f;
-                    dacc[c][r] = gg;
-                }
-                Xs[lrow * XS + 32 * c + i] = gg;
-            }
-        }
-        if constexpr (SAMEZ) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const float lmu = lstat[32 * c + i], lrs = lstat[64 + 32 * c + i];
-                float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    if ((r & 3) + 8 * (r >> 2) + 4 * h < rows) {
-                        s1 += dacc[c][r];
-                        s2 += dacc[c][r] * ((xv[r][c] - lmu) * lrs);
-                    }
-                }
-                lsum[(2 * c + 0) * 64 + lane] += s1;
-                lsum[(2 * c + 1) * 64 + lane] += s2;
-            }
-        }
+            for (int r = 0; r < 16; ++r) Xs[((r & 3) + 8 * (r >> 2) + 4 * h) * XS + 32 * c + i] = dacc[c][r];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -2917,72 +2858,46 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         GNM_RSTAMP(6 + 6 * min(tk, 9))
-        // the next tile: G before the weight-gradient product; the row-wise X fragments too where the registers allow it
-        // (SAMEZ carries eight more per-lane values through the tile and spilled 126 with both in flight: X follows the product)
+        // the next tile: G and the row-wise X fragments before the weight-gradient product
         load_next_g(t_next);                      // past the wave's last tile: empty descriptors, no traffic
-        if constexpr (!SAMEZ) load_next_x(t_next);
+        load_next_x(t_next);
         // ---- dW += dZ^T f(X): both operands from registers, batch rows in the accumulators' order ---------------------
-        if constexpr (WG16) {
 #pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                lin_bf16x8 dp[2][3], xp[2][3];
+        for (int m = 0; m < 2; ++m) {
+            lin_bf16x8 dp[2][3], xp[2][3];
 #pragma unroll
-                for (int a = 0; a < 2; ++a) {
-                    float f[8];
-                    u32x4 p1, p2, p3;
+            for (int a = 0; a < 2; ++a) {
+                float f[8];
+                u32x4 p1, p2, p3;
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) f[j] = dz[a][8 * m + j];
-                    lin_split8(f, p1, p2, p3);
-                    dp[a][0] = __builtin_bit_cast(lin_bf16x8, p1); dp[a][1] = __builtin_bit_cast(lin_bf16x8, p2);
-                    dp[a][2] = __builtin_bit_cast(lin_bf16x8, p3);
+                for (int j = 0; j < 8; ++j) f[j] = dz[a][8 * m + j];
+                lin_split8(f, p1, p2, p3);
+                dp[a][0] = __builtin_bit_cast(lin_bf16x8, p1); dp[a][1] = __builtin_bit_cast(lin_bf16x8, p2);
+                dp[a][2] = __builtin_bit_cast(lin_bf16x8, p3);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        float x = xv[8 * m + j][a];
-                        if (pro) {
-                            x = SAMEZ ? x * psv[32 * a + i] + psv[64 + 32 * a + i] : x * psc[a] + psh[a];
-                            if (p.pro_relu) x = gnm_relu(x);
-                        }
-                        f[j] = x;
-                    }
-                    lin_split8(f, p1, p2, p3);
-                    xp[a][0] = __builtin_bit_cast(lin_bf16x8, p1); xp[a][1] = __builtin_bit_cast(lin_bf16x8, p2);
-                    xp[a][2] = __builtin_bit_cast(lin_bf16x8, p3);
-                }
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][2], wacc[a][b], 0, 0, 0);
-                        wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][2], xp[b][0], wacc[a][b], 0, 0, 0);
-                        wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][1], xp[b][1], wacc[a][b], 0, 0, 0);
-                        wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][1], wacc[a][b], 0, 0, 0);
-                        wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][1], xp[b][0], wacc[a][b], 0, 0, 0);
-                        wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][0], wacc[a][b], 0, 0, 0);
-                    }
-            }
-        } else {
-#pragma unroll
-            for (int sidx = 0; sidx < 16; ++sidx) {
-                float xf[2];
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    float x = xv[sidx][b];
+                for (int j = 0; j < 8; ++j) {
+                    float x = xv[8 * m + j][a];
                     if (pro) {
-                        x = SAMEZ ? x * psv[32 * b + i] + psv[64 + 32 * b + i] : x * psc[b] + psh[b];
+                        x = x * psc[a] + psh[a];
                         if (p.pro_relu) x = gnm_relu(x);
                     }
-                    xf[b] = x;
+                    f[j] = x;
                 }
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-                        wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(dz[a][sidx], xf[b], wacc[a][b], 0, 0, 0);
+                lin_split8(f, p1, p2, p3);
+                xp[a][0] = __builtin_bit_cast(lin_bf16x8, p1); xp[a][1] = __builtin_bit_cast(lin_bf16x8, p2);
+                xp[a][2] = __builtin_bit_cast(lin_bf16x8, p3);
             }
-        }
-        if constexpr (SAMEZ) {
-            __builtin_amdgcn_sched_barrier(0);
-            load_next_x(t_next);      // (requested before the product it cost 24 spilled registers per tile: 122 us)
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][2], wacc[a][b], 0, 0, 0);
+                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][2], xp[b][0], wacc[a][b], 0, 0, 0);
+                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][1], xp[b][1], wacc[a][b], 0, 0, 0);
+                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][1], wacc[a][b], 0, 0, 0);
+                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][1], xp[b][0], wacc[a][b], 0, 0, 0);
+                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][0], wacc[a][b], 0, 0, 0);
+                }
         }
         GNM_RSTAMP(7 + 6 * min(tk, 9))
         ++tk;
@@ -2999,38 +2914,6 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
     __builtin_amdgcn_s_waitcnt(0x0F70);
     GNM_RSTAMP(62)
 
-    // ---- lower-BatchNorm sums: two rows of partials per workgroup (waves 0-3, 4-7), fixed order ----
-    if constexpr (SAMEZ) {
-        __syncthreads();
-        double* sred = reinterpret_cast<double*>(smem);           // [NW][2][KP]
-        float cs1[2], cs2[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            cs1[c] = lsum[(2 * c + 0) * 64 + lane];
-            cs2[c] = lsum[(2 * c + 1) * 64 + lane];
-        }
-        __syncthreads();                                          // (sred overlays nothing of lsum, but the weight images)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {                             // the two half-waves hold the same columns
-            double d1 = (double)cs1[c], d2 = (double)cs2[c];
-            d1 += __shfl_xor(d1, 32, 64);
-            d2 += __shfl_xor(d2, 32, 64);
-            if (h == 0) {
-                sred[(wave * 2 + 0) * KP + 32 * c + i] = d1;
-                sred[(wave * 2 + 1) * KP + 32 * c + i] = d2;
-            }
-        }
-        __syncthreads();
-        for (int idx = tid; idx < 2 * 2 * KP; idx += NT) {
-            const int grp = idx / (2 * KP), rest = idx - grp * 2 * KP;
-            const int which = rest / KP, col = rest - which * KP;
-            const int row = blockIdx.x * 2 + grp;
-            if (row >= p.part_rows) continue;
-            double sum = 0.0;
-            for (int w = 4 * grp; w < 4 * grp + 4; ++w) sum += sred[(w * 2 + which) * KP + col];
-            p.s_partial[((size_t)row * 2 + which) * p.K + col] = sum;
-        }
-    }
     // ---- dW / db: the waves of each half in a fixed order ----
     __syncthreads();
     float* dump = reinterpret_cast<float*>(smem);                 // [NW][4][16][64] + [NW][2][64]
@@ -3072,13 +2955,12 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
     GNM_RSTAMP(63)
 }
 
-template <bool SAMEZ, bool WG16>
 static int launch_lb_rz(const LbArgs& a, int grid, hipStream_t s) {
-    size_t lds = (size_t)6 * 512 * 16 + (size_t)kRzWaves * 32 * 68 * 4 + (size_t)(8 + 2 + kRzWaves * 4) * 64 * 4;
+    size_t lds = (size_t)6 * 512 * 16 + (size_t)kRzWaves * 32 * 68 * 4 + (size_t)8 * 64 * 4;
     const size_t dump = ((size_t)kRzWaves * 4 * 1024 + (size_t)kRzWaves * 2 * 64) * 4;
     if (dump > lds) lds = dump;
-    GNM_ALLOW_FULL_LDS((&gnm_linear_bwd_rz_kernel<SAMEZ, WG16>));
-    hipLaunchKernelGGL((gnm_linear_bwd_rz_kernel<SAMEZ, WG16>), dim3((grid + 1) / 2), dim3(kRzWaves * 64), lds, s, a);
+    GNM_ALLOW_FULL_LDS((&gnm_linear_bwd_rz_kernel));
+    hipLaunchKernelGGL(gnm_linear_bwd_rz_kernel, dim3((grid + 1) / 2), dim3(kRzWaves * 64), lds, s, a);
     GNM_CHECK_LAUNCH();
     return GNM_OK;
 }
@@ -3381,26 +3263,24 @@ extern "C" int gnm_linear_bwd_fused(const float* G, int ldg, const float* Z, int
     int rc = GNM_ERR_UNSUPPORTED;
     const int KT = narrow ? 0 : K / 32, HT = H / 32;
     // no statistics to reduce (the first Linear of an MLP): the cross-tile pipelined kernel
-    const bool pipe = !narrow && !sZ && !linbwd_no_pipe();
-    if (pipe) {
+    if (!narrow && !sZ) {
         if (KT == 1 && HT == 1) rc = launch_lb_pipe<1, 1>(a, grid, s);
         if (KT == 2 && HT == 1) rc = launch_lb_pipe<2, 1>(a, grid, s);
         if (KT == 1 && HT == 2) rc = launch_lb_pipe<1, 2>(a, grid, s);
-        if (KT == 2 && HT == 2) rc = linbwd_no_split() ? launch_lb_pipe<2, 2>(a, grid, s) : launch_lb_pipe<2, 2, true>(a, grid, s);
+        if (KT == 2 && HT == 2) rc = lin_no_split() ? launch_lb_pipe<2, 2>(a, grid, s) : launch_lb_pipe<2, 2, true>(a, grid, s);
     }
     if (narrow && HT == 1) rc = launch_lb<1, 1, false, true>(a, grid, s);
     if (narrow && HT == 2)
-        rc = linbwd_no_split() ? launch_lb<1, 2, false, true>(a, grid, s) : launch_lb<1, 2, false, true, false, true>(a, grid, s);
-    if (!pipe && KT == 1 && HT == 1) rc = sZ ? launch_lb<1, 1, true>(a, grid, s) : launch_lb<1, 1, false>(a, grid, s);
-    if (!pipe && KT == 2 && HT == 1) rc = sZ ? launch_lb<2, 1, true>(a, grid, s) : launch_lb<2, 1, false>(a, grid, s);
-    if (!pipe && KT == 1 && HT == 2) rc = sZ ? launch_lb<1, 2, true>(a, grid, s) : launch_lb<1, 2, false>(a, grid, s);
+        rc = lin_no_split() ? launch_lb<1, 2, false, true>(a, grid, s) : launch_lb<1, 2, false, true, false, true>(a, grid, s);
+    if (sZ && KT == 1 && HT == 1) rc = launch_lb<1, 1, true>(a, grid, s);
+    if (sZ && KT == 2 && HT == 1) rc = launch_lb<2, 1, true>(a, grid, s);
+    if (sZ && KT == 1 && HT == 2) rc = launch_lb<1, 2, true>(a, grid, s);
     // the second Linear of an MLP: the lower BatchNorm's input is this Linear's input and its affine is the prologue
-    const bool samez = sZ && sZ == X && ldsz == ldx && s_scale == pro_scale && s_shift == pro_shift && pro_relu &&
-                       !linbwd_no_samez();
-    if (!pipe && KT == 2 && HT == 2)
-        rc = samez ? (linbwd_no_split() ? launch_lb<2, 2, true, false, true>(a, grid, s)
-                                        : launch_lb<2, 2, true, false, true, true>(a, grid, s))
-                   : (sZ ? launch_lb<2, 2, true>(a, grid, s) : launch_lb<2, 2, false>(a, grid, s));
+    const bool samez = sZ && sZ == X && ldsz == ldx && s_scale == pro_scale && s_shift == pro_shift && pro_relu;
+    if (sZ && KT == 2 && HT == 2)
+        rc = samez ? (lin_no_split() ? launch_lb<2, 2, true, false, true>(a, grid, s)
+                                     : launch_lb<2, 2, true, false, true, true>(a, grid, s))
+                   : launch_lb<2, 2, true>(a, grid, s);
     if (rc != GNM_OK) return rc;
     if (!dW) return GNM_OK;      // deferred: the partials stay in `workspace` for gnm_reduce_partials_multi
     const long long stride = (long long)H * K + H;
@@ -3412,10 +3292,10 @@ extern "C" int gnm_linear_bwd_fused(const float* G, int ldg, const float* Z, int
 }
 
 // gnm_linear_bwd_fused for a Linear whose output Z the caller does NOT pass: Z = f(X) W^T + bias is recomputed
-// (gnm_linear_bwd_rz_kernel).  K = H = 64 with dA wanted, and either no lower BatchNorm (sZ = NULL) or the lower
-// BatchNorm's input being X with the prologue as its affine (the two Linears of the headline model's MLPs); anything
-// else returns GNM_ERR_UNSUPPORTED and the caller takes gnm_linear_bwd_fused with the stored Z.  Workspace, partial
-// rows and the deferred reduction (dW = NULL) are those of gnm_linear_bwd_fused.
+// (gnm_linear_bwd_rz_kernel).  K = H = 64 with dA wanted and no lower BatchNorm (sZ = NULL: the first Linear of the
+// headline model's MLPs), or the input layer's narrow first Linear; anything else, every sZ != NULL included, returns
+// GNM_ERR_UNSUPPORTED and the caller takes gnm_linear_bwd_fused with the stored Z.  Workspace, partial rows and the
+// deferred reduction (dW = NULL) are those of gnm_linear_bwd_fused.
 extern "C" int gnm_linear_bwd_fused_rz(const float* G, int ldg, const float* bias, const float* mean, const float* rstd,
                                        const float* cA, const float* m1, const float* m2, const float* X, int ldx,
                                        const float* pro_scale, const float* pro_shift, int pro_relu, const float* W,
@@ -3423,23 +3303,14 @@ extern "C" int gnm_linear_bwd_fused_rz(const float* G, int ldg, const float* bia
                                        int N, int K, int H, const float* sZ, int ldsz, const float* s_scale,
                                        const float* s_shift, const float* s_mean, const float* s_rstd,
                                        double* s_partial, void* stream) {
-    static const bool off = gnm_env_int("GNM_LINBWD_NO_RZ", 0) != 0;
-    static const bool wg16 = gnm_env_int("GNM_LINBWD_WG16", 1) != 0;     // A/B knob: weight gradient on the bf16 pipe
-    const bool narrow = K >= 1 && K <= 16 && !sZ && !pro_scale;    // the input layer's first Linear (one 16-wide step of Z): gnm_linear_bwd_rzn_kernel
-    if (off || N <= 0 || (K != 64 && !narrow) || H != 64 || (!dA && !narrow) || lin_force_generic() || linbwd_no_split())
+    // (a form with the lower BatchNorm's statistics measured behind the stored-Z kernel: DESIGN_HISTORY.md, "Retired variants")
+    if (sZ) return GNM_ERR_UNSUPPORTED;
+    const bool narrow = K >= 1 && K <= 16 && !pro_scale;    // the input layer's first Linear (one 16-wide step of Z): gnm_linear_bwd_rzn_kernel
+    if (N <= 0 || (K != 64 && !narrow) || H != 64 || (!dA && !narrow) || lin_force_generic() || lin_no_split())
         return GNM_ERR_UNSUPPORTED;
     if (!narrow && ((ldx & 3) || (lda & 3))) return GNM_ERR_UNSUPPORTED;
     if (!narrow && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(dA)) & 15)) return GNM_ERR_UNSUPPORTED;
     if ((long long)32 * (ldg > ldx ? (ldg > lda ? ldg : lda) : (ldx > lda ? ldx : lda)) * 4 >= (1LL << 31)) return GNM_ERR_UNSUPPORTED;
-    const bool samez = sZ != nullptr;
-    // the statistics form is correct and tested but measured BEHIND the kernel that reads Z (101.9 vs 99.3 us at the
-    // headline shape: its extra per-lane state lives in LDS); the plain form is ahead (87.9 vs 90.9 us).  GNM_LINBWD_RZ_STATS=1
-    // enables it for A/B timing and for its test.
-    static const bool rz_stats = gnm_env_int("GNM_LINBWD_RZ_STATS", 0) != 0;
-    if (samez && !rz_stats) return GNM_ERR_UNSUPPORTED;
-    if (samez && !(sZ == X && ldsz == ldx && s_scale == pro_scale && s_shift == pro_shift && pro_scale && pro_relu &&
-                   s_partial && s_mean && s_rstd))
-        return GNM_ERR_UNSUPPORTED;
     LbArgs a;
     a.sZ = sZ; a.s_scale = s_scale; a.s_shift = s_shift; a.s_mean = s_mean; a.s_rstd = s_rstd;
     a.s_partial = s_partial; a.ldsz = ldsz;
@@ -3455,10 +3326,7 @@ extern "C" int gnm_linear_bwd_fused_rz(const float* G, int ldg, const float* bia
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int grid = gnm_linear_bwd_grid(N);
     a.part_rows = grid;
-    int rc;
-    if (narrow) rc = launch_lb_rzn(a, grid, s);
-    else if (samez) rc = wg16 ? launch_lb_rz<true, true>(a, grid, s) : launch_lb_rz<true, false>(a, grid, s);
-    else rc = wg16 ? launch_lb_rz<false, true>(a, grid, s) : launch_lb_rz<false, false>(a, grid, s);
+    const int rc = narrow ? launch_lb_rzn(a, grid, s) : launch_lb_rz(a, grid, s);
     if (rc != GNM_OK) return rc;
     if (!dW) return GNM_OK;
     const long long stride = (long long)H * K + H;

@@ -23,8 +23,6 @@ from ._cabi import GnmError, check, lib
 # benchmark's 30 % 175 / 83 -- the product already wins at the sparsest point measured, which is the threshold.
 # Tuning knob, read once: GNM_DENSE_FILL (a value > 1 turns the matrix-core path off).
 DENSE_MIN_FILL = float(os.environ.get("GNM_DENSE_FILL", "0.04"))
-# GNM_NO_PARITY_ORDER=1: keep every CSR row in edge_mat order (A/B of the id ordering for the 128-byte-row gather)
-PARITY_ORDER = os.environ.get("GNM_NO_PARITY_ORDER") is None
 
 
 class _Growable:
@@ -150,11 +148,10 @@ class GraphArena:
             check(lib.gnm_csr_transpose(rowptr.ctypes.data, col.ctypes.data, n, rpt.ctypes.data, ct.ctypes.data),
                   "gnm_csr_transpose")
             ct = ct[:E]
-            if PARITY_ORDER:
-                check(lib.gnm_csr_parity_order(rpt.ctypes.data, ct.ctypes.data, n), "gnm_csr_parity_order")
+            check(lib.gnm_csr_parity_order(rpt.ctypes.data, ct.ctypes.data, n), "gnm_csr_parity_order")
             tr = (rpt, ct)
         # rows ordered by id parity for the 128-byte-row gather (include/gnm_hip.h gnm_csr_parity_order): same multiset
-        if E and PARITY_ORDER:
+        if E:
             check(lib.gnm_csr_parity_order(rowptr.ctypes.data, col.ctypes.data, n), "gnm_csr_parity_order")
         return rowptr, col, tr
 
@@ -571,11 +568,11 @@ class PackedStaticBatch:
         # captured kernels read through a device-to-device copy on the caller's stream (round 4).  A host-to-device
         # copy queued on the compute stream is a DMA-engine transfer between two replays: it starts when the previous
         # replay has drained and the next one waits for it (~40 us per step measured); from the side stream it passes
-        # while the previous step computes.  GNM_PACKED_DIRECT=1: the direct copy (A/B).
+        # while the previous step computes.
         # Only where a replay is LONG (a whole training step of hundreds of graphs: gnm/graphs.py CapturedTrainStep
         # asks for it): at one graph per forward the extra stream switch and event cost more host time than the
         # bubble they remove (0.130 -> 0.148 ms per evaluated graph measured with it everywhere).
-        self._two_stage = bool(two_stage) and dev.type == "cuda" and os.environ.get("GNM_PACKED_DIRECT") is None
+        self._two_stage = bool(two_stage) and dev.type == "cuda"
         self._side = torch.cuda.Stream(device=dev) if self._two_stage else None
         self._stage_dev = [torch.zeros(words, dtype=torch.int64, device=dev) for _ in self._ring] if self._two_stage else None
         self._done = [None] * len(self._ring)

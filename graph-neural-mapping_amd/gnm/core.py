@@ -13,7 +13,6 @@ for the sum/average path: on a non-GPU tensor the calls raise.
 """
 import contextlib
 import ctypes as C
-import os
 import types
 
 import numpy as np
@@ -25,9 +24,6 @@ from ._cabi import GnmError, check, lib, ptr
 
 BN_EPS = 1e-5       # nn.BatchNorm1d defaults (mlp.py:38, graphcnn.py:51)
 BN_MOMENTUM = 0.1
-# the dW / db partials of the fused Linear backwards are reduced by ONE launch at the end of the backward
-# (GNM_NO_DEFER_REDUCE=1: one launch after each Linear, for A/B timing)
-DEFER_WGRAD_REDUCE = os.environ.get("GNM_NO_DEFER_REDUCE") is None
 
 
 _STREAM = None      # raw hipStream_t of torch's current stream, fetched once per forward / backward
@@ -301,22 +297,10 @@ def _linear_wide(x, W, w_kmajor, bias, z, N, K, H, pro, stats):
         _linear(x, Wv, w_kmajor, bias[h0:h0 + hw] if bias is not None else None, z[:, h0:h0 + hw], N, K, hw, pro, None)
 
 
-# the K = H = 64 Linear backward recomputes the Linear's output from its input instead of reading it
-# (gnm_linear_bwd_fused_rz); GNM_NO_RZ=1 keeps the form that reads the stored output (A/B and tests)
-RZ_BACKWARD = os.environ.get("GNM_NO_RZ", "0") != "1"
-
-
-# GNM_NO_MASKED_DGRAD=1: the H = 128 Linears' dX without the fused ReLU mask / BatchNorm sums (A/B timing, tests)
-MASKED_DGRAD = os.environ.get("GNM_NO_MASKED_DGRAD", "0") != "1"
-
-# the three [B, L*H]-sized products of the Infomax tail on the hand-written kernel (csrc/sgemm.hip); GNM_NO_SGEMM=1
-# keeps torch.mm (hipBLASLt) for A/B timing
-SMALL_GEMM = os.environ.get("GNM_NO_SGEMM", "0") != "1"
-
-
+# the three [B, L*H]-sized products of the Infomax tail run on the hand-written kernel (csrc/sgemm.hip)
 def _small_gemm(A, a_cols, B, b_cols, out, M, N, K):
     """out[M,N] = A' B' (csrc/sgemm.hip: gnm_small_gemm); False when the kernel declines and the caller uses torch."""
-    if not SMALL_GEMM or A.stride(1) != 1 or B.stride(1) != 1 or out.stride(1) != 1:
+    if A.stride(1) != 1 or B.stride(1) != 1 or out.stride(1) != 1:
         return False
     rc = lib.gnm_small_gemm(A.data_ptr(), A.stride(0), int(a_cols), B.data_ptr(), B.stride(0), int(b_cols), out.data_ptr(),
                             out.stride(0), M, N, K, _stream())
@@ -469,10 +453,6 @@ class DiscUnit:
         self.kscale = 1.0
 
 
-# GNM_NO_DISC_UNIT=1: never produce the by-products (A/B timing against gnm_disc_score_bwd's pass)
-DISC_UNIT = os.environ.get("GNM_NO_DISC_UNIT") is None
-
-
 class ZAct:
     """A layer output that is not in memory: h = relu(z * scale + shift) (graphcnn.py:163-166) with z the pre-BatchNorm
     output of the layer's last Linear and (scale, shift) its folded BatchNorm.  Its BatchNorm + ReLU ran on the tile
@@ -526,14 +506,10 @@ def _hidden_ptr_arrays(hidden):
 _ptr_array = _hptr_array
 
 
-# GNM_NO_EVAL_FUSED=1: eval-mode forwards through the layer-by-layer kernels only (A/B timing, tests)
-EVAL_FUSED = os.environ.get("GNM_NO_EVAL_FUSED") is None
-
-
 def eval_fused_ok(spec, batch, X, P, mode=True):
     """can this eval-mode forward run as the one-launch encoder (csrc/evalfwd.hip; mode True) / as one launch per layer
     with a workgroup per 32-row block (csrc/evallayer.hip; mode "layers")?"""
-    if not EVAL_FUSED or spec.n_max or spec.sync_bn is not None or spec.keep_hidden:
+    if spec.n_max or spec.sync_bn is not None or spec.keep_hidden:
         return False
     layers = mode == "layers"
     if not getattr(batch, "has_bits", False) or batch.B < 1 or batch.n_max > (416 if layers else int(lib.gnm_eval_max_nodes())):
@@ -1100,17 +1076,17 @@ class GinInfoMaxFn(torch.autograd.Function):
                     G, part, nblk = pre_stats
                     pre_stats = None
                 else:
-                  G = torch.empty((N, Hk), **f32)
-                  part = torch.empty((B, 2, Hk), dtype=torch.float64, device=dev)
-                  nblk = B
-                  check(lib.gnm_bn_relu_bwd_stats(
-                      ptr(incoming), incoming.stride(0) if incoming is not None else 0,
-                      ptr(dp), dp.stride(0) if dp is not None else 0, int(spec.g_avg),
-                      ptr(dsc1) if use_disc else None, ptr(Ul), U.stride(0) if use_disc else 0,
-                      ptr(inv_perm) if use_disc else None, ptr(s2sum) if use_disc else None,
-                      sv.z.data_ptr(), sv.z.stride(0), sv.scale.data_ptr(), sv.shift.data_ptr(), sv.mean.data_ptr(),
-                      sv.rstd.data_ptr(), 1, G.data_ptr(), G.stride(0), batch.node_off.data_ptr(), B, Hk,
-                      part.data_ptr(), st), "gnm_bn_relu_bwd_stats")
+                    G = torch.empty((N, Hk), **f32)
+                    part = torch.empty((B, 2, Hk), dtype=torch.float64, device=dev)
+                    nblk = B
+                    check(lib.gnm_bn_relu_bwd_stats(
+                        ptr(incoming), incoming.stride(0) if incoming is not None else 0,
+                        ptr(dp), dp.stride(0) if dp is not None else 0, int(spec.g_avg),
+                        ptr(dsc1) if use_disc else None, ptr(Ul), U.stride(0) if use_disc else 0,
+                        ptr(inv_perm) if use_disc else None, ptr(s2sum) if use_disc else None,
+                        sv.z.data_ptr(), sv.z.stride(0), sv.scale.data_ptr(), sv.shift.data_ptr(), sv.mean.data_ptr(),
+                        sv.rstd.data_ptr(), 1, G.data_ptr(), G.stride(0), batch.node_off.data_ptr(), B, Hk,
+                        part.data_ptr(), st), "gnm_bn_relu_bwd_stats")
                 dgamma, dbeta = out_like(bn + ".weight", sv.scale), out_like(bn + ".bias", sv.scale)
                 cA, m1, m2 = (torch.empty(Hk, **f32) for _ in range(3))
                 check(lib.gnm_bn_bwd_finalize(part.data_ptr(), nblk, Hk, N, P[bn + ".weight"].data_ptr(),
@@ -1146,33 +1122,26 @@ class GinInfoMaxFn(torch.autograd.Function):
                 if lo is not None and need_dA:
                     lo_part = torch.empty((lib.gnm_linear_bwd_grid(N), 2, K), dtype=torch.float64, device=dev)
                 with _timed("linbwd_K%d_H%d" % (K, Hk), N=N, K=K, H=Hk) as tm:
-                    lo_args = (lo.z.data_ptr() if lo_part is not None else None,
-                               lo.z.stride(0) if lo_part is not None else 0,
-                               lo.scale.data_ptr() if lo_part is not None else None,
-                               lo.shift.data_ptr() if lo_part is not None else None,
-                               lo.mean.data_ptr() if lo_part is not None else None,
-                               lo.rstd.data_ptr() if lo_part is not None else None, ptr(lo_part), st)
+                    # every argument after Z (dW = NULL: the partials are reduced by ONE launch after the loop)
+                    args = (sv.mean.data_ptr(), sv.rstd.data_ptr(), cA.data_ptr(), m1.data_ptr(), m2.data_ptr(),
+                            sv.x_in.data_ptr(), sv.x_in.stride(0), ptr(sv.pro[0]) if sv.pro else None,
+                            ptr(sv.pro[1]) if sv.pro else None, 1 if sv.pro else 0, W.data_ptr(), W.stride(0), ptr(dA),
+                            dA.stride(0) if need_dA else 0, None, dW.stride(0), db.data_ptr(), ws.data_ptr(), N, K, Hk,
+                            lo.z.data_ptr() if lo_part is not None else None,
+                            lo.z.stride(0) if lo_part is not None else 0,
+                            lo.scale.data_ptr() if lo_part is not None else None,
+                            lo.shift.data_ptr() if lo_part is not None else None,
+                            lo.mean.data_ptr() if lo_part is not None else None,
+                            lo.rstd.data_ptr() if lo_part is not None else None, ptr(lo_part), st)
                     rc = -2
-                    if RZ_BACKWARD and Hk == 64 and ((K == 64 and need_dA) or (K <= 16 and not sv.pro and lo_part is None)):
+                    if Hk == 64 and lo_part is None and ((K == 64 and need_dA) or (K <= 16 and not sv.pro)):
                         # sv.z = Linear(sv.x_in) as gnm_linear_fwd left it: the pass recomputes it instead of reading it
-                        rc = lib.gnm_linear_bwd_fused_rz(
-                            G.data_ptr(), G.stride(0), P[wname + ".bias"].data_ptr(), sv.mean.data_ptr(),
-                            sv.rstd.data_ptr(), cA.data_ptr(), m1.data_ptr(), m2.data_ptr(), sv.x_in.data_ptr(),
-                            sv.x_in.stride(0), ptr(sv.pro[0]) if sv.pro else None, ptr(sv.pro[1]) if sv.pro else None,
-                            1 if sv.pro else 0, W.data_ptr(), W.stride(0), ptr(dA), dA.stride(0) if need_dA else 0,
-                            None if DEFER_WGRAD_REDUCE else dW.data_ptr(), dW.stride(0), db.data_ptr(), ws.data_ptr(),
-                            N, K, Hk, *lo_args)
+                        rc = lib.gnm_linear_bwd_fused_rz(G.data_ptr(), G.stride(0), P[wname + ".bias"].data_ptr(), *args)
                     if rc == -2:
-                      rc = lib.gnm_linear_bwd_fused(
-                        G.data_ptr(), G.stride(0), sv.z.data_ptr(), sv.z.stride(0), sv.mean.data_ptr(),
-                        sv.rstd.data_ptr(), cA.data_ptr(), m1.data_ptr(), m2.data_ptr(), sv.x_in.data_ptr(),
-                        sv.x_in.stride(0), ptr(sv.pro[0]) if sv.pro else None, ptr(sv.pro[1]) if sv.pro else None,
-                        1 if sv.pro else 0, W.data_ptr(), W.stride(0), ptr(dA), dA.stride(0) if need_dA else 0,
-                        None if DEFER_WGRAD_REDUCE else dW.data_ptr(), dW.stride(0), db.data_ptr(), ws.data_ptr(), N, K, Hk,
-                        *lo_args)
+                        rc = lib.gnm_linear_bwd_fused(G.data_ptr(), G.stride(0), sv.z.data_ptr(), sv.z.stride(0), *args)
                     if rc != 0:
                         tm.cancel()
-                if rc == 0 and DEFER_WGRAD_REDUCE:
+                if rc == 0:
                     wjobs.append((ws, dW, db, Hk, K))       # its dW / db partials: one reduction launch after the loop
                 if rc == 0 and lo_part is not None:
                     pre_stats = (dA, lo_part, lo_part.shape[0])
@@ -1191,7 +1160,7 @@ class GinInfoMaxFn(torch.autograd.Function):
                               "gnm_linear_wgrad")
                     if need_dA:
                         rc2 = -2
-                        if lo is not None and K == 128 and Hk == 128 and MASKED_DGRAD:
+                        if lo is not None and K == 128 and Hk == 128:
                             # dX = dZ W with the ReLU mask of the BatchNorm + ReLU below and that BatchNorm's backward
                             # sums taken in the epilogue (replaces its gnm_bn_relu_bwd_stats pass)
                             lo_part = torch.empty((int(lib.gnm_linear_grid(N)), 2, K), dtype=torch.float64, device=dev)

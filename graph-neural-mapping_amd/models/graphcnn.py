@@ -33,7 +33,7 @@ for _p in (_PKG, _HERE):
 from mlp import MLP  # noqa: E402
 from discriminator import Discriminator  # noqa: E402
 from gnm.arena import GraphArena  # noqa: E402
-from gnm.core import (DISC_UNIT, DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, edge_saliency_hip,  # noqa: E402
+from gnm.core import (DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, edge_saliency_hip,  # noqa: E402
                       eval_forward_fused, eval_fused_ok, launch_device, saliency_decline, saliency_hip, saliency_maps_hip)
 
 __all__ = ["GIN_InfoMaxReg", "GraphCNN", "MLP", "Discriminator"]
@@ -242,7 +242,7 @@ class GIN_InfoMaxReg(nn.Module):
                     c_logit, d_logit = _LazyEvalGradBatch.apply(self, batch, X, P0, perm, c_logit, d_logit, *tensors)
                 return c_logit, d_logit, g_f
         hold = None
-        if want_disc and self.training and DISC_UNIT and hand_over and torch.is_grad_enabled():
+        if want_disc and self.training and hand_over and torch.is_grad_enabled():
             # let the score kernel leave the backward's reductions for the reference's BCE loss (gnm/core.py DiscUnit);
             # only a loss that recognises the hand-over on d_logit (gnm.train.infomax_loss) makes use of it
             hold = want_disc = DiscUnit()

@@ -209,8 +209,8 @@ int gnm_linear_bwd_fused(const float* G, int ldg, const float* Z, int ldz, const
                          const float* s_rstd, double* s_partial, void* stream);
 /* The same pass for a Linear whose stored output the caller does not hand over: Z = f(X) W^T + bias (what
  * gnm_linear_fwd wrote, mlp.py:43,49) is recomputed in the kernel instead of being read -- three [N,64] streams instead
- * of four.  K = H = 64 and dA wanted; sZ either NULL or == X with (s_scale, s_shift) == (pro_scale, pro_shift) and
- * pro_relu (the two Linears of a 2-layer MLP).  Anything else: GNM_ERR_UNSUPPORTED, nothing launched -- call
+ * of four.  K = H = 64, dA wanted and sZ NULL (the first Linear of a 2-layer MLP), or K <= 16 without a prologue (the
+ * input layer's first Linear).  Anything else, every sZ != NULL included: GNM_ERR_UNSUPPORTED, nothing launched -- call
  * gnm_linear_bwd_fused with Z.  Workspace, partial rows and the dW = NULL deferral as for gnm_linear_bwd_fused. */
 int gnm_linear_bwd_fused_rz(const float* G, int ldg, const float* bias, const float* mean, const float* rstd,
                             const float* cA, const float* m1, const float* m2, const float* X, int ldx,
