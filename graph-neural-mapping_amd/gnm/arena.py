@@ -10,6 +10,7 @@ the device.
 """
 
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -81,9 +82,38 @@ class Batch:
     # batch (not looked up in the arena's tables at use): a captured hipGraph replays the lookup's kernels with the
     # table tensor of capture time, which is freed as soon as another graph is added to the arena.
 
+    def __init__(self, arena, cls):
+        self.arena = arena
+        for field, value in zip(BatchClass._fields, cls):
+            setattr(self, field, value)
+
     @property
     def equal_n(self):
         return self.n_max == self.n_min
+
+    @property
+    def batch_class(self):
+        return BatchClass(self.B, self.N, self.n_max, self.n_min, self.symmetric, self.dense, self.iso, self.has_bits,
+                          self.nnz_max)
+
+
+class BatchClass(NamedTuple):
+    """What a captured replay is specialised to: sizes, symmetry, aggregation route (dense), isolated nodes, bit rows,
+    and the edge count per graph its launch parameters were sized for.  A replay may run a batch only of a class it
+    admits(); any other batch runs eagerly (gnm/graphs.py)."""
+    B: int
+    N: int
+    n_max: int
+    n_min: int
+    symmetric: bool
+    dense: bool
+    iso: bool
+    has_bits: bool
+    nnz_max: int
+
+    def admits(self, other):
+        """every field equal, no more edges per graph than nnz_max"""
+        return other[:-1] == self[:-1] and other.nnz_max <= self.nnz_max
 
 
 class GraphArena:
@@ -317,32 +347,33 @@ class GraphArena:
         tb = self._tables()
         gh = gids.cpu().numpy() if torch.is_tensor(gids) else np.asarray(gids, dtype=np.int64)
         gd = self._upload(torch.as_tensor(gh, dtype=torch.int64))
-        ns = tb["n_host"][gh]
-        b = Batch()
-        b.arena = self
-        b.B = int(gh.shape[0])
+        b = Batch(self, self.class_of(gh))
         b.gids = gd
-        b.n_max, b.n_min = int(ns.max()), int(ns.min())
-        b.nnz_max = int(tb["nnz_host"][gh].max())
         node_off_host = np.zeros(b.B + 1, dtype=np.int64)
-        np.cumsum(ns, out=node_off_host[1:])
+        np.cumsum(tb["n_host"][gh], out=node_off_host[1:])
         b.node_off_host = node_off_host
-        b.N = int(node_off_host[-1])
         b.node_off = self._upload(torch.as_tensor(node_off_host.astype(np.int32)))
         b.rp_off = tb["rp"][gd]
         b.col_off = tb["col"][gd]
         b.feat_base = tb["feat"][gd]
-        b.symmetric = bool(tb["sym_host"][gh].all())
         if b.symmetric:
             b.t_rp_off, b.t_col_off = b.rp_off, b.col_off
         else:
             b.t_rp_off, b.t_col_off = tb["trp"][gd], tb["tcol"][gd]
-        b.dense = self.dense_ok(gh)
-        b.iso = bool(tb["iso_host"][gh].any())
-        b.has_bits = bool(gh.shape[0] > 0 and tb["bits_ok_host"][gh].all())
         b.bits_off = tb["bits"][gd]
         b.t_bits_off = b.bits_off if b.symmetric else tb["tbits"][gd]
         return b
+
+    def class_of(self, gh):
+        """BatchClass of the graphs with arena ids gh (host int64 array), from the host tables alone"""
+        tb = self._tables()
+        ns, nnz = tb["n_host"][gh], tb["nnz_host"][gh]
+        has_bits = bool(tb["bits_ok_host"][gh].all())
+        nf = ns.astype(np.float64)
+        # the matrix-core aggregation: every graph has a bit matrix and the batch is dense enough (DENSE_MIN_FILL)
+        dense = has_bits and float(nnz.sum()) >= DENSE_MIN_FILL * float((nf * nf).sum())
+        return BatchClass(int(gh.shape[0]), int(ns.sum()), int(ns.max()), int(ns.min()), bool(tb["sym_host"][gh].all()),
+                          dense, bool(tb["iso_host"][gh].any()), has_bits, int(nnz.max()))
 
     def _upload(self, host):
         """small host vector -> device without stalling the host: through pinned memory (torch's caching host allocator
@@ -351,14 +382,6 @@ class GraphArena:
         if self.device.type == "cuda":
             host = host.pin_memory()
         return host.to(self.device, non_blocking=True)
-
-    def dense_ok(self, gh):
-        """do the graphs gh (host int64 array of arena ids) form a batch for the matrix-core aggregation?"""
-        tb = self._tables()
-        if gh.shape[0] == 0 or not bool(tb["bits_ok_host"][gh].all()):
-            return False
-        ns = tb["n_host"][gh].astype(np.float64)
-        return float(tb["nnz_host"][gh].sum()) >= DENSE_MIN_FILL * float((ns * ns).sum())
 
     def _feature_rows(self, batch):
         if batch.equal_n:
@@ -483,8 +506,8 @@ class GraphArena:
 
 
 class BatchClassMismatch(ValueError):
-    """StaticBatch.load: the batch is of another class (size, symmetry, density route, isolated nodes) than the one the
-    buffers were captured for -- the one condition a replayed step answers by running eagerly (gnm/graphs.py)."""
+    """StaticBatch.load: the batch is of another BatchClass than the one the buffers were captured for -- the one
+    condition a replayed step answers by running eagerly (gnm/graphs.py)."""
 
 
 class StaticBatch:
@@ -495,9 +518,7 @@ class StaticBatch:
     serialised in front of every replay, cost ~40 us of a 2.9 ms step."""
 
     def __init__(self, template, extra_int64=0):
-        b = Batch()
-        for f in ("B", "N", "n_max", "n_min", "nnz_max", "arena", "symmetric", "dense", "iso", "has_bits"):
-            setattr(b, f, getattr(template, f))
+        b = Batch(template.arena, template.batch_class)
         b.node_off_host = np.array(template.node_off_host, copy=True)
         b.node_off = template.node_off.clone()
         self._names = ["rp_off", "col_off", "gids", "feat_base", "bits_off"]
@@ -518,8 +539,7 @@ class StaticBatch:
 
     def load(self, other, extra=None):
         b = self.batch
-        if (other.B, other.N, other.n_max, other.n_min, other.symmetric, other.dense, other.iso) != \
-                (b.B, b.N, b.n_max, b.n_min, b.symmetric, b.dense, b.iso) or other.nnz_max > b.nnz_max:
+        if not b.batch_class.admits(other.batch_class):
             raise BatchClassMismatch("StaticBatch.load: batch shape differs from the captured one")
         if (self.extra is None) != (extra is None):
             raise ValueError("StaticBatch.load: `extra` must be given exactly when the buffer was built with extra_int64")
@@ -544,12 +564,19 @@ class PackedStaticBatch:
     (gnm/graphs.py CapturedEval): assembling a Batch the general way costs ~15 tiny device ops (~150 us of host
     time), which is most of a B = 1 forward."""
 
-    def __init__(self, arena, B, n, symmetric, nnz_max, dense=False, iso=False, has_bits=False, extra_words=0,
-                 two_stage=False):
-        """extra_words: int64 words appended to the buffer for the caller's own per-batch values (a training step's
-        labels and Infomax permutation: gnm/graphs.py), uploaded by the same copy: load_gids(gh, extra)."""
+    def __init__(self, arena, cls, extra_words=0, two_stage=False):
+        """cls: the BatchClass (GraphArena.class_of) of the equal-size graphs the buffer is built for.  Its nnz_max
+        is rounded up to a power of two (at least 4096): the launch parameters are sized for that, so one capture
+        serves every selection up to it.  extra_words: int64 words appended to the buffer for the caller's own
+        per-batch values (a training step's labels and Infomax permutation: gnm/graphs.py), uploaded by the same copy:
+        load_gids(gh, extra)."""
+        if cls.n_max != cls.n_min:
+            raise ValueError("PackedStaticBatch needs equal-size graphs (as the discriminator does, "
+                             "discriminator.py:24)")
         dev = arena.device
-        self.arena, self.B, self.n = arena, int(B), int(n)
+        B, n = cls.B, cls.n_max
+        self.arena, self.B = arena, B
+        self.batch_class = cls._replace(nnz_max=max(4096, 1 << (cls.nnz_max - 1).bit_length()))
         self._base_words = 8 * B + (B + 2) // 2           # 8 int64 vectors + node_off as int32 pairs
         words = self._base_words + int(extra_words)
         node_off = np.arange(B + 1, dtype=np.int64) * n
@@ -577,16 +604,11 @@ class PackedStaticBatch:
         self._stage_dev = [torch.zeros(words, dtype=torch.int64, device=dev) for _ in self._ring] if self._two_stage else None
         self._done = [None] * len(self._ring)
         dv = self._dev
-        b = Batch()
-        b.arena, b.B, b.N, b.n_max, b.n_min, b.nnz_max = arena, int(B), int(B * n), int(n), int(n), int(nnz_max)
-        b.symmetric = bool(symmetric)
-        b.dense = bool(dense)
-        b.iso = bool(iso)
-        b.has_bits = bool(has_bits)
+        b = Batch(arena, self.batch_class)
         b.bits_off = dv[6 * B:7 * B]
-        b.t_bits_off = b.bits_off if symmetric else dv[7 * B:8 * B]
+        b.t_bits_off = b.bits_off if b.symmetric else dv[7 * B:8 * B]
         b.rp_off, b.col_off = dv[0:B], dv[B:2 * B]
-        b.t_rp_off, b.t_col_off = (b.rp_off, b.col_off) if symmetric else (dv[2 * B:3 * B], dv[3 * B:4 * B])
+        b.t_rp_off, b.t_col_off = (b.rp_off, b.col_off) if b.symmetric else (dv[2 * B:3 * B], dv[3 * B:4 * B])
         b.gids = dv[4 * B:5 * B]
         b.feat_base = dv[5 * B:6 * B]
         b.node_off = dv[8 * B:self._base_words].view(torch.int32)[:B + 1]
@@ -596,17 +618,16 @@ class PackedStaticBatch:
         self._dev.copy_(self._ring[0])
 
     def fits(self, gh):
-        """can the graphs with arena ids gh (host int64 array) be loaded? (same count, node count, symmetry class;
-        no more edges than the launch parameters were sized for)"""
-        tb = self.arena._tables()
-        b = self.batch
-        return (gh.shape[0] == b.B and bool((tb["n_host"][gh] == self.n).all())
-                and bool(tb["sym_host"][gh].all()) == b.symmetric and int(tb["nnz_host"][gh].max()) <= b.nnz_max
-                and self.arena.dense_ok(gh) == b.dense and bool(tb["iso_host"][gh].any()) == b.iso
-                and bool(tb["bits_ok_host"][gh].all()) == b.has_bits)
+        """can the graphs with arena ids gh (host int64 array) be loaded?"""
+        return self.batch_class.admits(self.arena.class_of(gh))
 
     def load_gids(self, gh, extra=None):
-        """extra: host int64 array filling the extra words (all of them), or None"""
+        """extra: host int64 array filling the extra words (all of them), given exactly when the buffer has some"""
+        if (extra is None) != (self.extra is None):
+            raise ValueError("PackedStaticBatch.load_gids: `extra` must be given exactly when the buffer was built "
+                             "with extra_words")
+        if extra is not None and np.shape(extra) != tuple(self.extra.shape):
+            raise ValueError("PackedStaticBatch.load_gids: extra must be %d values" % self.extra.shape[0])
         tb = self.arena._tables()
         i = self._next
         self._next = (i + 1) % len(self._ring)

@@ -16,7 +16,7 @@ import gc
 
 import torch
 
-from .arena import BatchClassMismatch, PackedStaticBatch, StaticBatch
+from .arena import PackedStaticBatch, StaticBatch
 from .core import perm_to_device
 
 
@@ -32,6 +32,7 @@ def _capture(graph, pool=None):
     gc.collect()
     gc.disable()
     try:
+        # thread_local: other threads of the process (e.g. RCCL's watchdog) keep issuing HIP calls
         kw = {"capture_error_mode": "thread_local"}
         if pool is not None:
             kw["pool"] = pool
@@ -40,6 +41,32 @@ def _capture(graph, pool=None):
     finally:
         if was:
             gc.enable()
+
+
+def _warm_up_and_capture(fn, warmup, dev=None, warm=None):
+    """`warmup` calls of warm() (default: fn) on a side stream -- allocator, hipFuncSetAttribute, lazy inits, as
+    torch's CUDA-graph recipe prescribes -- then fn() captured: (the graph, what the captured fn returned)"""
+    s = torch.cuda.Stream(device=dev)
+    s.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(s):
+        for _ in range(warmup):
+            (warm or fn)()
+    torch.cuda.current_stream(dev).wait_stream(s)
+    torch.cuda.synchronize(dev)
+    graph = torch.cuda.CUDAGraph()
+    with _capture(graph):
+        out = fn()
+    return graph, out
+
+
+def _arena_buffers(a):
+    """the buffers captured kernels read the graph pool from: adding graphs may re-allocate them"""
+    return [a.rowptr.buf, a.col.buf, a.feat.buf, a.bits.buf] + \
+        [v["buf"] for _, v in sorted(a._agg0.items()) if v["buf"] is not None]
+
+
+def _arena_ptrs(a):
+    return tuple(t.data_ptr() for t in _arena_buffers(a))
 
 
 class CapturedTrainStep:
@@ -55,25 +82,24 @@ class CapturedTrainStep:
         captured on a PackedStaticBatch whose ONE buffer also carries the labels and the Infomax permutation, and
         run_gids(ids, labels, perm) feeds a replay with O(B) host index arithmetic and ONE pinned upload -- instead of
         a Batch assembled by six device gathers, two uploads and a concatenation (~75 us of launches per step)."""
+        B = template_batch.B
+        if gids_host is not None:
+            gh = np.asarray(gids_host, dtype=np.int64)
+            cls = template_batch.arena.class_of(gh)
+            if cls != template_batch.batch_class:
+                raise ValueError("CapturedTrainStep: gids_host are of class %s, template_batch of class %s"
+                                 % (cls, template_batch.batch_class))
         self.model = model
-        self.eager_fallbacks = 0           # replays that ran eagerly instead (a batch of another class: run())
+        self.eager_fallbacks = 0           # replays that ran eagerly instead (a batch of another class)
         self._post = post_backward
         self._agg0_cache = agg0_cache      # False: aggregate the input features inside the step (bench.py)
         keep = [t for t in model.state_dict().values()] + list(preserve)
         snapshot = [t.clone() for t in keep]
         dev = template_batch.node_off.device
-        B = template_batch.B
         self.packed = None
-        if gids_host is not None and template_batch.equal_n and B > 0:
-            gh = np.asarray(gids_host, dtype=np.int64)
-            arena = template_batch.arena
-            tb = arena._tables()
-            nnz = int(tb["nnz_host"][gh].max())
-            nnz_cap = max(4096, 1 << (nnz - 1).bit_length()) if nnz > 0 else 4096
+        if gids_host is not None and template_batch.equal_n:
             self._perm_words = (B + 1) // 2
-            self.packed = PackedStaticBatch(arena, B, template_batch.n_max, template_batch.symmetric, nnz_cap,
-                                            dense=template_batch.dense, iso=template_batch.iso,
-                                            has_bits=template_batch.has_bits, extra_words=B + self._perm_words,
+            self.packed = PackedStaticBatch(template_batch.arena, cls, extra_words=B + self._perm_words,
                                             two_stage=B >= 64)
             self.packed.load_gids(gh, self._pack_extra(np.zeros(B, dtype=np.int64), np.arange(B)))
             self.static = self.packed
@@ -83,33 +109,14 @@ class CapturedTrainStep:
             self.static = StaticBatch(template_batch, extra_int64=B)      # the labels ride in the same buffer
             self.labels = self.static.extra
             self.perm = torch.arange(B, dtype=torch.int32, device=dev)
-        self.loss = None
         self._zero = zero_grad or (lambda: model.zero_grad(set_to_none=False))
         self._loss_fn = loss_fn
-        # warm-up on a side stream (allocator, hipFuncSetAttribute, lazy inits), as torch's
-        # CUDA-graph recipe prescribes, then capture
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._step()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        # thread_local: other threads of the process (e.g. RCCL's watchdog) keep issuing HIP calls
-        with _capture(self.graph):
-            self.loss = self._step()
+        self.graph, self.loss = _warm_up_and_capture(self._step, warmup)
         with torch.no_grad():
             for t, s0 in zip(keep, snapshot):
                 t.copy_(s0)
         torch.cuda.synchronize()
-        self._arena_ptrs = self._arena_buffers()
-
-    def _arena_buffers(self):
-        """addresses the captured kernels read the graph pool from: adding graphs may re-allocate them"""
-        a = self.static.batch.arena
-        return (a.rowptr.buf.data_ptr(), a.col.buf.data_ptr(), a.feat.buf.data_ptr(), a.bits.buf.data_ptr(),
-                tuple(sorted((k, v["buf"].data_ptr()) for k, v in a._agg0.items() if v["buf"] is not None)))
+        self._arena_ptrs = _arena_ptrs(self.static.batch.arena)
 
     def _step(self):
         self._zero()
@@ -137,7 +144,7 @@ class CapturedTrainStep:
         if self._agg0_cache:        # graphs added since the capture: their layer-0 aggregate must exist before a replay
             sp = self.model._spec
             self.static.batch.arena.refresh_agg0(sp.n_avg, not sp.learn_eps)
-        if self._arena_buffers() != self._arena_ptrs:
+        if _arena_ptrs(self.static.batch.arena) != self._arena_ptrs:
             raise RuntimeError("the graph arena was re-allocated after this step was captured (graphs were added): "
                                "add every graph before building CapturedTrainStep / FusedTrainStep, or build a new one")
 
@@ -153,11 +160,9 @@ class CapturedTrainStep:
         perm = check_permutation(np.random.permutation(B) if perm is None else perm, B)
         self._check_arena()
         if not self.packed.fits(gh):
-            self.eager_fallbacks += 1
             arena = self.packed.arena
-            bt = arena.batch_from_gids(gh)
             lab = torch.as_tensor(np.asarray(labels_host, dtype=np.int64)).to(arena.device)
-            return self._eager(bt, lab, perm)
+            return self._fallback(arena.batch_from_gids(gh), lab, perm)
         self.packed.load_gids(gh, self._pack_extra(np.asarray(labels_host, dtype=np.int64), perm))
         self.graph.replay()
         return self.loss
@@ -167,45 +172,32 @@ class CapturedTrainStep:
         np.random.permutation(B) of graphcnn.py:199 (drawn here if None)."""
         if perm is None:
             perm = np.random.permutation(batch.B)
+        self._check_arena()
+        if not self.static.batch.batch_class.admits(batch.batch_class):
+            return self._fallback(batch, labels, perm)
         if self.packed is not None:
             # (captured on the packed buffer: a ready-made Batch is copied in vector by vector -- the general route)
-            self._check_arena()
             b = self.packed.batch
-            if (batch.B, batch.N, batch.n_max, batch.n_min, batch.symmetric, batch.dense, batch.iso) != \
-                    (b.B, b.N, b.n_max, b.n_min, b.symmetric, b.dense, b.iso) or batch.nnz_max > b.nnz_max:
-                self.eager_fallbacks += 1
-                return self._eager(batch, labels, perm)
             for name in ("rp_off", "col_off", "gids", "feat_base", "bits_off") + \
                     (() if b.symmetric else ("t_rp_off", "t_col_off", "t_bits_off")):
                 getattr(b, name).copy_(getattr(batch, name), non_blocking=True)
             self.labels.copy_(labels.to(torch.int64), non_blocking=True)
-            perm_to_device(perm, self.perm.shape[0], self.perm.device, out=self.perm)
-            self.graph.replay()
-            return self.loss
-        if self._agg0_cache:        # graphs added since the capture: their layer-0 aggregate must exist before a replay
-            sp = self.model._spec
-            batch.arena.refresh_agg0(sp.n_avg, not sp.learn_eps)
-        if self._arena_buffers() != self._arena_ptrs:
-            raise RuntimeError("the graph arena was re-allocated after this step was captured (graphs were added): "
-                               "add every graph before building CapturedTrainStep / FusedTrainStep, or build a new one")
-        try:
+        else:
             self.static.load(batch, extra=labels.to(torch.int64))
-        except BatchClassMismatch:
-            # a batch of another class than the captured one (a pool that straddles the density threshold of the
-            # matrix-core aggregation, a graph with an isolated node, another size): the same step, launched eagerly.
-            # Counted (bench.py prints it) and announced once: a caller whose every batch lands here is not replaying.
-            # Any other ValueError of load() is API misuse and propagates.
-            self.eager_fallbacks += 1
-            if self.eager_fallbacks == 1:
-                import warnings
-                warnings.warn("CapturedTrainStep: a batch of another class than the captured one runs eagerly "
-                              "(counted in .eager_fallbacks)", RuntimeWarning, stacklevel=2)
-            return self._eager(batch, labels, perm)
         perm_to_device(perm, self.perm.shape[0], self.perm.device, out=self.perm)
         self.graph.replay()
         return self.loss
 
-    def _eager(self, batch, labels, perm):
+    def _fallback(self, batch, labels, perm):
+        """A batch of another class than the captured one (a pool that straddles the density threshold of the
+        matrix-core aggregation, a graph with an isolated node or without bit rows, another size): the same step,
+        launched eagerly.  Counted (bench.py prints it) and announced once: a caller whose every batch lands here is
+        not replaying."""
+        self.eager_fallbacks += 1
+        if self.eager_fallbacks == 1:
+            import warnings
+            warnings.warn("CapturedTrainStep: a batch of another class than the captured one runs eagerly "
+                          "(counted in .eager_fallbacks)", RuntimeWarning, stacklevel=3)
         self._zero()
         X = None if self._agg0_cache else batch.arena.features(batch)
         c_logit, d_logit = self.model.forward_batch(batch, X=X, perm=perm)
@@ -227,41 +219,18 @@ class CapturedEval:
 
     def __init__(self, model, gids_host, warmup=2):
         arena = model.arena()
-        tb = arena._tables()
         gh = np.asarray(gids_host, dtype=np.int64)
-        n = int(tb["n_host"][gh[0]])
-        if not (tb["n_host"][gh] == n).all():
-            raise ValueError("CapturedEval needs equal-size graphs (as the discriminator does, discriminator.py:24)")
-        nnz = int(tb["nnz_host"][gh].max())
-        nnz_cap = max(4096, 1 << (nnz - 1).bit_length()) if nnz > 0 else 4096     # launch parameters sized for this
         self.model = model
         self._fused = getattr(model, "eval_fused", False)
-        self.static = PackedStaticBatch(arena, gh.shape[0], n, bool(tb["sym_host"][gh].all()), nnz_cap,
-                                        dense=arena.dense_ok(gh), iso=bool(tb["iso_host"][gh].any()),
-                                        has_bits=bool(tb["bits_ok_host"][gh].all()))
+        self.static = PackedStaticBatch(arena, arena.class_of(gh))
         self.static.load_gids(gh)
         dev = arena.device
-        B = gh.shape[0]
-        self.perm = torch.arange(B, dtype=torch.int32, device=dev)      # (a valid permutation from the start)
+        self.perm = torch.arange(gh.shape[0], dtype=torch.int32, device=dev)      # (a valid permutation from the start)
         self._params = [p for p in model.parameters()] + [b for b in model.buffers()]
         self._param_ptrs = tuple(t.data_ptr() for t in self._params)
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._forward()
-        torch.cuda.current_stream(dev).wait_stream(s)
+        self.graph, (self.c_logit, self.d_logit, self.g_f) = _warm_up_and_capture(self._forward, warmup, dev)
         torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with _capture(self.graph):
-            self.c_logit, self.d_logit, self.g_f = self._forward()
-        torch.cuda.synchronize(dev)
-        self._arena_ptrs = self._arena_buffers()
-
-    def _arena_buffers(self):
-        a = self.static.arena
-        return (a.rowptr.buf.data_ptr(), a.col.buf.data_ptr(), a.feat.buf.data_ptr(), a.bits.buf.data_ptr(),
-                tuple(sorted((k, v["buf"].data_ptr()) for k, v in a._agg0.items() if v["buf"] is not None)))
+        self._arena_ptrs = _arena_ptrs(arena)
 
     def _forward(self):
         m = self.model
@@ -278,7 +247,7 @@ class CapturedEval:
     def valid_for(self, gh):
         """still replayable for these graphs?  (shape fits, and neither the arena nor the parameters moved, nor the
         choice between the layer-by-layer kernels and the one-launch encoder)"""
-        return (self.static.fits(gh) and self._arena_buffers() == self._arena_ptrs
+        return (self.static.fits(gh) and _arena_ptrs(self.static.arena) == self._arena_ptrs
                 and tuple(t.data_ptr() for t in self._params) == self._param_ptrs
                 and getattr(self.model, "eval_fused", False) == self._fused)
 
@@ -312,23 +281,14 @@ class CapturedTrain:
 
     def __init__(self, model, gids_host, warmup=2):
         arena = model.arena()
-        tb = arena._tables()
         gh = np.asarray(gids_host, dtype=np.int64)
-        n = int(tb["n_host"][gh[0]])
-        if not (tb["n_host"][gh] == n).all():
-            raise ValueError("CapturedTrain needs equal-size graphs (as the discriminator does, discriminator.py:24)")
-        nnz = int(tb["nnz_host"][gh].max())
-        nnz_cap = max(4096, 1 << (nnz - 1).bit_length()) if nnz > 0 else 4096
         self.model = model
-        self.static = PackedStaticBatch(arena, gh.shape[0], n, bool(tb["sym_host"][gh].all()), nnz_cap,
-                                        dense=arena.dense_ok(gh), iso=bool(tb["iso_host"][gh].any()),
-                                        has_bits=bool(tb["bits_ok_host"][gh].all()))
+        self.static = PackedStaticBatch(arena, arena.class_of(gh))
         self.static.load_gids(gh)
         dev = arena.device
-        B = gh.shape[0]
         # a PERMUTATION from the start: the warm-up passes run the backward, whose shuffled-branch term indexes by the
         # inverse permutation (zeros here left it mostly unwritten -> wild reads: a GPU memory fault in the first version)
-        self.perm = torch.arange(B, dtype=torch.int32, device=dev)
+        self.perm = torch.arange(gh.shape[0], dtype=torch.int32, device=dev)
         self._params = [p for p in model.parameters()]
         self._req = [p for p in self._params if p.requires_grad]
         self._tracked = self._params + [b for b in model.buffers()]
@@ -348,26 +308,21 @@ class CapturedTrain:
             own_sink[nm] = self._flat[off:off + p.numel()].view_as(p)
             off += p.numel()
         sink = model._spec.grad_sink
-        try:
-            s = torch.cuda.Stream(device=dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                # which parameters get a gradient at all (eps does not when learn_eps is False): one plain pass
-                model._spec.grad_sink = None
-                c, d, _ = self._forward()
-                plain = torch.autograd.grad((c, d), self._req, (torch.zeros_like(c), torch.zeros_like(d)), allow_unused=True)
-                used = iter([g is not None for g in plain])
+
+        def warm():
+            c, d, _ = self._forward()
+            grads = torch.autograd.grad((c, d), self._req, (torch.zeros_like(c), torch.zeros_like(d)),
+                                        allow_unused=True)
+            if model._spec.grad_sink is None:
+                # the first pass, in plain autograd: which parameters get a gradient at all (eps does not when
+                # learn_eps is False).  The others write into the sink.
+                used = iter([g is not None for g in grads])
                 self._has_grad = [bool(next(used)) if p.requires_grad else False for p in self._params]
-                del plain
                 model._spec.grad_sink = own_sink
-                for _ in range(warmup):
-                    c, d, _ = self._forward()
-                    torch.autograd.grad((c, d), self._req, (torch.zeros_like(c), torch.zeros_like(d)), allow_unused=True)
-            torch.cuda.current_stream(dev).wait_stream(s)
-            torch.cuda.synchronize(dev)
-            self.fwd_graph = torch.cuda.CUDAGraph()
-            with _capture(self.fwd_graph):
-                self.c_logit, self.d_logit, _ = self._forward()
+        try:
+            model._spec.grad_sink = None
+            self.fwd_graph, (self.c_logit, self.d_logit, _) = _warm_up_and_capture(self._forward, 1 + warmup, dev,
+                                                                                   warm=warm)
             self.dC = torch.zeros_like(self.c_logit)
             self.dD = torch.zeros_like(self.d_logit)
             self.bwd_graph = torch.cuda.CUDAGraph()
@@ -382,18 +337,14 @@ class CapturedTrain:
                     t.copy_(s0)
         self.grads = [own_sink[nm] if has else None for nm, has in zip(names, self._has_grad)]
         torch.cuda.synchronize(dev)
-        self._arena_ptrs = self._arena_buffers()
+        self._arena_ptrs = _arena_ptrs(arena)
         # The captured kernels read the graph pool at the addresses of capture time.  A forward re-checks them
         # (valid_for), but the arena may GROW between a replayed forward and its backward (another batch's graphs added
         # in between: the arena then moves to bigger buffers and drops the old ones) -- so this capture keeps the
         # buffers it was recorded on alive: they stay complete for the graphs it can be replayed on.
-        a = arena
-        self._arena_refs = (a.rowptr.buf, a.col.buf, a.feat.buf, a.bits.buf,
-                            tuple(v["buf"] for v in a._agg0.values() if v["buf"] is not None))
+        self._arena_refs = _arena_buffers(arena)
         self._grad_ptrs = frozenset(g.data_ptr() for g in self.grads if g is not None)
         self._flat.zero_()
-
-    _arena_buffers = CapturedEval._arena_buffers
 
     def _forward(self):
         m = self.model
@@ -405,7 +356,7 @@ class CapturedTrain:
 
     def valid_for(self, gh):
         m = self.model
-        return (self.static.fits(gh) and self._arena_buffers() == self._arena_ptrs
+        return (self.static.fits(gh) and _arena_ptrs(self.static.arena) == self._arena_ptrs
                 and tuple(t.data_ptr() for t in self._tracked) == self._ptrs
                 and tuple(p.requires_grad for p in self._params) == self._req_mask
                 and m._spec.grad_sink is None and m._spec.sync_bn is None)

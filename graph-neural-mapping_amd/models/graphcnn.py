@@ -505,7 +505,46 @@ class GIN_InfoMaxReg(nn.Module):
                 out[:, offs[j]:offs[j + 1]][..., :nj] = r[:, so[k]:so[k + 1]][..., :nj]
         return out
 
-    # ------------------------------------------------------------------ evaluation replay
+    # ------------------------------------------------------------------ replays
+    def _replay_ids(self, batch_graph):
+        """(arena ids, (B, n)) of a batch of equal-size graphs, with the layer-0 cache brought up to date (a replay
+        only gathers from it); None for graphs of different sizes or an arena off the GPU"""
+        arena = self.arena()
+        if arena.device.type != "cuda":
+            return None
+        gh = np.asarray(arena.add_many(batch_graph), dtype=np.int64)
+        n_host = arena._tables()["n_host"]
+        n = int(n_host[gh[0]])
+        if gh.shape[0] > 1 and not (n_host[gh] == n).all():
+            return None
+        arena.refresh_agg0(self._spec.n_avg, not self._spec.learn_eps)
+        return gh, (int(gh.shape[0]), n)
+
+    def _captured(self, cache, key, kind, gh, entries, mode):
+        """The capture for `key` in `cache` ({(B, n): capture}, at most `entries` of them): the cached one when it is
+        valid_for(gh), else a new kind(self, gh), which takes the place of a stale one for the same key and otherwise
+        evicts the oldest entry.  None when the capture fails (e.g. a user hook that synchronises inside the forward):
+        no entry is left, `mode`-mode replay is switched off with a warning, the numpy RNG is put back, and the caller
+        runs eagerly."""
+        c = cache.get(key)
+        if c is not None and c.valid_for(gh):
+            return c
+        cache.pop(key, None)
+        if len(cache) >= entries:
+            cache.pop(next(iter(cache)))
+        rng_state = np.random.get_state()
+        try:
+            with torch.cuda.device(self.arena().device):
+                c = cache[key] = kind(self, gh)
+        except Exception as e:
+            import warnings
+            warnings.warn("%s-mode hipGraph capture failed (%s: %s); running eagerly from now on"
+                          % (mode, type(e).__name__, e))
+            setattr(self, mode + "_replay", False)
+            np.random.set_state(rng_state)
+            return None
+        return c
+
     EVAL_REPLAY_MAX_B = 64          # larger eval batches are GPU-bound anyway (and hold more captured activations)
     EVAL_REPLAY_ENTRIES = 6
 
@@ -513,34 +552,15 @@ class GIN_InfoMaxReg(nn.Module):
         """forward() in eval mode for a small batch of equal-size graphs: the eager path's kernels replayed from
         a captured hipGraph (bitwise the same results, ~0.1 ms of host time instead of ~1.4 ms).  None when the batch
         does not qualify -- the caller then takes the eager path."""
-        arena = self.arena()
-        if arena.device.type != "cuda":
+        ids = self._replay_ids(batch_graph)
+        if ids is None:
             return None
-        gh = np.asarray(arena.add_many(batch_graph), dtype=np.int64)
-        tb = arena._tables()
-        n = int(tb["n_host"][gh[0]])
-        B = int(gh.shape[0])
-        if B > 1 and not (tb["n_host"][gh] == n).all():
-            return None
+        gh, key = ids
         from gnm.graphs import CapturedEval
-        arena.refresh_agg0(self._spec.n_avg, not self._spec.learn_eps)       # the replay only gathers from this cache
-        key = (B, n)
-        ce = self._eval_cache.get(key)
-        rng_state = np.random.get_state() if (ce is None or not ce.valid_for(gh)) else None
-        perm = np.random.permutation(B)                                       # graphcnn.py:199, consumed as always
-        if rng_state is not None:
-            if len(self._eval_cache) >= self.EVAL_REPLAY_ENTRIES:
-                self._eval_cache.pop(next(iter(self._eval_cache)))
-            try:
-                with torch.cuda.device(arena.device):
-                    ce = self._eval_cache[key] = CapturedEval(self, gh)
-            except Exception as e:          # e.g. a user hook that synchronises inside the forward: stay eager
-                import warnings
-                warnings.warn("eval-mode hipGraph capture failed (%s: %s); evaluating eagerly from now on"
-                              % (type(e).__name__, e))
-                self.eval_replay = False
-                np.random.set_state(rng_state)
-                return None
+        ce = self._captured(self._eval_cache, key, CapturedEval, gh, self.EVAL_REPLAY_ENTRIES, "eval")
+        if ce is None:
+            return None
+        perm = np.random.permutation(key[0])                                  # graphcnn.py:199, consumed as always
         c_logit, d_logit, g_f = ce.run(gh, perm)
         if latent:
             return g_f.cpu().numpy()                                          # graphcnn.py:248-249
@@ -561,38 +581,21 @@ class GIN_InfoMaxReg(nn.Module):
         hipGraphs (same kernels, same order as the eager path).  None when the batch does not qualify -- other shapes,
         a forward still outstanding on the capture, a gradient sink / cross-rank BatchNorm installed, parameters that
         moved -- and the caller then takes the eager path."""
-        arena = self.arena()
         sp = self._spec
-        if arena.device.type != "cuda" or sp.grad_sink is not None or sp.sync_bn is not None or sp.keep_hidden:
+        if sp.grad_sink is not None or sp.sync_bn is not None or sp.keep_hidden:
             return None
-        gh = np.asarray(arena.add_many(batch_graph), dtype=np.int64)
-        tb = arena._tables()
-        n = int(tb["n_host"][gh[0]])
-        B = int(gh.shape[0])
-        if not (tb["n_host"][gh] == n).all():
+        ids = self._replay_ids(batch_graph)
+        if ids is None:
             return None
-        from gnm.graphs import CapturedTrain
-        arena.refresh_agg0(sp.n_avg, not sp.learn_eps)
-        key = (B, n)
+        gh, key = ids
         ct = self._train_cache.get(key)
         if ct is not None and ct.busy():
             return None                                   # its activations belong to a forward not yet backpropagated
-        if ct is None or not ct.valid_for(gh):
-            if len(self._train_cache) >= self.TRAIN_REPLAY_ENTRIES and key not in self._train_cache:
-                self._train_cache.pop(next(iter(self._train_cache)))
-            rng_state = np.random.get_state()
-            try:
-                with torch.cuda.device(arena.device):
-                    ct = self._train_cache[key] = CapturedTrain(self, gh)
-            except Exception as e:          # e.g. a hook that synchronises inside the forward: stay eager
-                import warnings
-                warnings.warn("train-mode hipGraph capture failed (%s: %s); training eagerly from now on"
-                              % (type(e).__name__, e))
-                self.train_replay = False
-                self._train_cache.pop(key, None)
-                np.random.set_state(rng_state)
-                return None
-        perm = np.random.permutation(B)                                       # graphcnn.py:199, consumed as always
+        from gnm.graphs import CapturedTrain
+        ct = self._captured(self._train_cache, key, CapturedTrain, gh, self.TRAIN_REPLAY_ENTRIES, "train")
+        if ct is None:
+            return None
+        perm = np.random.permutation(key[0])                                  # graphcnn.py:199, consumed as always
         names, tensors, _ = self._param_lists()
         c_logit, d_logit = _TrainReplayFn.apply(ct, gh, perm, *tensors)
         return c_logit, d_logit

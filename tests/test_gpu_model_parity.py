@@ -475,6 +475,59 @@ def test_hipgraph_replay_matches_eager_bitwise():
         cap3.run_gids(gids3[sels[0]], labels_host[sels[0]], np.array([0, 0, 1, 2]))
 
 
+def test_captured_step_runs_a_batch_without_bit_rows_eagerly():
+    """A batch that differs from the captured one only in has_bits -- one multigraph among its graphs (a repeated edge:
+    no bit rows), in a batch sparse enough to stay on the gather route either way -- is not replayed: run() on the
+    packed capture runs the step eagerly, counts it and warns once, with the eager step's bits."""
+    import warnings
+    from gnm import synth
+    from gnm.graphs import CapturedTrainStep
+    from models.graphcnn import GIN_InfoMaxReg
+    dev = torch.device(DEV)
+    n = 120
+    pool = synth.make_pool("knn", 6, n=n, k=2, f0=7)                 # ~2.5 % of n^2: below DENSE_MIN_FILL
+    e = pool[5].edge_mat
+    pool[5].edge_mat = torch.cat([e, e[:, [0, e.shape[1] // 2]]], 1)   # edge 0 once more, both ways
+    d_labels = torch.cat([torch.ones(4 * n, 1), torch.zeros(4 * n, 1)], 0).to(dev)
+
+    def loss_fn(c, d, lab):
+        return torch.nn.functional.cross_entropy(c, lab) + \
+            0.05 * torch.nn.functional.binary_cross_entropy_with_logits(d, d_labels)
+
+    def fresh():
+        torch.manual_seed(0)
+        m = GIN_InfoMaxReg(3, 2, 7, 32, 2, 0.0, True, "sum", "sum", dev).to(dev).train()
+        ar = m.arena()
+        return m, ar, np.array(ar.add_many(pool), dtype=np.int64)
+
+    sel, perm = np.array([4, 5, 1, 2]), np.array([2, 0, 3, 1])
+    labels = torch.tensor([pool[i].label for i in sel], device=dev)
+    m, ar, gids = fresh()
+    template, bt = ar.batch_from_gids(gids[:4]), ar.batch_from_gids(gids[sel])
+    assert template.has_bits and not bt.has_bits and not template.dense and not bt.dense
+    assert template.batch_class._replace(has_bits=False, nnz_max=0) == bt.batch_class._replace(nnz_max=0)
+    loss = loss_fn(*m.forward_batch(bt, perm=perm), labels)
+    loss.backward()
+    want = [loss.detach().clone()] + [p.grad.clone() for p in m.parameters()]
+
+    m2, ar2, gids2 = fresh()
+    for p in m2.parameters():
+        p.grad = torch.zeros_like(p)
+    cap = CapturedTrainStep(m2, ar2.batch_from_gids(gids2[:4]), loss_fn, gids_host=gids2[:4])
+    assert cap.packed is not None and cap.packed.batch_class.nnz_max >= bt.nnz_max
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        loss = cap.run(ar2.batch_from_gids(gids2[sel]), labels, perm)
+    torch.cuda.synchronize()
+    assert cap.eager_fallbacks == 1
+    assert [str(w.message) for w in caught if issubclass(w.category, RuntimeWarning)] == \
+        ["CapturedTrainStep: a batch of another class than the captured one runs eagerly (counted in .eager_fallbacks)"]
+    got = [loss.detach().clone()] + [p.grad.clone() for p in m2.parameters()]
+    assert len(got) == len(want)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+
+
 @pytest.mark.parametrize("case", ["tiny_s0_eps1_gsum_nsum", "tiny_s1_eps0_gaverage_nsum", "tiny_s2_mlp1",
                                   "tiny_s1_eps1_gaverage_nmax_iso"])
 def test_gradient_sink_matches_autograd_accumulation(case):
