@@ -82,7 +82,8 @@ class TorchCpuGIN:
         k = self.m - 1
         return F.linear(x, self.p[f"mlps.{l}.linears.{k}.weight"], self.p[f"mlps.{l}.linears.{k}.bias"])
 
-    def forward(self, batch, perm, training=True, want_disc=True):
+    def forward(self, batch, perm, training=True, want_disc=True, out=None):
+        """out: an optional dict that receives the per-layer outputs ("hidden", [N, H] each) and the readout ("g_f")"""
         X = torch.cat([torch.as_tensor(np.asarray(g.node_features), dtype=torch.float32) for g in batch], 0)   # :195
         P = _graph_pool(batch, self.gpool)                                                    # :196
         n0 = int(batch[0].num_nodes)
@@ -104,6 +105,8 @@ class TorchCpuGIN:
             c_logit = c_logit + F.linear(ph, self.p[f"linears_prediction.{l}.weight"],
                                          self.p[f"linears_prediction.{l}.bias"])
             latent.append(ph)
+        if out is not None:
+            out["hidden"], out["g_f"] = [t.detach() for t in hidden], torch.cat(latent, 1).detach()
         if not want_disc:
             return c_logit, None
         n_f, g_f = torch.cat(hidden, 1), torch.cat(latent, 1)                                 # :233-234

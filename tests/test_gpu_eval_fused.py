@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import Calibrated, RTOL, assert_close, load_case
+from helpers import Calibrated, RTOL, assert_close, golden_cases, load_case
 from test_gpu_kernels import RG, random_graphs
 from test_gpu_model_parity import make_graphs, make_model, oracle_batch, oracle_model
 
@@ -219,3 +219,64 @@ def test_backward_through_an_eval_mode_forward_on_the_encoder():
     for name in grads[0]:
         # (the upstream gradient 2 c_logit differs by the two forwards' rounding; everything else is the same backward)
         assert rel_err(grads[0][name], grads[1][name].astype(np.float64)) < 1e-4, name
+
+
+def _golden_route_params():
+    """every golden case whose neighbour pooling is not max, under the default route ("layers") and, where its envelope
+    allows (H = 64, F0 <= 64, n <= 400), the one-launch encoder; the n = 1000 cases (true_c4_*) under both, as fallbacks"""
+    out = []
+    for case in golden_cases():
+        if "_nmax" in case:
+            continue
+        cfg = load_case(case)[0]
+        for mode in MODES:
+            if mode is True and not (cfg["H"] == 64 and cfg["f0"] <= 64 and cfg["n"] <= 400) and cfg["n"] <= 416:
+                continue
+            for replay in (False, True):
+                out.append(pytest.param(case, mode, replay, id="%s-%s-%s" % (case, ENTRY[mode], "replay" if replay else "eager")))
+    return out
+
+
+@pytest.mark.parametrize("case,mode,replay", _golden_route_params())
+def test_eval_routes_vs_golden(case, mode, replay, monkeypatch):
+    """the reference's eval outputs (c_logit, d_logit, latent) through the evaluation encoders, eager and replayed, and
+    every layer's hidden rows from the same entry point; tiny cases at 1e-5, true-shape cases calibrated against the
+    fp64 oracle (helpers.Calibrated).  A graph beyond the encoders' 416 / 400 nodes must take the training kernels."""
+    from test_gpu_eval_envelope import eval_kernel
+    cfg, state, d = load_case(case)
+    model = make_model(cfg, state).eval()
+    model.eval_fused = mode
+    model.eval_replay = replay
+    graphs = make_graphs(cfg, d)
+    inside = cfg["n"] <= (416 if mode == "layers" else 400)
+    calls = count_calls(monkeypatch, ENTRY[mode])
+    with torch.no_grad():
+        np.random.seed(cfg["np_seed"])
+        c_logit, d_logit = model(graphs)
+        np.random.seed(cfg["np_seed"])
+        lat = model(graphs, latent=True)
+    c_logit, d_logit = c_logit.cpu().numpy(), d_logit.cpu().numpy()
+    if not inside:
+        assert not calls
+    elif replay:
+        assert len(calls) >= 1           # (warm-up passes and the capture; the replays launch it from the hipGraph)
+    else:
+        assert len(calls) == 2
+    hidden = eval_kernel(model, model._batch_of(graphs), mode)[0] if inside else None
+    rs = slice(None, None, cfg["row_stride"])
+    if case.startswith("tiny_"):
+        for l in range(cfg["L"]):
+            assert_close(hidden[l][rs], d[f"eval_hidden_{l}"], what=f"hidden {l}")
+        assert_close(c_logit, d["eval_c_logit"], what="c_logit")
+        assert_close(d_logit, d["eval_d_logit"], what="d_logit")
+        assert_close(lat, d["eval_latent"], what="latent")
+        return
+    O, om = oracle_model(cfg, state)
+    tc, td, tcache = om.forward(oracle_batch(O, cfg, d), d["perm"], training=False)
+    cal = Calibrated()
+    if hidden is not None:
+        for l in range(cfg["L"]):
+            cal.check(hidden[l][rs], d[f"eval_hidden_{l}"], tcache["hidden"][l][rs], what=f"hidden {l}")
+    cal.check(c_logit, d["eval_c_logit"], tc, what="c_logit")
+    cal.check(d_logit, d["eval_d_logit"], td, what="d_logit")
+    cal.check(lat, d["eval_latent"], tcache["g_f"], what="latent")
