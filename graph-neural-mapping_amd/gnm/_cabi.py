@@ -95,6 +95,11 @@ SIGNATURES = {
     "gnm_loss_workspace_doubles": (_ll, [_ll]),
     "gnm_loss_ce_bce": (_i, [_p, _i, _p, _i, _i, _p, _p, _ll, _ll, _f, _p, _p, _i, _p, _p, _p]),
     "gnm_loss_ce_bce_grad": (_i, [_p, _i, _p, _i, _i, _p, _p, _ll, _ll, _f, _p, _p, _i, _p, _p]),
+    "gnm_connectome_max_nodes": (_i, []),
+    "gnm_connectome_workspace_words": (_ll, [_i, _i]),
+    "gnm_connectome_thresholds": (_i, [_p, _i, _i, _ll, _ll, C.c_double, _p, _p]),
+    "gnm_connectome_structure": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
+    "gnm_connectome_emit": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
     "gnm_adam_step": (_i, [_p, _p, _p, _p, _ll, _p, _p, _p]),
 }
 

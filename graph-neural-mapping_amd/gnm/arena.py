@@ -229,6 +229,65 @@ class GraphArena:
         self._dev_tables = None
         return list(range(first, len(self.n)))
 
+    # workspace of gnm_connectome_structure / _emit per call: subjects are processed in chunks that fit
+    CONNECTOME_WORK_BYTES = 256 << 20
+
+    def add_connectivity(self, fc, sparsity, feats):
+        """Append the graphs of an [S, n, n] FC stack thresholded at `sparsity` percent (gnm/connectome.py: the
+        reference's load_data, util.py:20-122), built on the device: thresholds, edges, node order and the CSR rows
+        (csrc/connectome.hip) written straight into the arena's buffers, node features (feats: [n, F] for every
+        subject or [S, n, F]) copied device to device.  The same buffers and tables as _append_host, so graphs from
+        both paths mix in one batch.  Returns the new arena ids."""
+        from .connectome import _as_fc, _thresholds_dev
+        fcd = _as_fc(fc, self.device)              # shapes checked first; GnmError on an arena that is not on a GPU
+        S, n = int(fcd.shape[0]), int(fcd.shape[1])
+        ft = feats if torch.is_tensor(feats) else torch.as_tensor(np.asarray(feats))
+        ft = ft.to(device=self.device, dtype=torch.float32)
+        if ft.dim() == 2:
+            ft = ft.unsqueeze(0).expand(S, -1, -1)
+        F0 = int(ft.shape[-1]) if self.feat is None else self.feat.width
+        if ft.dim() != 3 or tuple(ft.shape) != (S, n, F0):
+            raise ValueError("node_features must be [n, %d] or [S, n, %d] with S = %d, n = %d, got %s"
+                             % (F0, F0, S, n, tuple(feats.shape)))
+        thr = _thresholds_dev(fcd, sparsity)
+        if S == 0:
+            return []
+        if self.feat is None:
+            self.feat = _Growable(torch.float32, self.device, width=F0)
+        per = int(lib.gnm_connectome_workspace_words(1, n))
+        chunk = max(1, min(S, self.CONNECTOME_WORK_BYTES // (4 * per)))
+        work = torch.empty(chunk * per, dtype=torch.int32, device=self.device)
+        nnz = torch.empty(S, dtype=torch.int32, device=self.device)
+        iso = torch.empty(S, dtype=torch.int32, device=self.device)
+        first = len(self.n)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            for c0 in range(0, S, chunk):
+                m = min(S, c0 + chunk) - c0
+                check(lib.gnm_connectome_structure(fcd[c0].data_ptr(), m, n, thr[c0:].data_ptr(), work.data_ptr(),
+                                                   nnz[c0:].data_ptr(), iso[c0:].data_ptr(), st),
+                      "gnm_connectome_structure")
+                nh = nnz[c0:c0 + m].cpu().numpy().astype(np.int64)       # the one small download: space to reserve
+                ih = iso[c0:c0 + m].cpu().numpy()
+                rp_base = self.rowptr.reserve(m * (n + 1))
+                col_base = self.col.reserve(int(nh.sum()))
+                rp = rp_base + np.arange(m, dtype=np.int64) * (n + 1)
+                co = col_base + np.concatenate([[0], np.cumsum(nh)[:-1]]).astype(np.int64)
+                rp_d = torch.from_numpy(rp).to(self.device)
+                co_d = torch.from_numpy(co).to(self.device)
+                check(lib.gnm_connectome_emit(work.data_ptr(), m, n, self.rowptr.buf.data_ptr(),
+                                              self.col.buf.data_ptr(), rp_d.data_ptr(), co_d.data_ptr(), st),
+                      "gnm_connectome_emit")
+                feat_base = self.feat.append(ft[c0:c0 + m].reshape(m * n, F0))
+                for j in range(m):
+                    self.n.append(n); self.nnz.append(int(nh[j])); self.sym.append(True); self.iso.append(bool(ih[j]))
+                    self.rp_off.append(int(rp[j])); self.col_off.append(int(co[j]))
+                    self.t_rp_off.append(int(rp[j])); self.t_col_off.append(int(co[j]))
+                    self.feat_off.append(feat_base + j * n)
+        self._build_bits(first)
+        self._dev_tables = None
+        return list(range(first, len(self.n)))
+
     def _build_bits(self, first):
         """bit adjacency (include/gnm_hip.h, gnm_adj_bits_build) of the graphs first.. : forward, and transposed where
         the graph is not symmetric.  Graphs too large for the matrix-core kernel, multigraphs (a repeated edge: the

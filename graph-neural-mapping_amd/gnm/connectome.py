@@ -1,0 +1,209 @@
+"""Connectome graphs from functional-connectivity matrices, built on the device.
+
+Replaces the graph loop of the reference's loader (util.py:20-122 load_data, dataset.py:93-101
+DataEdges.get_adjacency) for a whole [S, n, n] stack of FC matrices:
+
+    graphs = graphs_from_connectivity(model_or_arena, fc, sparsity, node_features, labels)
+
+Per subject s, exactly what load_data produces:
+  * threshold  thr_s = np.percentile(fc[s], 100 - sparsity) over the whole matrix, diagonal included (dataset.py:94),
+               bitwise as numpy 2.x's "linear" method computes it (csrc/connectome.hip, gnm_connectome_thresholds);
+  * edges      {u, v}, u < v, with fc[s, u, v] > thr_s: the upper triangle only (dataset.py:95-100);
+  * order      networkx's, for the graph load_data builds node by node (util.py:43-103): see order_graph().
+The graphs are registered in the arena as they come out of the device (GraphArena.add_connectivity); their edge_mat,
+neighbors and node_features are materialized on the host on first access only.
+"""
+import numbers
+
+import numpy as np
+import torch
+
+from ._cabi import GnmError, check, lib
+
+
+def _sparsity(sparsity):
+    if isinstance(sparsity, (bool, np.bool_)) or not isinstance(sparsity, numbers.Real):
+        raise ValueError("sparsity must be an int or float in [0, 100], got %r" % (sparsity,))
+    s = int(sparsity) if isinstance(sparsity, numbers.Integral) else float(sparsity)
+    if not 0 <= s <= 100:                     # NaN fails too
+        raise ValueError("sparsity must be in [0, 100], got %r" % (sparsity,))
+    return s
+
+
+def percentile_indexes(N, sparsity):
+    """(k_lo, k_hi, gamma) numpy's percentile(a, 100 - sparsity) of N values reads: order statistics k_lo and k_hi of
+    the sorted values and the _lerp weight between them (numpy/lib/_function_base_impl.py _quantile, _get_indexes,
+    _get_gamma; method "linear": virtual index (N - 1) q).  Past the last index both statistics are the maximum and
+    gamma is numpy's virtual index - (-1)."""
+    s = _sparsity(sparsity)
+    N = int(N)
+    if N < 1:
+        raise ValueError("N must be positive")
+    q = (100 - s) / 100                        # np.true_divide(100 - threshold, 100), float64
+    vi = (N - 1) * q
+    if vi >= N - 1:
+        return N - 1, N - 1, vi - (-1.0)
+    k = int(np.floor(vi))
+    return k, k + 1, vi - float(k)
+
+
+def _as_fc(fc, device):
+    """[S, n, n] float64 contiguous tensor on the device (float32 is widened first)"""
+    t = fc if torch.is_tensor(fc) else torch.from_numpy(np.asarray(fc))
+    if t.dim() != 3 or t.shape[1] != t.shape[2]:
+        raise ValueError("fc must be [S, n, n], got %s" % (tuple(t.shape),))
+    if t.dtype not in (torch.float64, torch.float32):
+        raise ValueError("fc must be float64 or float32, got %s" % t.dtype)
+    n = int(t.shape[1])
+    if n < 1 or n > int(lib.gnm_connectome_max_nodes()):
+        raise ValueError("fc matrices of %d nodes: 1 <= n <= %d is supported (uint16 column ids)"
+                         % (n, int(lib.gnm_connectome_max_nodes())))
+    if device.type != "cuda":
+        raise GnmError("connectome graphs are built on the GPU only (libgnm_hip.so); the device is %s" % device)
+    return t.to(device=device, dtype=torch.float64).contiguous()
+
+
+def _default_device(fc):
+    if torch.is_tensor(fc) and fc.is_cuda:
+        return fc.device
+    return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+
+
+def _thresholds_dev(fcd, sparsity):
+    S, n = int(fcd.shape[0]), int(fcd.shape[1])
+    k_lo, k_hi, gamma = percentile_indexes(n * n, sparsity)
+    thr = torch.empty(S, dtype=torch.float64, device=fcd.device)
+    with torch.cuda.device(fcd.device):
+        st = torch.cuda.current_stream(fcd.device).cuda_stream
+        check(lib.gnm_connectome_thresholds(fcd.data_ptr(), S, n, k_lo, k_hi, gamma, thr.data_ptr(), st),
+              "gnm_connectome_thresholds")
+    return thr
+
+
+def connectivity_thresholds(fc, sparsity, device=None):
+    """[S] float64 device tensor: np.percentile(fc[s], 100 - sparsity) per matrix, bitwise (NaN for a matrix holding a
+    NaN).  fc: [S, n, n] float64 or float32 (widened first), numpy or torch, host or device."""
+    _sparsity(sparsity)
+    dev = torch.device(device) if device is not None else _default_device(fc)
+    return _thresholds_dev(_as_fc(fc, dev), sparsity)
+
+
+def order_graph(n, iu, ju):
+    """The order load_data's networkx graph gives the undirected edges {iu[e], ju[e]} (iu < ju) of an n-node graph
+    (util.py:43-103): nodes are inserted row by row, each row first adding itself, then its new upper neighbours in
+    ascending id.  So with t(y) the first row i < y holding an edge {i, y} (y if none), the node order pi sorts by
+    (t(y), y).  Returns (edge_mat [2, 2E] int64, neighbors: list of lists, max_neighbor):
+      * edge_mat: for each u in pi order, (u, v) for every v later in pi, v ascending; then the same pairs reversed;
+      * neighbors[x]: the neighbours earlier in pi, in pi order, then the later ones in ascending id."""
+    iu = np.asarray(iu, dtype=np.int64).reshape(-1)
+    ju = np.asarray(ju, dtype=np.int64).reshape(-1)
+    t = np.arange(n, dtype=np.int64)
+    np.minimum.at(t, ju, iu)
+    pi = np.lexsort((np.arange(n), t))
+    rank = np.empty(n, dtype=np.int64)
+    rank[pi] = np.arange(n)
+    first_is_u = rank[iu] < rank[ju]
+    a = np.where(first_is_u, iu, ju)
+    b = np.where(first_is_u, ju, iu)
+    o = np.lexsort((b, rank[a]))
+    a, b = a[o], b[o]
+    edge_mat = np.stack([np.concatenate([a, b]), np.concatenate([b, a])])
+    # neighbours: the earlier ends (key rank) before the later ends (key id), per node
+    x = np.concatenate([b, a])
+    y = np.concatenate([a, b])
+    group = np.concatenate([np.zeros(a.shape[0], np.int64), np.ones(a.shape[0], np.int64)])
+    key = np.where(group == 0, rank[y], y)
+    o = np.lexsort((key, group, x))
+    deg = np.bincount(x, minlength=n)
+    neighbors = [r.tolist() for r in np.split(y[o], np.cumsum(deg)[:-1])] if n else []
+    return edge_mat, neighbors, int(deg.max()) if n else 0
+
+
+class ConnectomeGraph:
+    """S2VGraph-shaped (util.py:9-17) graph registered in a GraphArena by add_connectivity.  g, label and node_tags are
+    plain; edge_mat, neighbors, max_neighbor and node_features are read back from the device on first access (and
+    may be assigned, as on an S2VGraph)."""
+
+    __slots__ = ("g", "label", "node_tags", "_gnm_cache", "_gnm_maxnb", "_arena", "_gid", "_edge_mat", "_neighbors",
+                 "_max_neighbor", "_node_features")
+
+    def __init__(self, arena, gid, n, label):
+        self.g = range(n)                       # only len(graph.g) is read
+        self.label = int(label)
+        self.node_tags = None
+        self._arena, self._gid = arena, gid
+        self._gnm_cache = (arena._token, gid)
+        self._gnm_maxnb = None
+        self._edge_mat = self._neighbors = self._max_neighbor = self._node_features = None
+
+    def _structure(self):
+        ar, gid, n = self._arena, self._gid, len(self.g)
+        rp0, c0, E = ar.rp_off[gid], ar.col_off[gid], ar.nnz[gid]
+        rowptr = ar.rowptr.buf[rp0:rp0 + n + 1].cpu().numpy().astype(np.int64)
+        col = ar.col.buf[c0:c0 + E].cpu().numpy().view(np.uint16).astype(np.int64)
+        src = np.repeat(np.arange(n, dtype=np.int64), np.diff(rowptr))
+        up = src < col
+        em, nb, mx = order_graph(n, src[up], col[up])
+        if self._edge_mat is None:
+            self._edge_mat = torch.from_numpy(em)
+        if self._neighbors is None:
+            self._neighbors = nb
+        if self._max_neighbor is None:
+            self._max_neighbor = mx
+
+    @property
+    def edge_mat(self):
+        if self._edge_mat is None:
+            self._structure()
+        return self._edge_mat
+
+    @edge_mat.setter
+    def edge_mat(self, v):
+        self._edge_mat = v
+
+    @property
+    def neighbors(self):
+        if self._neighbors is None:
+            self._structure()
+        return self._neighbors
+
+    @neighbors.setter
+    def neighbors(self, v):
+        self._neighbors = v
+
+    @property
+    def max_neighbor(self):
+        if self._max_neighbor is None:
+            self._structure()
+        return self._max_neighbor
+
+    @max_neighbor.setter
+    def max_neighbor(self, v):
+        self._max_neighbor = v
+
+    @property
+    def node_features(self):
+        if self._node_features is None:
+            ar, r0 = self._arena, self._arena.feat_off[self._gid]
+            self._node_features = ar.feat.buf[r0:r0 + len(self.g)].cpu().clone()
+        return self._node_features
+
+    @node_features.setter
+    def node_features(self, v):
+        self._node_features = v
+
+
+def graphs_from_connectivity(model_or_arena, fc, sparsity, node_features, labels):
+    """S graphs of load_data's shape from an [S, n, n] FC stack (util.py:20-122 for one --sparsity value), registered
+    in the arena (a model means model.arena()).  node_features: [n, F] shared by every subject, or [S, n, F];
+    labels: S ints.  Returns a list of ConnectomeGraph, usable wherever S2VGraph objects are."""
+    arena = model_or_arena.arena() if hasattr(model_or_arena, "arena") and callable(model_or_arena.arena) \
+        else model_or_arena
+    _sparsity(sparsity)
+    S = int(fc.shape[0]) if hasattr(fc, "shape") else len(fc)
+    labels = [int(x) for x in (labels.tolist() if hasattr(labels, "tolist") else labels)]
+    if len(labels) != S:
+        raise ValueError("labels: %d values for %d matrices" % (len(labels), S))
+    gids = arena.add_connectivity(fc, sparsity, node_features)
+    n = int(fc.shape[1])
+    return [ConnectomeGraph(arena, gid, n, lab) for gid, lab in zip(gids, labels)]

@@ -487,6 +487,27 @@ int gnm_loss_ce_bce(const float* c_logit, int ldc, const long long* labels, int 
 int gnm_loss_ce_bce_grad(const float* c_logit, int ldc, const long long* labels, int B, int C, const float* d_logit,
                          const float* d_target, long long M, long long n_pos, float beta, const float* gscale_dev,
                          float* dC, int lddc, float* dD, void* stream);
+/* ---- Connectome graphs from connectivity matrices (util.py:20-122 load_data, dataset.py:93-101) ------------------
+ * fc: [S, n, n] fp64, contiguous; 1 <= n <= gnm_connectome_max_nodes() (GNM_ERR_UNSUPPORTED above).  One workgroup
+ * per matrix in each entry.
+ * gnm_connectome_thresholds: thr[s] = np.percentile(fc[s], 100 - sparsity) (dataset.py:94), bitwise as numpy 2.x's
+ *   "linear" method computes it: order statistics k_lo and k_hi of the n^2 values (k_hi = k_lo + 1, or both n^2 - 1
+ *   when the virtual index is past the end) combined with numpy's _lerp at weight gamma (all three from the host:
+ *   gnm/connectome.py percentile_indexes).  A NaN in the matrix gives a NaN threshold.
+ * gnm_connectome_structure: edges {u < v} with fc[s, u, v] > thr[s] (dataset.py:94-100), degrees and the networkx
+ *   node order of util.py:43-76, into work (gnm_connectome_workspace_words(S, n) 32-bit words, 16-byte aligned);
+ *   nnz[s] = directed edge count (2 x undirected), iso[s] = 1 when a node has no neighbour.
+ * gnm_connectome_emit: from work, graph s's CSR exactly as GraphArena.add builds it from util.py:97-103's edge_mat
+ *   (gnm_csr_from_edge_mat, then gnm_csr_parity_order): rowptr[g_rp_off[s] ..][n + 1], col[g_col_off[s] ..][nnz[s]]. */
+int gnm_connectome_max_nodes(void);
+long long gnm_connectome_workspace_words(int S, int n);
+int gnm_connectome_thresholds(const double* fc, int S, int n, long long k_lo, long long k_hi, double gamma, double* thr,
+                              void* stream);
+int gnm_connectome_structure(const double* fc, int S, int n, const double* thr, uint32_t* work, int32_t* nnz,
+                             int32_t* iso, void* stream);
+int gnm_connectome_emit(const uint32_t* work, int S, int n, int32_t* rowptr, uint16_t* col, const int64_t* g_rp_off,
+                        const int64_t* g_col_off, void* stream);
+
 /* gnm_adam_step replaces optimizer.step() of optim.Adam(model.parameters(), lr) (main.py:136, 39-41) on a flat
  * fp32 parameter buffer: torch.optim.Adam's default update (no AMSGrad, L2 weight decay).
  * hyper: DEVICE array of 6 doubles {lr, beta1, beta2, eps, weight_decay, grad_scale} (grad is multiplied by
