@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: graphs/sec, forward + backward, of the GIN hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full]      (N > 1: launched by torch.distributed.run)
 
 Workload at N = 1 (BASELINE.json configs[1]): batches of 1024 synthetic 400-node dense-FC
 connectivity graphs (47,600 directed edges each), 7 input features, hidden 64, 5 GIN
@@ -12,7 +12,10 @@ pool (CSR + features) and labels are resident in HBM before the timed region.  F
 every rank owns `--batch` graphs per step (weak scaling, configs[2] at --batch 512) and the
 step ends with ONE RCCL all-reduce of the flat gradient buffer.
 
-Prints one JSON line (rank 0).  Extra objects:
+Prints one JSON line (rank 0).  A plain run does only what the headline needs: set-up, warm-up, the timed steps,
+--dump-outputs, the line.  --full adds the figures that cost time or launches of their own: `cpu_baseline`, the CSR
+gather timing next to the matrix-core kernel (`roofline.csr_gather`) and, when no timed step carried HIP events
+(--graph on, N > 1), a few eager steps after the timed region for `kernel_ms` and the rooflines.  Extra objects:
   roofline      the sum-aggregation kernel at F = 64 (forward launches, as the step runs them: with the
                 previous layer's BatchNorm+ReLU+readout on the tile load): bytes per launch / mean launch duration
                 from HIP events on the launch stream, against 8 TB/s.  Bytes: for the matrix-core kernel the bytes
@@ -21,9 +24,9 @@ Prints one JSON line (rank 0).  Extra objects:
                 gather kernels the canonical count itself.
   roofline_mlp  the Linear(64,64) forward launches: bytes in + out against 8 TB/s (the split-precision bf16 kernel
                 is HBM-bound; with GNM_LIN_NO_SPLIT=1 the fp32-MFMA kernel against 157.3 TFLOP/s).
-  cpu_baseline  oracle/gin_torch_cpu.py (torch-CPU restatement with the reference's own ATen operators, all host
-                cores; pinned to the reference's golden vectors) timed on this host on config C1 (B = 32 of the same
-                graphs), rank 0, N = 1 only; the numpy oracle's time next to it.
+  cpu_baseline  (--full) oracle/gin_torch_cpu.py (torch-CPU restatement with the reference's own ATen operators,
+                all host cores; pinned to the reference's golden vectors) timed on this host on config C1 (B = 32 of the
+                same graphs), rank 0, N = 1 only; the numpy oracle's time next to it.
 
 --dump-outputs DIR writes what the last timed step computed (loss, parameter gradients, BatchNorm running
 statistics) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments compare file by file.
@@ -316,9 +319,13 @@ def main():
                     help="N > 1: BatchNorm over the union batch (20 tiny all-reduces per step, eager launches)")
     ap.add_argument("--torch-loss", action="store_true",
                     help="compute CE + 0.05*BCE with torch ops (as main.py does) instead of the fused loss kernel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline (up to ~30 s), the CSR gather "
+                         "kernel next to the matrix-core one, and kernel times on extra eager steps when no timed step "
+                         "carried HIP events")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--numpy-oracle", action="store_true",
-                    help="cpu_baseline: also time oracle/gin_oracle.py (the numpy parity checker) next to the torch-CPU port")
+                    help="--full: also time oracle/gin_oracle.py (the numpy parity checker) next to the torch-CPU port")
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--time-all-kernels", action="store_true",
                     help="HIP events around every launch (default: only the two kernels the rooflines are quoted on)")
@@ -616,7 +623,7 @@ def main():
                       "grads_agree_after_allreduce": bool((allv[:, 1] == allv[0, 1]).all() and (allv[:, 2] == allv[0, 2]).all()),
                       "grad_abs_sum": float(allv[0, 2]), "final_loss_per_rank": [float(v) for v in allv[:, 3]]}
 
-    if timer is None and not args.no_kernel_timer and rank == 0:
+    if args.full and timer is None and not args.no_kernel_timer and rank == 0:
         # replayed steps carry no HIP events: time the two roofline kernels on a few eager steps of the same
         # batches, after (and outside) the timed region
         core.TIMER = core.KernelTimer(("agg_fwd_F%d" % H, "agg_bwd_F%d" % H, "lin_fwd_K%d_H%d" % (H, H)))
@@ -738,7 +745,7 @@ def main():
                     # (only when the arrays are kept: by default the activation is not written at all)
                     extra = 4.0 * n * H * meta["B"]
                     roof["frac_incl_fused_activation_write"] = (bytes_launch + extra) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-                if meta.get("mfma") and rank == 0:
+                if args.full and meta.get("mfma") and rank == 0:
                     # BASELINE.json's north_star describes the aggregation as a CSR neighbour-sum; dense batches run the
                     # matrix-core kernel instead.  The CSR gather kernel stays the general path:
                     # time it on the same batch here (outside the timed region, plain forward form) so that both
@@ -822,7 +829,7 @@ def main():
         out["roofline_mlp"] = roof_mlp
         out["roofline_step"] = step_roofline(B, 1e3 * elapsed / args.steps) if (default_cfg and not sparse and world == 1
                                                                             and H == 64 and L == 5) else None
-        if world == 1 and not args.no_cpu_baseline and not sparse and default_cfg:
+        if args.full and world == 1 and not args.no_cpu_baseline and not sparse and default_cfg:
             out["cpu_baseline"] = cpu_baseline(pool[:32], state_cpu, with_numpy_oracle=args.numpy_oracle)
         else:
             out["cpu_baseline"] = None

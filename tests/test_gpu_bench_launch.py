@@ -112,3 +112,26 @@ def test_bench_dump_outputs_are_reproducible(tmp_path):
     for k in a:
         assert np.array_equal(a[k], b[k]), k
     assert not all(np.array_equal(a[k], c[k]) for k in grads), "--steps 4 dumped the same step as --steps 3"
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_what_a_plain_run_leaves_out():
+    """A plain run prints the headline without the figures that cost time or launches of their own; --full adds the
+    CPU baseline (config C1: the first 32 graphs of the pool) and the CSR gather timing next to the matrix-core kernel"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "16", "--pool", "32",
+                            "--steps", "3", "--warmup", "1"] + list(extra),
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    plain, full = run(), run("--full")
+    assert plain["cpu_baseline"] is None
+    assert plain["roofline"]["mean_launch_ms"] > 0 and "csr_gather" not in plain["roofline"]
+    c = full["cpu_baseline"]
+    assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1
+    assert full["roofline"]["csr_gather"]["median_launch_ms"] > 0

@@ -10,8 +10,9 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 R=$GRAFT_REPO_ROOT
 mkdir -p gpurun_out
+OUT=$_           # the directory just made: every file of the run goes there
 timeout -k 10 900 python -m pytest tests -q -m gpu > gpurun_out/${T}_pytest.log 2>&1; echo "pytest exit $?"; tail -2 gpurun_out/${T}_pytest.log
-timeout -k 10 300 python bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err; echo "bench exit $?"; cut -c1-220 gpurun_out/${T}_bench.json
+timeout -k 10 300 python bench.py --full > $OUT/${T}_bench.json 2> $OUT/${T}_bench.err; echo "bench exit $?"; cut -c1-220 $OUT/${T}_bench.json
 timeout -k 10 300 python bench.py --config c4 > gpurun_out/${T}_c4_bench.json 2> gpurun_out/${T}_c4_bench.err; echo "c4 exit $?"; cut -c1-200 gpurun_out/${T}_c4_bench.json
 GNM_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --batch 512 --no-cpu-baseline > gpurun_out/${T}_bench_rccl_world1.json 2> gpurun_out/${T}_bench_rccl1.err; echo "rccl exit $?"; cut -c1-200 gpurun_out/${T}_bench_rccl_world1.json
 echo "# python tools/time_train_loop.py 32 ; python tools/time_eval.py" > gpurun_out/${T}_caller_side_timings.txt
