@@ -100,6 +100,11 @@ SIGNATURES = {
     "gnm_connectome_thresholds": (_i, [_p, _i, _i, _ll, _ll, C.c_double, _p, _p]),
     "gnm_connectome_structure": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
     "gnm_connectome_emit": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
+    "gnm_timeseries_max_nodes": (_i, []),
+    "gnm_timeseries_means": (_i, [_p, _i, _p, _i, _i, _p, _p]),
+    "gnm_timeseries_zscores": (_i, [_p, _i, _i, _p, _p, _p]),
+    "gnm_timeseries_gram": (_i, [_p, _i, _p, _p, _i, _i, _p, _p, _p]),
+    "gnm_timeseries_normalize": (_i, [_p, _i, _i, _p, _p]),
     "gnm_adam_step": (_i, [_p, _p, _p, _p, _ll, _p, _p, _p]),
 }
 

@@ -12,6 +12,11 @@ Per subject s, exactly what load_data produces:
   * order      networkx's, for the graph load_data builds node by node (util.py:43-103): see order_graph().
 The graphs are registered in the arena as they come out of the device (GraphArena.add_connectivity); their edge_mat,
 neighbors and node_features are materialized on the host on first access only.
+
+From ROI time series instead of FC matrices (csrc/timeseries.hip; the contract is written out above
+connectivity_from_timeseries):
+
+    graphs = graphs_from_timeseries(model_or_arena, ts, sparsity, labels, node_features="mean_bold")
 """
 import numbers
 
@@ -206,4 +211,180 @@ def graphs_from_connectivity(model_or_arena, fc, sparsity, node_features, labels
         raise ValueError("labels: %d values for %d matrices" % (len(labels), S))
     gids = arena.add_connectivity(fc, sparsity, node_features)
     n = int(fc.shape[1])
+    return [ConnectomeGraph(arena, gid, n, lab) for gid, lab in zip(gids, labels)]
+
+
+# ---------------------------------------------------------------------------------------------------- time series
+# The FC matrices load_data thresholds (dataset.py:90-91) are Pearson correlations of the ROI time series the loader
+# reads for mean_bold (dataset.py:45-46).  csrc/timeseries.hip computes, per subject, what numpy 2.x's
+# np.corrcoef(ts[s], rowvar=False) does, in numpy's order:
+#   1. Xc = X - mean(X, 0)                      (two passes: the data are centred as they are staged, never
+#                                                X^T X - T m m^T, which loses the digits of a large offset)
+#   2. C = (Xc^T Xc) * (1 / (T - 1))           (a multiply by the reciprocal; T = 1 gives 1 / 0 = inf, C all NaN)
+#   3. s_i = sqrt(C_ii)
+#   4. R_ij = (C_ij / s_i) / s_j              for every (i, j), from the one C_ij of the pair (C is symmetric; R is
+#                                                not, to the ulp)
+#   5. np.clip(R, -1, 1), NaN kept             (n = 1: numpy returns c / c unclipped)
+# The Gram runs on fp64 matrix cores with a fixed summation order, so it is not numpy's BLAS order: |R - numpy| is
+# within 1e-12, not bitwise.  The column means are numpy's pairwise sums over time divided by T: bitwise what np.mean
+# gives for the loader's column-major (pandas) array; a row-major array's np.mean sums sequentially and differs from
+# it by rounding.  mean_bold (dataset.py:73-74, util.py:118-121) is z = (m - m.mean()) / (m.std() + 1e-8) of those
+# means with numpy's pairwise sums over the ROIs, in fp64, then rounded to fp32.
+# Every kernel runs a subject inside one workgroup (no atomics, no split of T), so a subject's FC and features are
+# bitwise the same alone, inside a stack or inside a ragged list.
+
+def _as_tensor(a):
+    return a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
+
+
+def _check_nodes(n):
+    nmax = int(lib.gnm_timeseries_max_nodes())
+    if n < 1 or n > nmax:
+        raise ValueError("time series of %d ROIs: 1 <= n <= %d is supported" % (n, nmax))
+
+
+def pack_timeseries(ts):
+    """A list of [T_s, n] arrays (numpy or torch) packed into one [sum T, n] tensor, row after row, plus the int64 row
+    offsets t_off [S + 1] (numpy) of each subject.  The packed dtype is float64 if any array is float64, else float32
+    (widening is exact).  Arrays on the host are packed on the host; if any is on a GPU, all are packed there."""
+    parts = [_as_tensor(a) for a in ts]
+    if not parts:
+        raise ValueError("ts: an empty list of time series")
+    n = None
+    for k, p in enumerate(parts):
+        if p.dim() != 2:
+            raise ValueError("ts[%d] must be [T, n], got %s" % (k, tuple(p.shape)))
+        if p.dtype not in (torch.float64, torch.float32):
+            raise ValueError("ts[%d] must be float64 or float32, got %s" % (k, p.dtype))
+        if int(p.shape[0]) < 1:
+            raise ValueError("ts[%d] has no time points" % k)
+        if n is None:
+            n = int(p.shape[1])
+        elif int(p.shape[1]) != n:
+            raise ValueError("ts[%d] has %d ROIs, ts[0] has %d" % (k, int(p.shape[1]), n))
+    _check_nodes(n)
+    dtype = torch.float64 if any(p.dtype == torch.float64 for p in parts) else torch.float32
+    t_off = np.concatenate([[0], np.cumsum([int(p.shape[0]) for p in parts])]).astype(np.int64)
+    on_gpu = [p.device for p in parts if p.is_cuda]
+    if on_gpu:
+        packed = torch.cat([p.to(device=on_gpu[0], dtype=dtype) for p in parts])
+    else:
+        npd = np.float64 if dtype == torch.float64 else np.float32
+        packed = torch.from_numpy(np.concatenate([p.numpy().astype(npd, copy=False) for p in parts]))
+    return packed, t_off
+
+
+def _ts_device(ts):
+    if torch.is_tensor(ts) and ts.is_cuda:
+        return ts.device
+    if isinstance(ts, (list, tuple)):
+        for a in ts:
+            if torch.is_tensor(a) and a.is_cuda:
+                return a.device
+    return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+
+
+def _timeseries(ts):
+    """(x [sum T, n] float32 / float64 tensor, t_off [S + 1] int64 numpy, S, n) from an [S, T, n] array or a list of
+    [T_s, n] arrays, every shape and dtype checked; nothing is copied to a device yet."""
+    if isinstance(ts, (list, tuple)):
+        x, t_off = pack_timeseries(ts)
+        S, n = len(t_off) - 1, int(x.shape[1])
+    else:
+        t = _as_tensor(ts)
+        if t.dim() != 3:
+            raise ValueError("ts must be [S, T, n] or a list of [T, n] arrays, got shape %s" % (tuple(t.shape),))
+        if t.dtype not in (torch.float64, torch.float32):
+            raise ValueError("ts must be float64 or float32, got %s" % t.dtype)
+        S, T, n = (int(d) for d in t.shape)
+        if T < 1:
+            raise ValueError("ts has no time points (T = 0)")
+        _check_nodes(n)
+        x, t_off = t.reshape(S * T, n), np.arange(S + 1, dtype=np.int64) * T
+    return x, t_off, S, n
+
+
+def _to_device(x, t_off, device):
+    if device.type != "cuda":
+        raise GnmError("time series are reduced on the GPU only (libgnm_hip.so); the device is %s" % device)
+    return x.to(device).contiguous(), torch.from_numpy(t_off).to(device)
+
+
+def _as_timeseries(ts, device):
+    """(x [sum T, n] contiguous on the device, t_off [S + 1] int64 on the device, S, n): _timeseries, then the copy"""
+    x, t_off, S, n = _timeseries(ts)
+    x, t_off = _to_device(x, t_off, device)
+    return x, t_off, S, n
+
+
+def _ts_means(x, t_off, S, n):
+    mean = torch.empty((S, n), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        check(lib.gnm_timeseries_means(x.data_ptr(), int(x.dtype == torch.float64), t_off.data_ptr(), S, n,
+                                       mean.data_ptr(), st), "gnm_timeseries_means")
+    return mean
+
+
+def _ts_fc(x, t_off, mean, S, n):
+    fc = torch.empty((S, n, n), dtype=torch.float64, device=x.device)
+    diag = torch.empty((S, n), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        check(lib.gnm_timeseries_gram(x.data_ptr(), int(x.dtype == torch.float64), t_off.data_ptr(), mean.data_ptr(),
+                                      S, n, fc.data_ptr(), diag.data_ptr(), st), "gnm_timeseries_gram")
+        check(lib.gnm_timeseries_normalize(diag.data_ptr(), S, n, fc.data_ptr(), st), "gnm_timeseries_normalize")
+    return fc
+
+
+def _ts_zscores(mean, S, n, dtype):
+    z = torch.empty((S, n), dtype=dtype, device=mean.device)
+    f64 = dtype == torch.float64
+    with torch.cuda.device(mean.device):
+        st = torch.cuda.current_stream(mean.device).cuda_stream
+        check(lib.gnm_timeseries_zscores(mean.data_ptr(), S, n, z.data_ptr() if f64 else None,
+                                         None if f64 else z.data_ptr(), st), "gnm_timeseries_zscores")
+    return z.unsqueeze(-1)
+
+
+def connectivity_from_timeseries(ts, device=None):
+    """[S, n, n] float64 device tensor: np.corrcoef(ts[s], rowvar=False) per subject, within 1e-12 elementwise, with
+    numpy's NaN pattern (a constant or non-finite ROI gives a NaN row and column, T = 1 an all-NaN matrix) and values
+    in [-1, 1] otherwise.  ts: [S, T, n] or a list of [T_s, n] arrays (time in rows, ROIs in columns), float64 or
+    float32 (widened on the device, as np.cov computes in float64), numpy or torch, host or device."""
+    dev = torch.device(device) if device is not None else _ts_device(ts)
+    x, t_off, S, n = _as_timeseries(ts, dev)
+    return _ts_fc(x, t_off, _ts_means(x, t_off, S, n), S, n)
+
+
+def mean_bold_features(ts, device=None, dtype=torch.float32):
+    """[S, n, 1] device tensor: the reference loader's mean_bold node features (dataset.py:73-74, util.py:118-121),
+    m = ts[s].mean(0), z = (m - m.mean()) / (m.std() + 1e-8) in float64, then rounded to float32.  dtype=torch.float64
+    returns the float64 z-scores.  ts as in connectivity_from_timeseries."""
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("dtype must be torch.float32 or torch.float64, got %s" % (dtype,))
+    dev = torch.device(device) if device is not None else _ts_device(ts)
+    x, t_off, S, n = _as_timeseries(ts, dev)
+    return _ts_zscores(_ts_means(x, t_off, S, n), S, n, dtype)
+
+
+def graphs_from_timeseries(model_or_arena, ts, sparsity, labels, node_features="mean_bold"):
+    """S graphs of load_data's shape from ROI time series: the FC of connectivity_from_timeseries, kept on the device
+    and passed straight to graphs_from_connectivity's builder (GraphArena.add_connectivity).  node_features:
+    "mean_bold" (the loader's [n, 1] features of each subject, mean_bold_features) or an array as
+    graphs_from_connectivity takes it ([n, F] or [S, n, F]); labels: S ints."""
+    arena = model_or_arena.arena() if hasattr(model_or_arena, "arena") and callable(model_or_arena.arena) \
+        else model_or_arena
+    _sparsity(sparsity)
+    if isinstance(node_features, str) and node_features != "mean_bold":
+        raise ValueError("node_features must be \"mean_bold\" or an array, got %r" % (node_features,))
+    labels = [int(x) for x in (labels.tolist() if hasattr(labels, "tolist") else labels)]
+    x, t_off, S, n = _timeseries(ts)
+    if len(labels) != S:
+        raise ValueError("labels: %d values for %d subjects" % (len(labels), S))
+    x, t_off = _to_device(x, t_off, arena.device)
+    mean = _ts_means(x, t_off, S, n)
+    fc = _ts_fc(x, t_off, mean, S, n)
+    feats = _ts_zscores(mean, S, n, torch.float32) if isinstance(node_features, str) else node_features
+    gids = arena.add_connectivity(fc, sparsity, feats)
     return [ConnectomeGraph(arena, gid, n, lab) for gid, lab in zip(gids, labels)]

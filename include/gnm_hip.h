@@ -508,6 +508,24 @@ int gnm_connectome_structure(const double* fc, int S, int n, const double* thr, 
 int gnm_connectome_emit(const uint32_t* work, int S, int n, int32_t* rowptr, uint16_t* col, const int64_t* g_rp_off,
                         const int64_t* g_col_off, void* stream);
 
+/* ---- connectivity and mean_bold features from ROI time series (csrc/timeseries.hip) ----------
+ * x: packed [sum T, n] row-major (time in rows, ROIs in columns), fp64 (x_f64 = 1) or fp32 (x_f64 = 0, widened on
+ * load); subject s owns rows t_off[s] .. t_off[s + 1] (int64 [S + 1], device; every T_s >= 1).
+ * 1 <= n <= gnm_timeseries_max_nodes() (= gnm_connectome_max_nodes(); GNM_ERR_UNSUPPORTED above).
+ * gnm_timeseries_means: mean[s, i] = column mean, summed in numpy's pairwise order over time, divided by T_s.
+ * gnm_timeseries_zscores: dataset.py:73-74 on the means, z = (m - m.mean()) / (m.std() + 1e-8) as numpy computes it,
+ *   fp64 into z64 [S, n] and rounded to fp32 into z32 [S, n] (either may be NULL, not both).
+ * gnm_timeseries_gram: np.cov's C = (Xc^T Xc) * (1 / (T - 1)), Xc = x - mean: the entries i <= j of fc[s] ([S, n, n]
+ *   fp64) and the diagonal into diag [S, n].  The entries i > j are left as they are.
+ * gnm_timeseries_normalize: in place on the Gram's output, np.corrcoef's R_ij = (C_ij / s_i) / s_j with s = sqrt(diag)
+ *   for both triangles from the upper one, then np.clip(R, -1, 1) with NaN kept; n = 1 gives numpy's c / c. */
+int gnm_timeseries_max_nodes(void);
+int gnm_timeseries_means(const void* x, int x_f64, const int64_t* t_off, int S, int n, double* mean, void* stream);
+int gnm_timeseries_zscores(const double* mean, int S, int n, double* z64, float* z32, void* stream);
+int gnm_timeseries_gram(const void* x, int x_f64, const int64_t* t_off, const double* mean, int S, int n, double* fc,
+                        double* diag, void* stream);
+int gnm_timeseries_normalize(const double* diag, int S, int n, double* fc, void* stream);
+
 /* gnm_adam_step replaces optimizer.step() of optim.Adam(model.parameters(), lr) (main.py:136, 39-41) on a flat
  * fp32 parameter buffer: torch.optim.Adam's default update (no AMSGrad, L2 weight decay).
  * hyper: DEVICE array of 6 doubles {lr, beta1, beta2, eps, weight_decay, grad_scale} (grad is multiplied by
