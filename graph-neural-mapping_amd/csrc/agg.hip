@@ -31,7 +31,6 @@
 // In backward it also produces d eps[layer] = sum dpooled * h (fp64 partials).
 #include "gnm_common.h"
 #include <stdlib.h>
-#include <string.h>
 
 #include "gnm_agg_args.h"
 
@@ -1686,20 +1685,13 @@ extern "C" int gnm_agg(const int32_t* rowptr, const uint16_t* col, const int64_t
     if (B <= 0) return GNM_OK;
     if (F <= 0 || n_max < 0 || n_max > 65535) return GNM_ERR_BAD_ARG;
     const int fs = gnm_agg_slice_width(F, n_max);
-    AggArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rowptr = rowptr; a.col = col; a.b_rp_off = b_rp_off; a.b_col_off = b_col_off;
-    a.deg_rowptr = deg_rowptr ? deg_rowptr : rowptr;
-    a.b_deg_off = b_deg_off ? b_deg_off : b_rp_off;
-    a.node_off = node_off; a.x = x; a.y = y; a.eps = eps; a.hfwd = hfwd; a.deps_partial = deps_partial;
-    a.ldx = ldx; a.ldy = ldy; a.ldh = ldh; a.F = F;
-    a.nslices = fs > 0 ? (F + fs - 1) / fs : 1;
-    a.average = average; a.self_loop = self_loop; a.backward = backward;
-    a.debug = 0;
+    if (deps_partial && !hfwd) return GNM_ERR_BAD_ARG;
+    AggArgs a = agg_args(rowptr, col, b_rp_off, b_col_off, deg_rowptr, b_deg_off, node_off, x, ldx, y, ldy, F, eps,
+                         average, self_loop, backward, hfwd, ldh, deps_partial);
+    if (fs > 0) a.nslices = (F + fs - 1) / fs;
     a.ids_in_lds = nnz_max > 0 ? nnz_max : 0;   // launch_agg turns this into the 0/1 flag
     static const int env_debug = gnm_env_int("GNM_AGG16_DEBUG", 0);   // only acted on by -DGNM_AGG16_TUNING builds
     a.debug = env_debug;
-    if (deps_partial && !hfwd) return GNM_ERR_BAD_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (fs == 0) {              // no slice of this graph fits in LDS: gather from global memory
         a.nslices = 1;
@@ -1717,11 +1709,6 @@ extern "C" int gnm_agg(const int32_t* rowptr, const uint16_t* col, const int64_t
 
 // Aggregation backward fused with the BatchNorm-backward statistics of the layer below
 // (see AggArgs): only for the 64-wide single-slice shape; GNM_ERR_UNSUPPORTED otherwise.
-static AggArgs g_stats_none() {
-    AggArgs z;
-    memset(&z, 0, sizeof(z));
-    return z;
-}
 extern "C" int gnm_agg_bwd_stats(const int32_t* rowptr, const uint16_t* col, const int64_t* b_rp_off,
                                  const int64_t* b_col_off, const int32_t* deg_rowptr, const int64_t* b_deg_off,
                                  const int32_t* node_off, int B, int n_max, int nnz_max, const float* x, int ldx,
@@ -1746,13 +1733,8 @@ extern "C" int gnm_agg_bwd_stats(const int32_t* rowptr, const uint16_t* col, con
     if (al & 15) return GNM_ERR_UNSUPPORTED;
     // deps_partial with hfwd == NULL: h is recomputed from sZ in the epilogue (needs the (1+eps) self-term form)
     if (deps_partial && !hfwd && self_loop) return GNM_ERR_BAD_ARG;
-    AggArgs a = g_stats_none();
-    a.rowptr = rowptr; a.col = col; a.b_rp_off = b_rp_off; a.b_col_off = b_col_off;
-    a.deg_rowptr = deg_rowptr ? deg_rowptr : rowptr;
-    a.b_deg_off = b_deg_off ? b_deg_off : b_rp_off;
-    a.node_off = node_off; a.x = x; a.y = y; a.eps = eps; a.hfwd = hfwd; a.deps_partial = deps_partial;
-    a.ldx = ldx; a.ldy = ldy; a.ldh = ldh; a.F = F; a.nslices = 1;
-    a.average = average; a.self_loop = self_loop; a.backward = 1;
+    AggArgs a = agg_args(rowptr, col, b_rp_off, b_col_off, deg_rowptr, b_deg_off, node_off, x, ldx, y, ldy, F, eps,
+                         average, self_loop, 1, hfwd, ldh, deps_partial);
     a.sZ = sZ; a.s_scale = s_scale; a.s_shift = s_shift; a.s_mean = s_mean; a.s_rstd = s_rstd;
     a.s_dpool = dpool; a.s_dsc1 = dsc1; a.s_U = U; a.s_inv_perm = inv_perm; a.s_s2sum = s2sum;
     a.s_partial = s_partial; a.ldsz = ldsz; a.ld_dpool = ld_dpool; a.ld_U = ld_U; a.s_avg = graph_avg;
@@ -1786,12 +1768,8 @@ extern "C" int gnm_agg_fwd_bnrelu(const int32_t* rowptr, const uint16_t* col, co
                          reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(hout) |
                          reinterpret_cast<uintptr_t>(gf) | reinterpret_cast<uintptr_t>(y);
     if (al & 15) return GNM_ERR_UNSUPPORTED;
-    AggArgs a = g_stats_none();
-    a.rowptr = rowptr; a.col = col; a.b_rp_off = b_rp_off; a.b_col_off = b_col_off;
-    a.deg_rowptr = rowptr; a.b_deg_off = b_rp_off;
-    a.node_off = node_off; a.x = z; a.y = y; a.eps = eps;
-    a.ldx = ldz; a.ldy = ldy; a.F = F; a.nslices = 1;
-    a.average = average; a.self_loop = self_loop; a.backward = 0;
+    AggArgs a = agg_args(rowptr, col, b_rp_off, b_col_off, nullptr, nullptr, node_off, z, ldz, y, ldy, F, eps, average,
+                         self_loop, 0, nullptr, 0, nullptr);
     a.p_scale = scale; a.p_shift = shift; a.p_hout = hout; a.p_gf = gf; a.p_ldh = ldh; a.p_ldgf = ldgf;
     a.p_gf_avg = graph_avg;
     if (sliced32) {

@@ -27,7 +27,6 @@
 //            backward terms and BatchNorm statistics of gnm_agg_bwd_stats, 128-B row segments stored.
 // The row-block -> wave map is static, so every reduction (column statistics, d eps, readout) has a fixed order.
 #include "gnm_agg_args.h"
-#include <string.h>
 #include <type_traits>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -649,15 +648,9 @@ extern "C" int gnm_aggm(const int32_t* rowptr, const uint16_t* col, const int64_
     if (B <= 0) return GNM_OK;
     if (F <= 0 || n_max < 0) return GNM_ERR_BAD_ARG;
     if (deps_partial && !hfwd) return GNM_ERR_BAD_ARG;
-    AggArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rowptr = rowptr; a.col = col; a.b_rp_off = b_rp_off; a.b_col_off = b_col_off;
+    AggArgs a = agg_args(rowptr, col, b_rp_off, b_col_off, deg_rowptr, b_deg_off, node_off, x, ldx, y, ldy, F, eps,
+                         average, self_loop, backward, hfwd, ldh, deps_partial);
     a.adj_bits = adj_bits; a.b_bits_off = b_bits_off;
-    a.deg_rowptr = deg_rowptr ? deg_rowptr : rowptr;
-    a.b_deg_off = b_deg_off ? b_deg_off : b_rp_off;
-    a.node_off = node_off; a.x = x; a.y = y; a.eps = eps; a.hfwd = hfwd; a.deps_partial = deps_partial;
-    a.ldx = ldx; a.ldy = ldy; a.ldh = ldh; a.F = F; a.nslices = 1;
-    a.average = average; a.self_loop = self_loop; a.backward = backward;
     if (!aggm_shape_ok(a, n_max)) return GNM_ERR_UNSUPPORTED;
     return launch_aggm(a, B, n_max, false, reinterpret_cast<hipStream_t>(stream));
 }
@@ -675,15 +668,9 @@ extern "C" int gnm_aggm_bwd_stats(const int32_t* rowptr, const uint16_t* col, co
     if (B <= 0) return GNM_OK;
     if (F != 64 || !y || !sZ || !s_partial) return GNM_ERR_UNSUPPORTED;
     if (deps_partial && !hfwd && self_loop) return GNM_ERR_BAD_ARG;
-    AggArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rowptr = rowptr; a.col = col; a.b_rp_off = b_rp_off; a.b_col_off = b_col_off;
+    AggArgs a = agg_args(rowptr, col, b_rp_off, b_col_off, deg_rowptr, b_deg_off, node_off, x, ldx, y, ldy, F, eps,
+                         average, self_loop, 1, hfwd, ldh, deps_partial);
     a.adj_bits = adj_bits; a.b_bits_off = b_bits_off;
-    a.deg_rowptr = deg_rowptr ? deg_rowptr : rowptr;
-    a.b_deg_off = b_deg_off ? b_deg_off : b_rp_off;
-    a.node_off = node_off; a.x = x; a.y = y; a.eps = eps; a.hfwd = hfwd; a.deps_partial = deps_partial;
-    a.ldx = ldx; a.ldy = ldy; a.ldh = ldh; a.F = F; a.nslices = 1;
-    a.average = average; a.self_loop = self_loop; a.backward = 1;
     a.sZ = sZ; a.s_scale = s_scale; a.s_shift = s_shift; a.s_mean = s_mean; a.s_rstd = s_rstd;
     a.s_dpool = dpool; a.s_dsc1 = dsc1; a.s_U = U; a.s_inv_perm = inv_perm; a.s_s2sum = s2sum;
     a.s_partial = s_partial; a.ldsz = ldsz; a.ld_dpool = ld_dpool; a.ld_U = ld_U; a.s_avg = graph_avg;
@@ -705,14 +692,9 @@ extern "C" int gnm_aggm_fwd_bnrelu(const int32_t* rowptr, const uint16_t* col, c
     const uintptr_t al = reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift) |
                          reinterpret_cast<uintptr_t>(hout) | reinterpret_cast<uintptr_t>(gf);
     if (al & 15) return GNM_ERR_UNSUPPORTED;
-    AggArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rowptr = rowptr; a.col = col; a.b_rp_off = b_rp_off; a.b_col_off = b_col_off;
+    AggArgs a = agg_args(rowptr, col, b_rp_off, b_col_off, nullptr, nullptr, node_off, z, ldz, y, ldy, F, eps, average,
+                         self_loop, 0, nullptr, 0, nullptr);
     a.adj_bits = adj_bits; a.b_bits_off = b_bits_off;
-    a.deg_rowptr = rowptr; a.b_deg_off = b_rp_off;
-    a.node_off = node_off; a.x = z; a.y = y; a.eps = eps;
-    a.ldx = ldz; a.ldy = ldy; a.F = F; a.nslices = 1;
-    a.average = average; a.self_loop = self_loop; a.backward = 0;
     a.p_scale = scale; a.p_shift = shift; a.p_hout = hout; a.p_gf = gf; a.p_ldh = ldh; a.p_ldgf = ldgf;
     a.p_gf_avg = graph_avg;
     if (!aggm_shape_ok(a, n_max)) return GNM_ERR_UNSUPPORTED;

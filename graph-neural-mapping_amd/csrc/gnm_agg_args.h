@@ -1,7 +1,8 @@
 // Argument block shared by the aggregation kernels: the CSR gather kernels (agg.hip) and the matrix-core kernel over
-// the bit adjacency (aggm.hip).  One struct, so the three C-ABI entry points fill it once and either path takes it.
+// the bit adjacency (aggm.hip).  One struct, filled by agg_args() below, so either path takes it.
 #pragma once
 #include "gnm_common.h"
+#include <string.h>
 
 struct AggArgs {
     const int32_t* rowptr;     // gather structure arena (forward CSR, or transposed for backward)
@@ -39,3 +40,22 @@ struct AggArgs {
     const uint32_t* adj_bits; const int64_t* b_bits_off;
     int n_graphs, n16_max;     // aggm.hip: B (the grid is padded to whole XCD rounds) and ceil(n_max / 16) * 16
 };
+
+// What every aggregation entry fills the same way: the gather structure, the degree CSR (null: the gather's own, as
+// for symmetric graphs and the forward), input / output, eps and the d-eps operands, one slice, the mode.  Every other
+// field is zero; an entry then sets its own (prologue or epilogue, bit adjacency, slicing).
+static inline AggArgs agg_args(const int32_t* rowptr, const uint16_t* col, const int64_t* b_rp_off,
+                               const int64_t* b_col_off, const int32_t* deg_rowptr, const int64_t* b_deg_off,
+                               const int32_t* node_off, const float* x, int ldx, float* y, int ldy, int F,
+                               const float* eps, int average, int self_loop, int backward, const float* hfwd, int ldh,
+                               double* deps_partial) {
+    AggArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = rowptr; a.col = col; a.b_rp_off = b_rp_off; a.b_col_off = b_col_off;
+    a.deg_rowptr = deg_rowptr ? deg_rowptr : rowptr;
+    a.b_deg_off = b_deg_off ? b_deg_off : b_rp_off;
+    a.node_off = node_off; a.x = x; a.y = y; a.eps = eps; a.hfwd = hfwd; a.deps_partial = deps_partial;
+    a.ldx = ldx; a.ldy = ldy; a.ldh = ldh; a.F = F; a.nslices = 1;
+    a.average = average; a.self_loop = self_loop; a.backward = backward;
+    return a;
+}

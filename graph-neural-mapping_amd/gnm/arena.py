@@ -15,6 +15,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from . import core
 from ._cabi import GnmError, check, lib
 
 # A batch takes the matrix-core aggregation (csrc/aggm.hip: bit adjacency x bf16 planes) when every graph in it has
@@ -74,7 +75,7 @@ class Batch:
     # iso: some graph of the batch has a node without neighbours.  Under neighbour "average" + learn_eps that node's
     # row is 0/0 = NaN (graphcnn.py:157-158) and the reference keeps the NaN to ITS row and its neighbours' -- none -- per
     # layer; the matrix-core product would spread it to every row of the graph (0 x NaN), so such batches take the
-    # CSR gather in that mode (gnm/core.py _dense)
+    # CSR gather in that mode (gnm/core.py _dense, asked by agg_launch)
     # maxnb: gnm.maxnb.MaxNeighbours of the batch when the model pools neighbours with "max" (set by forward())
     # dense: every graph has a bit adjacency and the batch is dense enough for the matrix-core aggregation
     # (DENSE_MIN_FILL); bits_off / t_bits_off: int64 [B] offsets of the forward / transposed bit matrices in arena.bits
@@ -90,6 +91,19 @@ class Batch:
     @property
     def equal_n(self):
         return self.n_max == self.n_min
+
+    # The batch's graphs as the kernels take them: (rowptr, col, b_rp_off, b_col_off) of the forward or the transposed
+    # CSR, (adj_bits, b_bits_off) of the forward or the transposed bit rows, (deg_rowptr, b_deg_off) of the forward CSR
+    # (degrees).  Read at every call: the arena's buffers move as graphs are added (replays check them, gnm/graphs.py).
+    def csr_ptrs(self, transposed=False):
+        rp, co = (self.t_rp_off, self.t_col_off) if transposed else (self.rp_off, self.col_off)
+        return self.arena.rowptr.buf.data_ptr(), self.arena.col.buf.data_ptr(), rp.data_ptr(), co.data_ptr()
+
+    def bits_ptrs(self, transposed=False):
+        return self.arena.bits.buf.data_ptr(), (self.t_bits_off if transposed else self.bits_off).data_ptr()
+
+    def deg_ptrs(self):
+        return self.arena.rowptr.buf.data_ptr(), self.rp_off.data_ptr()
 
     @property
     def batch_class(self):
@@ -478,7 +492,7 @@ class GraphArena:
     # layer 0's neighbour aggregation of the INPUT features does not depend on any parameter:
     #   learn_eps:  pooled_0 = A X [/deg] + (1 + eps_0) X      (graphcnn.py:154-161)  -> cache A X [/deg]
     #   otherwise:  pooled_0 = (A + I) X [/(deg + 1)]          (graphcnn.py:178-182)  -> cache all of it
-    # so it is computed once per graph (by the same gnm_agg kernel, over the arena's own feature rows) and a
+    # so it is computed once per graph (by the same aggregation kernels, over the arena's own feature rows) and a
     # forward only gathers it, like the features themselves.
     AGG0_CACHE_BYTES = 8 << 30
 
@@ -498,7 +512,6 @@ class GraphArena:
             store["buf"] = nb
         if self._minus_one is None:
             self._minus_one = torch.full((1,), -1.0, dtype=torch.float32, device=self.device)
-        minus_one = self._minus_one                                   # eps = -1: no self term
         st = torch.cuda.current_stream(self.device).cuda_stream
         F0 = self.feat.width
         for g0 in range(store["graphs"], G, 4096):
@@ -507,24 +520,10 @@ class GraphArena:
             r0 = self.feat_off[g0]
             x = self.feat.buf[r0:r0 + bt.N]                 # feature rows are stored in arena (= this batch's) order
             y = store["buf"][r0:r0 + bt.N]
-            # the same kernel choice as a step that aggregates the input features itself (gnm/core.py _agg): dense
-            # batches take the matrix-core kernel, so cached and direct layer-0 values are the same bits
-            rc = -2
-            if bt.dense and (F0 < 32 or F0 % 32 == 0):
-                rc = lib.gnm_aggm(self.rowptr.buf.data_ptr(), self.col.buf.data_ptr(), bt.rp_off.data_ptr(),
-                                  bt.col_off.data_ptr(), self.bits.buf.data_ptr(), bt.bits_off.data_ptr(),
-                                  self.rowptr.buf.data_ptr(), bt.rp_off.data_ptr(), bt.node_off.data_ptr(), bt.B,
-                                  bt.n_max, x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), F0,
-                                  None if self_loop else minus_one.data_ptr(), int(bool(average)),
-                                  int(bool(self_loop)), 0, None, 0, None, st)
-                if rc not in (0, -2):
-                    check(rc, "gnm_aggm")
-            if rc == -2:
-                check(lib.gnm_agg(self.rowptr.buf.data_ptr(), self.col.buf.data_ptr(), bt.rp_off.data_ptr(),
-                                  bt.col_off.data_ptr(), self.rowptr.buf.data_ptr(), bt.rp_off.data_ptr(),
-                                  bt.node_off.data_ptr(), bt.B, bt.n_max, bt.nnz_max, x.data_ptr(), x.stride(0),
-                                  y.data_ptr(), y.stride(0), F0, None if self_loop else minus_one.data_ptr(),
-                                  int(bool(average)), int(bool(self_loop)), 0, None, 0, None, st), "gnm_agg")
+            # the step's kernel choice per chunk (core.agg_launch, no isolated-node exception); eps = -1: no self term
+            core.agg_launch(bt, "plain", F0, (x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), F0,
+                                              None if self_loop else self._minus_one.data_ptr(), int(bool(average)),
+                                              int(bool(self_loop)), 0, None, 0, None), timed=False, stream=st)
         store["graphs"] = G
         return store["buf"]
 

@@ -119,11 +119,14 @@ def _new_event():
 
 
 class _timed:
+    """times the launches of its block under `name` (None: never timed)"""
+
     def __init__(self, name, **meta):
         self.name, self.meta = name, meta
 
     def __enter__(self):
-        self.on = TIMER is not None and (TIMER.prefixes is None or self.name.startswith(TIMER.prefixes))
+        self.on = TIMER is not None and self.name is not None and (TIMER.prefixes is None or
+                                                                   self.name.startswith(TIMER.prefixes))
         if self.on:
             self.a = _new_event()
             self.b = _new_event()
@@ -188,37 +191,65 @@ def agg_partials_capacity(batch, F_):
     return k
 
 
-def _agg(batch, x, y, F_, eps_ptr, spec, backward, hfwd=None, deps_partial=None):
-    """y = None: only the d-eps partials are produced (no gather).  Returns the number of d-eps partials written."""
-    a = batch.arena
-    if backward:
-        rp_off, col_off = batch.t_rp_off, batch.t_col_off
-    else:
-        rp_off, col_off = batch.rp_off, batch.col_off
-    tag = "agg_%s_F%d%s" % ("bwd" if backward else "fwd", F_, "_dot" if y is None else "")
+# The neighbour aggregation's three launch forms.  Each has an entry on the matrix cores over the bit adjacency
+# (csrc/aggm.hip) and one that gathers over the CSR (csrc/agg.hip); the two take the same arguments after the graph's.
+# form -> (matrix-core entry, CSR entry, timer meta of the form)
+_AGG_FORMS = {
+    "plain": ("gnm_aggm", "gnm_agg", {}),
+    # + the BatchNorm + ReLU + readout of the layer below on the tile load
+    "fwd_bnrelu": ("gnm_aggm_fwd_bnrelu", "gnm_agg_fwd_bnrelu", {"fused_bnrelu": 1}),
+    # + the BatchNorm-backward sums of the layer below in the epilogue
+    "bwd_stats": ("gnm_aggm_bwd_stats", "gnm_agg_bwd_stats", {"fused_stats": 1}),
+}
+
+
+def agg_launch(batch, form, F_, args, spec=None, backward=False, dot=False, timed=True, stream=None):
+    """The one place that chooses between the two aggregation kernels.  args: the form's own arguments, everything
+    between the graph and the stream.  The matrix-core entry runs when _dense(batch, F_, spec) holds and it does not
+    decline (-2), else the CSR gather.  The plain form always ends on a launch; a fused form is not tried under max
+    pooling and returns -2 when both entries decline (the caller then runs the unfused kernels).  Timed as
+    agg_{fwd,bwd}_F<F_>[_dot] unless `timed` is False.  Returns (status, d-eps partials the kernel that ran wrote)."""
+    mfma_entry, csr_entry, meta = _AGG_FORMS[form]
+    plain = form == "plain"
+    if not plain and spec.n_max:
+        return -2, 0
+    B, n_max = batch.B, batch.n_max
+    pro = form == "fwd_bnrelu"          # the prologue form takes no degree CSR and writes no d-eps partials
+    graph = batch.csr_ptrs(backward)
+    deg = () if pro else batch.deg_ptrs()
+    tail = args + (_stream() if stream is None else stream,)
+    tag = ("agg_%s_F%d%s" % ("bwd" if backward else "fwd", F_, "_dot" if dot else "")) if timed else None
     if _dense(batch, F_, spec):
-        bits_off = batch.t_bits_off if backward else batch.bits_off
-        with _timed(tag, F=F_, B=batch.B, N=batch.N, mfma=1) as tm:
-            rc = lib.gnm_aggm(a.rowptr.buf.data_ptr(), a.col.buf.data_ptr(), rp_off.data_ptr(), col_off.data_ptr(),
-                              a.bits.buf.data_ptr(), bits_off.data_ptr(), a.rowptr.buf.data_ptr(),
-                              batch.rp_off.data_ptr(), batch.node_off.data_ptr(), batch.B, batch.n_max, x.data_ptr(),
-                              x.stride(0), ptr(y), y.stride(0) if y is not None else 0, F_, eps_ptr, int(spec.n_avg),
-                              int(not spec.learn_eps), int(backward), ptr(hfwd),
-                              hfwd.stride(0) if hfwd is not None else 0, ptr(deps_partial), _stream())
-            if rc != 0:
-                tm.cancel()
+        rc = _agg_try(mfma_entry, mfma_entry if plain else csr_entry, False,
+                      graph + batch.bits_ptrs(backward) + deg + (batch.node_off.data_ptr(), B, n_max) + tail,
+                      _timed(tag, F=F_, B=B, N=batch.N, **meta, mfma=1))
         if rc == 0:
-            return int(lib.gnm_aggm_num_partials(F_, batch.B))
-        if rc != -2:
-            check(rc, "gnm_aggm")
-    with _timed(tag, F=F_, B=batch.B, N=batch.N):
-        check(lib.gnm_agg(a.rowptr.buf.data_ptr(), a.col.buf.data_ptr(), rp_off.data_ptr(), col_off.data_ptr(),
-                          a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(), batch.node_off.data_ptr(), batch.B,
-                          batch.n_max, batch.nnz_max, x.data_ptr(), x.stride(0), ptr(y),
-                          y.stride(0) if y is not None else 0, F_,
-                          eps_ptr, int(spec.n_avg), int(not spec.learn_eps), int(backward), ptr(hfwd),
-                          hfwd.stride(0) if hfwd is not None else 0, ptr(deps_partial), _stream()), "gnm_agg")
-    return int(lib.gnm_agg_num_partials(F_, batch.n_max, batch.B))
+            return 0, 0 if pro else int(lib.gnm_aggm_num_partials(F_, B))
+    rc = _agg_try(csr_entry, csr_entry, plain,
+                  graph + deg + (batch.node_off.data_ptr(), B, n_max, batch.nnz_max) + tail,
+                  _timed(tag, F=F_, B=B, N=batch.N, **meta))
+    return rc, 0 if pro or rc != 0 else int(lib.gnm_agg_num_partials(F_, n_max, B))
+
+
+def _agg_try(entry, name, final, argv, timed):
+    """one entry of agg_launch, in its `timed` block: returns its status, a decline (-2, nothing launched) only when it
+    is not the `final` one; any other failure raises under `name`"""
+    with timed as tm:
+        rc = getattr(lib, entry)(*argv)
+        if rc != 0:
+            if final or rc != -2:
+                check(rc, name)
+            tm.cancel()
+    return rc
+
+
+def _agg(batch, x, y, F_, eps_ptr, spec, backward, hfwd=None, deps_partial=None):
+    """The plain aggregation (agg_launch).  y = None: only the d-eps partials are produced (no gather).  Returns the
+    number of d-eps partials written."""
+    return agg_launch(batch, "plain", F_, (x.data_ptr(), x.stride(0), ptr(y), y.stride(0) if y is not None else 0, F_,
+                                           eps_ptr, int(spec.n_avg), int(not spec.learn_eps), int(backward), ptr(hfwd),
+                                           hfwd.stride(0) if hfwd is not None else 0, ptr(deps_partial)),
+                      spec, backward, dot=y is None)[1]
 
 
 def _max_fwd(batch, h, pooled, F_, eps_ptr):
@@ -328,7 +359,6 @@ def encoder_forward(spec, batch, X, P, training, update_running, P0=None):
     h = X
     sync = spec.sync_bn if training else None
     Ng = sync.global_count(N, dev) if sync is not None else N        # rows of the union batch
-    a = batch.arena
     pending = None      # (z, scale, shift, hout, gslice) of the previous layer: its BatchNorm+ReLU+readout not yet run
 
     def readout(z, scale, shift, hout, gslice):
@@ -352,29 +382,10 @@ def encoder_forward(spec, batch, X, P, training, update_running, P0=None):
                 # the previous layer's BatchNorm + ReLU + readout ride on this aggregation's tile load; unless the
                 # caller wants the arrays (spec.keep_hidden) the activation itself is not written
                 z, scale, shift, hout, gslice = pending
-                hout_ptr, hout_ld = (hout.data_ptr(), hout.stride(0)) if hout is not None else (None, 0)
-                rc = -2
-                if _dense(batch, F_l, spec) and not spec.n_max:
-                    with _timed("agg_fwd_F%d" % F_l, F=F_l, B=B, N=N, fused_bnrelu=1, mfma=1) as tm:
-                        rc = lib.gnm_aggm_fwd_bnrelu(
-                            a.rowptr.buf.data_ptr(), a.col.buf.data_ptr(), batch.rp_off.data_ptr(),
-                            batch.col_off.data_ptr(), a.bits.buf.data_ptr(), batch.bits_off.data_ptr(),
-                            batch.node_off.data_ptr(), B, batch.n_max, z.data_ptr(), z.stride(0), scale.data_ptr(),
-                            shift.data_ptr(), hout_ptr, hout_ld, gslice.data_ptr(), g_f.stride(0),
-                            int(spec.g_avg), pooled.data_ptr(), pooled.stride(0), F_l, eps_ptr, int(spec.n_avg),
-                            int(not spec.learn_eps), _stream())
-                        if rc != 0:
-                            tm.cancel()
-                if rc == -2 and not spec.n_max:
-                    with _timed("agg_fwd_F%d" % F_l, F=F_l, B=B, N=N, fused_bnrelu=1) as tm:
-                        rc = lib.gnm_agg_fwd_bnrelu(
-                            a.rowptr.buf.data_ptr(), a.col.buf.data_ptr(), batch.rp_off.data_ptr(),
-                            batch.col_off.data_ptr(), batch.node_off.data_ptr(), B, batch.n_max, batch.nnz_max,
-                            z.data_ptr(), z.stride(0), scale.data_ptr(), shift.data_ptr(), hout_ptr,
-                            hout_ld, gslice.data_ptr(), g_f.stride(0), int(spec.g_avg), pooled.data_ptr(),
-                            pooled.stride(0), F_l, eps_ptr, int(spec.n_avg), int(not spec.learn_eps), _stream())
-                        if rc != 0:
-                            tm.cancel()       # declined (or failed): no launch happened, the fallback below times itself
+                rc, _ = agg_launch(batch, "fwd_bnrelu", F_l, (
+                    z.data_ptr(), z.stride(0), scale.data_ptr(), shift.data_ptr(), ptr(hout),
+                    hout.stride(0) if hout is not None else 0, gslice.data_ptr(), g_f.stride(0), int(spec.g_avg),
+                    pooled.data_ptr(), pooled.stride(0), F_l, eps_ptr, int(spec.n_avg), int(not spec.learn_eps)), spec)
                 if rc == -2:
                     if hout is None:                 # declined: the unfused pair of kernels needs the array after all
                         hout = torch.empty((N, z.shape[1]), **f32)
@@ -382,7 +393,6 @@ def encoder_forward(spec, batch, X, P, training, update_running, P0=None):
                         h = hout
                     readout(z, scale, shift, hout, gslice)
                 else:
-                    check(rc, "gnm_agg_fwd_bnrelu")
                     fused = True
                 pending = None
             if spec.n_max:
@@ -566,7 +576,6 @@ def eval_forward_fused(spec, batch, perm, P, X, want_disc, mode=True):
     Cn = P["linears_prediction.0.weight"].shape[0]
     f32 = dict(dtype=torch.float32, device=dev)
     X = X.contiguous()
-    a = batch.arena
     words = []
     for l in range(L):
         for k in range(m):
@@ -600,9 +609,9 @@ def eval_forward_fused(spec, batch, perm, P, X, want_disc, mode=True):
         scratch = torch.empty(int(lib.gnm_eval_layers_scratch_floats(B, batch.n_max, H, L)), **f32)
         with _stream_scope(dev):
             check(lib.gnm_eval_layers(
-                a.bits.buf.data_ptr(), batch.bits_off.data_ptr(), batch.node_off.data_ptr(), a.rowptr.buf.data_ptr(),
-                batch.rp_off.data_ptr(), B, batch.n_max, X.data_ptr(), X.stride(0), X.shape[1], H, L, m, Cn,
-                int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS, table.data_ptr(),
+                *batch.bits_ptrs(), batch.node_off.data_ptr(), *batch.deg_ptrs(), B, batch.n_max, X.data_ptr(),
+                X.stride(0), X.shape[1], H, L, m, Cn, int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS,
+                table.data_ptr(),
                 P["eps"].data_ptr() if spec.learn_eps else None, hidden_all.data_ptr(), hidden_all.stride(0), H,
                 scratch.data_ptr(), g_f.data_ptr(), g_f.stride(0), ptr(c), c_logit.data_ptr(), c_logit.stride(0),
                 _stream()), "gnm_eval_layers")
@@ -610,9 +619,8 @@ def eval_forward_fused(spec, batch, perm, P, X, want_disc, mode=True):
       s0, s1 = torch.empty((N, H), **f32), torch.empty((N, H), **f32)
       with _stream_scope(dev):
         check(lib.gnm_eval_encoder(
-            a.bits.buf.data_ptr(), batch.bits_off.data_ptr(), batch.node_off.data_ptr(), a.rowptr.buf.data_ptr(),
-            batch.rp_off.data_ptr(), B, batch.n_max, X.data_ptr(), X.stride(0), X.shape[1], H, L, m, Cn,
-            int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS, table.data_ptr(),
+            *batch.bits_ptrs(), batch.node_off.data_ptr(), *batch.deg_ptrs(), B, batch.n_max, X.data_ptr(), X.stride(0),
+            X.shape[1], H, L, m, Cn, int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS, table.data_ptr(),
             P["eps"].data_ptr() if spec.learn_eps else None, hidden_all.data_ptr(), hidden_all.stride(0), H,
             s0.data_ptr(), s1.data_ptr(), H, g_f.data_ptr(), g_f.stride(0), ptr(c), c_logit.data_ptr(),
             c_logit.stride(0), _stream()), "gnm_eval_encoder")
@@ -717,18 +725,16 @@ def saliency_hip(spec, batch, X, P, classes, outs=None):
     [N, F0] destinations)."""
     res = []
     with _saliency_launch(spec, batch, X, P, lib.gnm_saliency_scratch_floats) as k:
-        a = batch.arena
         N, F0 = k.N, k.F0
         for ci, c in enumerate(classes):
             dX = outs[ci] if outs is not None else torch.empty((N, F0), dtype=torch.float32, device=k.dev)
             if dX.shape != (N, F0) or dX.stride(1) != 1:
                 raise GnmError("saliency output must be a row-contiguous [%d, %d] array" % (N, F0))
             with _timed("saliency_hip", B=k.B, N=N, F0=F0, H=k.H):
-                check(lib.gnm_saliency(a.bits.buf.data_ptr(), batch.t_bits_off.data_ptr(), batch.node_off.data_ptr(),
-                                       a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(), k.B, batch.n_max, N, F0, k.H,
-                                       spec.L, spec.m, k.Cn, int(c), int(spec.n_avg), int(not spec.learn_eps),
-                                       int(spec.g_avg), k.table.data_ptr(), k.eps, k.scratch.data_ptr(), dX.data_ptr(),
-                                       dX.stride(0), _stream()), "gnm_saliency")
+                check(lib.gnm_saliency(*batch.bits_ptrs(transposed=True), batch.node_off.data_ptr(), *batch.deg_ptrs(),
+                                       k.B, batch.n_max, N, F0, k.H, spec.L, spec.m, k.Cn, int(c), int(spec.n_avg),
+                                       int(not spec.learn_eps), int(spec.g_avg), k.table.data_ptr(), k.eps,
+                                       k.scratch.data_ptr(), dX.data_ptr(), dX.stride(0), _stream()), "gnm_saliency")
             res.append(dX)
     return res
 
@@ -776,15 +782,14 @@ def saliency_maps_hip(spec, batch, X, P, classes, out=None):
     in `classes`: one eval forward (_saliency_launch), then L launches of gnm_saliency_maps per class.  Parameters,
     buffers and the numpy RNG are not touched.  Returns a float32 [len(classes), N] tensor (`out` when given)."""
     with _saliency_launch(spec, batch, X, P, lib.gnm_saliency_scratch_floats) as k:
-        a = batch.arena
         out = _out_array(out, (len(classes), k.N), k.dev)
         for ci, c in enumerate(classes):
             with _timed("saliency_maps_hip", B=k.B, N=k.N, H=k.H):
-                check(lib.gnm_saliency_maps(a.bits.buf.data_ptr(), batch.t_bits_off.data_ptr(),
-                                            batch.node_off.data_ptr(), a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(),
-                                            k.B, batch.n_max, k.N, k.H, spec.L, spec.m, k.Cn, int(c), int(spec.n_avg),
-                                            int(not spec.learn_eps), int(spec.g_avg), k.table.data_ptr(), k.eps,
-                                            k.scratch.data_ptr(), out[ci].data_ptr(), _stream()), "gnm_saliency_maps")
+                check(lib.gnm_saliency_maps(*batch.bits_ptrs(transposed=True), batch.node_off.data_ptr(),
+                                            *batch.deg_ptrs(), k.B, batch.n_max, k.N, k.H, spec.L, spec.m, k.Cn, int(c),
+                                            int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg),
+                                            k.table.data_ptr(), k.eps, k.scratch.data_ptr(), out[ci].data_ptr(),
+                                            _stream()), "gnm_saliency_maps")
     return out
 
 
@@ -797,7 +802,6 @@ def edge_saliency_hip(spec, batch, X, P, classes, out=None):
     graph b's map is rows node_off[b] .. node_off[b + 1], columns 0 .. n_b."""
     L = spec.L
     with _saliency_launch(spec, batch, X, P, lambda N, H: lib.gnm_edge_saliency_scratch_floats(N, H, L)) as k:
-        a = batch.arena
         nm = int(batch.n_max)
         out = _out_array(out, (len(classes), k.N, nm), k.dev)
         W0 = P["mlps.0.linear.weight" if spec.m == 1 else "mlps.0.linears.0.weight"]
@@ -805,12 +809,11 @@ def edge_saliency_hip(spec, batch, X, P, classes, out=None):
         _linear(k.X, W0, 0, None, Y, k.N, k.F0, k.H, None, None)          # layer 0's term at width H: <dZ0, X W0^T>
         for ci, c in enumerate(classes):
             with _timed("edge_saliency_hip", B=k.B, N=k.N, H=k.H):
-                check(lib.gnm_edge_saliency(a.bits.buf.data_ptr(), batch.bits_off.data_ptr(),
-                                            batch.t_bits_off.data_ptr(), batch.node_off.data_ptr(),
-                                            a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(), k.B, nm, k.N, k.H, L,
-                                            spec.m, k.Cn, int(c), int(spec.n_avg), int(not spec.learn_eps),
-                                            int(spec.g_avg), k.table.data_ptr(), k.eps, k.scratch.data_ptr(),
-                                            Y.data_ptr(), Y.stride(0), out[ci].data_ptr(), out.stride(1), _stream()),
+                check(lib.gnm_edge_saliency(*batch.bits_ptrs(), batch.t_bits_off.data_ptr(), batch.node_off.data_ptr(),
+                                            *batch.deg_ptrs(), k.B, nm, k.N, k.H, L, spec.m, k.Cn, int(c),
+                                            int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg),
+                                            k.table.data_ptr(), k.eps, k.scratch.data_ptr(), Y.data_ptr(), Y.stride(0),
+                                            out[ci].data_ptr(), out.stride(1), _stream()),
                       "gnm_edge_saliency")
     return out
 
@@ -1184,10 +1187,7 @@ class GinInfoMaxFn(torch.autograd.Function):
                 dpooled = incoming
                 want_dh = l > 0 or need_dx
                 dh = torch.empty((N, F_l), **f32) if want_dh else None
-                part = None
-                if spec.learn_eps:
-                    eps_counts[l] = int(lib.gnm_agg_num_partials(F_l, batch.n_max, B))
-                    part = eps_parts[l]
+                part = eps_parts[l] if spec.learn_eps else None
                 eps_ptr = P["eps"].data_ptr() + 4 * l if spec.learn_eps else None
                 fused = False
                 if l > 0 and want_dh and not spec.n_max:
@@ -1197,47 +1197,20 @@ class GinInfoMaxFn(torch.autograd.Function):
                     Ulo = U[:, (l - 1) * H:l * H] if use_disc else None
                     dplo = dph[l - 1]
                     spart = torch.empty((B, 2, F_l), dtype=torch.float64, device=dev)
-                    a = batch.arena
-                    rc = -2
-                    if _dense(batch, F_l, spec):
-                        with _timed("agg_bwd_F%d" % F_l, F=F_l, B=B, N=N, fused_stats=1, mfma=1) as tm:
-                            rc = lib.gnm_aggm_bwd_stats(
-                                a.rowptr.buf.data_ptr(), a.col.buf.data_ptr(), batch.t_rp_off.data_ptr(),
-                                batch.t_col_off.data_ptr(), a.bits.buf.data_ptr(), batch.t_bits_off.data_ptr(),
-                                a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(), batch.node_off.data_ptr(), B,
-                                batch.n_max, dpooled.data_ptr(), dpooled.stride(0), dh.data_ptr(), dh.stride(0), F_l,
-                                eps_ptr, int(spec.n_avg), int(not spec.learn_eps), None, 0, ptr(part),
-                                lo.z.data_ptr(), lo.z.stride(0), lo.scale.data_ptr(), lo.shift.data_ptr(),
-                                lo.mean.data_ptr(), lo.rstd.data_ptr(), ptr(dplo),
-                                dplo.stride(0) if dplo is not None else 0, int(spec.g_avg),
-                                ptr(dsc1) if use_disc else None, ptr(Ulo), U.stride(0) if use_disc else 0,
-                                ptr(inv_perm) if use_disc else None, ptr(s2sum) if use_disc else None,
-                                spart.data_ptr(), st)
-                            if rc != 0:
-                                tm.cancel()
-                        if rc == 0 and spec.learn_eps:
-                            eps_counts[l] = int(lib.gnm_aggm_num_partials(F_l, B))
-                    if rc == -2:
-                        with _timed("agg_bwd_F%d" % F_l, F=F_l, B=B, N=N, fused_stats=1) as tm:
-                            rc = lib.gnm_agg_bwd_stats(
-                                a.rowptr.buf.data_ptr(), a.col.buf.data_ptr(), batch.t_rp_off.data_ptr(),
-                                batch.t_col_off.data_ptr(), a.rowptr.buf.data_ptr(), batch.rp_off.data_ptr(),
-                                batch.node_off.data_ptr(), B, batch.n_max, batch.nnz_max, dpooled.data_ptr(),
-                                dpooled.stride(0), dh.data_ptr(), dh.stride(0), F_l, eps_ptr, int(spec.n_avg),
-                                int(not spec.learn_eps), None, 0,      # h_in is recomputed from lo.z in the epilogue (d eps)
-                                ptr(part), lo.z.data_ptr(), lo.z.stride(0),
-                                lo.scale.data_ptr(), lo.shift.data_ptr(), lo.mean.data_ptr(), lo.rstd.data_ptr(),
-                                ptr(dplo), dplo.stride(0) if dplo is not None else 0, int(spec.g_avg),
-                                ptr(dsc1) if use_disc else None, ptr(Ulo), U.stride(0) if use_disc else 0,
-                                ptr(inv_perm) if use_disc else None, ptr(s2sum) if use_disc else None, spart.data_ptr(),
-                                st)
-                            if rc != 0:
-                                tm.cancel()
+                    rc, cnt = agg_launch(batch, "bwd_stats", F_l, (
+                        dpooled.data_ptr(), dpooled.stride(0), dh.data_ptr(), dh.stride(0), F_l, eps_ptr,
+                        int(spec.n_avg), int(not spec.learn_eps),
+                        None, 0,      # h_in is recomputed from lo.z in the epilogue (d eps)
+                        ptr(part), lo.z.data_ptr(), lo.z.stride(0), lo.scale.data_ptr(), lo.shift.data_ptr(),
+                        lo.mean.data_ptr(), lo.rstd.data_ptr(), ptr(dplo), dplo.stride(0) if dplo is not None else 0,
+                        int(spec.g_avg), ptr(dsc1) if use_disc else None, ptr(Ulo), U.stride(0) if use_disc else 0,
+                        ptr(inv_perm) if use_disc else None, ptr(s2sum) if use_disc else None, spart.data_ptr()),
+                        spec, backward=True, stream=st)
                     if rc == 0:
                         fused = True
                         pre_outer = (dh, spart, B)
-                    elif rc != -2:
-                        check(rc, "gnm_agg_bwd_stats")
+                        if spec.learn_eps:
+                            eps_counts[l] = cnt
                 if not fused and dh is None:
                     # nothing below consumes d h: only d eps[l] = sum dpooled . h is needed -- a flat dot product
                     eps_counts[l] = int(lib.gnm_rowdot_num_partials())

@@ -290,3 +290,136 @@ def test_tile_to_wave_map_of_the_linear_kernels_is_a_bijection():
             assert len(seen) == 4 * rows
             if rows == groups * nwg and nwg > 1:
                 assert len({seen[t][0] for t in range(nwg)}) == nwg
+
+
+
+# the aggregation entries by form: (matrix-core, CSR)
+_AGG_ENTRIES = {"plain": ("gnm_aggm", "gnm_agg"), "fwd_bnrelu": ("gnm_aggm_fwd_bnrelu", "gnm_agg_fwd_bnrelu"),
+                "bwd_stats": ("gnm_aggm_bwd_stats", "gnm_agg_bwd_stats")}
+_STREAM = 4242
+
+
+def _fake_agg_batch(dense, iso):
+    """an arena batch on CPU tensors, every pointer the kernels take distinct"""
+    from types import SimpleNamespace
+    from gnm.arena import Batch, BatchClass
+    buf = lambda: SimpleNamespace(buf=torch.zeros(64, dtype=torch.int32))   # noqa: E731
+    b = Batch(SimpleNamespace(rowptr=buf(), col=buf(), bits=buf()),
+              BatchClass(B=3, N=30, n_max=12, n_min=8, symmetric=False, dense=dense, iso=iso, has_bits=True, nnz_max=40))
+    for name in ("node_off", "rp_off", "col_off", "t_rp_off", "t_col_off", "bits_off", "t_bits_off"):
+        setattr(b, name, torch.zeros(4, dtype=torch.int64))
+    return b
+
+
+def _agg_calls(core, b, F, spec, npool, learn_eps):
+    """(form, backward, the form's own arguments, call -> d-eps count, timer tag, fused meta, spec or None) of every
+    route into the aggregation: core._agg forward, backward and d-eps only; the layer-0 cache's untimed call without a
+    spec; the two fused forms"""
+    x, y, hf = torch.zeros(b.N, F), torch.zeros(b.N, F), torch.zeros(b.N, F)
+    part = torch.zeros(64, dtype=torch.float64)
+    eps = 1000 if learn_eps else None
+    out = []
+    for bwd, dot in ((False, False), (True, False), (True, True)):
+        yy = None if dot else y
+        h, p = (hf, part) if bwd and learn_eps else (None, None)
+        rest = (x.data_ptr(), F, None if dot else y.data_ptr(), 0 if dot else F, F, eps, int(npool == "average"),
+                int(not learn_eps), int(bwd), None if h is None else h.data_ptr(), 0 if h is None else F,
+                None if p is None else p.data_ptr())
+        out.append(("plain", bwd, rest, lambda bwd=bwd, yy=yy, h=h, p=p: core._agg(b, x, yy, F, eps, spec, bwd, h, p),
+                    "agg_%s_F%d%s" % ("bwd" if bwd else "fwd", F, "_dot" if dot else ""), {}, spec))
+    rest0 = (x.data_ptr(), F, y.data_ptr(), F, F, eps, int(npool == "average"), int(not learn_eps), 0, None, 0, None)
+    out.append(("plain", False, rest0,
+                lambda: core.agg_launch(b, "plain", F, rest0, timed=False, stream=_STREAM)[1], None, {}, None))
+    for form, bwd, meta, graph_args in (("fwd_bnrelu", False, {"fused_bnrelu": 1}, 8),
+                                        ("bwd_stats", True, {"fused_stats": 1}, 10)):
+        from gnm._cabi import SIGNATURES
+        rest = tuple(range(7000, 7000 + len(SIGNATURES[_AGG_ENTRIES[form][1]][1]) - graph_args - 1))
+        out.append((form, bwd, rest, lambda form=form, bwd=bwd, rest=rest: core.agg_launch(b, form, F, rest, spec,
+                                                                                            backward=bwd),
+                    "agg_%s_F%d" % ("bwd" if bwd else "fwd", F), meta, spec))
+    return out
+
+
+@pytest.mark.parametrize("dense", (False, True))
+@pytest.mark.parametrize("iso", (False, True))
+@pytest.mark.parametrize("F", (7, 64, 128))
+def test_aggregation_routing_table(monkeypatch, dense, iso, F):
+    """core.agg_launch, the one choice between the matrix-core aggregation (csrc/aggm.hip) and the CSR gather
+    (csrc/agg.hip), against the routing the training step made by hand before it (core._agg, encoder_forward's fused
+    prologue, _backward's fused epilogue, the layer-0 cache): the entry tried first, the one after a decline (-2), the
+    arguments each gets, the d-eps partial count, the timer tag and meta, the failure names, and -2 from a fused form
+    that both entries decline.  The six entries are spies returning programmed statuses."""
+    from gnm import core
+    from gnm._cabi import SIGNATURES, GnmError
+    monkeypatch.setattr(core, "_new_event", _FakeEvent)
+    monkeypatch.setattr(core, "_STREAM", _STREAM)
+    status, calls = {}, []
+
+    def spy(name):
+        def call(*argv):
+            calls.append((name, argv))
+            return status[name]
+        return call
+    for pair in _AGG_ENTRIES.values():
+        for name in pair:
+            monkeypatch.setattr(core.lib, name, spy(name), raising=False)
+
+    b = _fake_agg_batch(dense, iso)
+    rowptr, col, bits = (t.buf.data_ptr() for t in (b.arena.rowptr, b.arena.col, b.arena.bits))
+    for npool in ("sum", "average", "max"):
+        for learn_eps in (False, True):
+            spec = core.GinSpec(3, 2, learn_eps, "sum", npool)
+            for form, bwd, rest, run, tag, meta, sp in _agg_calls(core, b, F, spec, npool, learn_eps):
+                # the routing before agg_launch (core._dense): a dense batch of whole 32-column blocks or F < 32 takes
+                # the matrix-core kernel, except neighbour "average" + learn_eps with an isolated node -- a rule the
+                # layer-0 cache (no spec) does not apply
+                mfma = dense and (F % 32 == 0 or F < 32) and not (
+                    sp is not None and npool == "average" and learn_eps and iso)
+                m_name, c_name = _AGG_ENTRIES[form]
+                rp, co = (b.t_rp_off, b.t_col_off) if bwd else (b.rp_off, b.col_off)
+                graph = (rowptr, col, rp.data_ptr(), co.data_ptr())
+                deg = () if form == "fwd_bnrelu" else (rowptr, b.rp_off.data_ptr())
+                node = (b.node_off.data_ptr(), b.B, b.n_max)
+                m_argv = graph + (bits, (b.t_bits_off if bwd else b.bits_off).data_ptr()) + deg + node + rest + (_STREAM,)
+                c_argv = graph + deg + node + (b.nnz_max,) + rest + (_STREAM,)
+                assert len(m_argv) == len(SIGNATURES[m_name][1]) and len(c_argv) == len(SIGNATURES[c_name][1])
+                m_count, c_count = 0, 0         # the fused forward writes no d-eps partials
+                if form != "fwd_bnrelu":
+                    m_count = int(core.lib.gnm_aggm_num_partials(F, b.B))
+                    c_count = int(core.lib.gnm_agg_num_partials(F, b.n_max, b.B))
+                base = dict(F=F, B=b.B, N=b.N, **meta)
+                for rc_m in (0, -2, -1):
+                    for rc_c in (0, -2, -1):
+                        what = (form, bwd, tag, npool, learn_eps, rc_m, rc_c)
+                        status.update({m_name: rc_m, c_name: rc_c})
+                        calls.clear()
+                        timer = core.KernelTimer()
+                        monkeypatch.setattr(core, "TIMER", timer)
+                        if form != "plain" and npool == "max":          # the fused forms: never under max pooling
+                            assert run() == (-2, 0) and calls == [] and timer.records == [], what
+                            continue
+                        # expected: entries called, result, recorded meta, failure name
+                        want_calls, want, rec, raises = [], None, None, None
+                        if mfma:
+                            want_calls.append((m_name, m_argv))
+                            if rc_m == 0:
+                                want, rec = (0, m_count), dict(base, mfma=1)
+                            elif rc_m == -1:
+                                raises = m_name if form == "plain" else c_name
+                        if not want and not raises:
+                            want_calls.append((c_name, c_argv))
+                            if rc_c == 0:
+                                want, rec = (0, c_count), base
+                            elif rc_c == -2 and form != "plain":
+                                want = (-2, 0)
+                            else:                                       # the plain form must end on a launch
+                                raises = c_name
+                        if raises:
+                            with pytest.raises(GnmError, match="^%s failed" % raises):
+                                run()
+                        else:
+                            got = run()
+                            assert got == (want[1] if form == "plain" else want), what
+                        assert calls == want_calls, what
+                        assert [(r[0], r[1]) for r in timer.records] == \
+                            ([(tag, rec)] if rec is not None and tag is not None else []), what
