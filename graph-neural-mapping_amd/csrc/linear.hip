@@ -83,10 +83,23 @@ extern "C" void gnm_debug_set_lin_stamps(void* p) { g_lin_stamps = reinterpret_c
     if (p.stamps && (threadIdx.x & 63) == 0)                                                                  \
         p.stamps[((size_t)blockIdx.x * kSplitWaves + (threadIdx.x >> 6)) * 64 + (k)] = __builtin_amdgcn_s_memtime();
 #else
+static unsigned long long* const g_lin_stamps = nullptr;
 #define GNM_LSTAMP(k)
 #define GNM_RSTAMP(k)
 #define GNM_SSTAMP(k)
 #endif
+
+// What gnm_linear_fwd and gnm_linear_dgrad_masked fill the same way; every other field is zero (the masked form then
+// sets its m* fields, a launcher its stat_rows / stage_out).
+static inline LinArgs lin_args(const float* X, int ldx, const float* W, int ldw, int w_kmajor, const float* bias, float* Z,
+                               int ldz, int N, int K, int H, const float* pro_scale, const float* pro_shift, int pro_relu,
+                               double* stats_partial) {
+    LinArgs a = {};
+    a.X = X; a.W = W; a.bias = bias; a.Z = Z; a.pro_scale = pro_scale; a.pro_shift = pro_shift;
+    a.stats_partial = stats_partial; a.ldx = ldx; a.ldw = ldw; a.ldz = ldz; a.N = N; a.K = K; a.H = H;
+    a.w_kmajor = w_kmajor; a.pro_relu = pro_relu; a.stamps = g_lin_stamps;
+    return a;
+}
 
 template <int KC, int HT>
 __global__ void __launch_bounds__(256) gnm_lin_kernel(const LinArgs p) {
@@ -1348,17 +1361,7 @@ extern "C" int gnm_linear_fwd(const float* X, int ldx, const float* W, int ldw, 
                               const float* pro_shift, int pro_relu, double* stats_partial, void* stream) {
     if (N <= 0) return GNM_OK;
     if (K <= 0 || H <= 0 || H > 128) return GNM_ERR_BAD_ARG;
-    LinArgs a;
-    a.X = X; a.W = W; a.bias = bias; a.Z = Z; a.pro_scale = pro_scale; a.pro_shift = pro_shift;
-    a.stats_partial = stats_partial; a.ldx = ldx; a.ldw = ldw; a.ldz = ldz; a.N = N; a.K = K; a.H = H;
-    a.w_kmajor = w_kmajor; a.pro_relu = pro_relu;
-    a.stat_rows = 0; a.stage_out = 0;
-    a.mZ = nullptr; a.m_scale = a.m_shift = a.m_mean = a.m_rstd = nullptr; a.ldmz = 0;
-#ifdef GNM_LIN_TUNING
-    a.stamps = g_lin_stamps;
-#else
-    a.stamps = nullptr;
-#endif
+    const LinArgs a = lin_args(X, ldx, W, ldw, w_kmajor, bias, Z, ldz, N, K, H, pro_scale, pro_shift, pro_relu, stats_partial);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int grid = gnm_linear_grid(N);
     const int HT = (H + 31) / 32;
@@ -1415,10 +1418,7 @@ extern "C" int gnm_linear_dgrad_masked(const float* dZ, int ldd, const float* W,
     if (!dZ || !W || !G || !mZ || !m_scale || !m_shift || !m_mean || !m_rstd || !stats_partial) return GNM_ERR_BAD_ARG;
     if ((ldd & 3) || (reinterpret_cast<uintptr_t>(dZ) & 15)) return GNM_ERR_UNSUPPORTED;
     if ((long long)(ldd > ldg ? (ldd > ldmz ? ldd : ldmz) : (ldg > ldmz ? ldg : ldmz)) * 32 * 4 >= (1LL << 31)) return GNM_ERR_UNSUPPORTED;
-    LinArgs a;
-    a.X = dZ; a.W = W; a.bias = nullptr; a.Z = G; a.pro_scale = nullptr; a.pro_shift = nullptr;
-    a.stats_partial = stats_partial; a.ldx = ldd; a.ldw = ldw; a.ldz = ldg; a.N = N; a.K = H; a.H = K;
-    a.w_kmajor = 1; a.pro_relu = 0; a.stamps = nullptr; a.stat_rows = 0; a.stage_out = 0;
+    LinArgs a = lin_args(dZ, ldd, W, ldw, 1, nullptr, G, ldg, N, H, K, nullptr, nullptr, 0, stats_partial);
     a.mZ = mZ; a.m_scale = m_scale; a.m_shift = m_shift; a.m_mean = m_mean; a.m_rstd = m_rstd; a.ldmz = ldmz;
     return launch_lin_split128(a, gnm_linear_grid(N), reinterpret_cast<hipStream_t>(stream));
 }
@@ -1898,6 +1898,17 @@ __global__ void __launch_bounds__(1024) gnm_reduce_partials_kernel(const float* 
     }
 }
 
+// One such reduction: `nblk` partials of [H * kw + H] floats in `workspace` into columns k0 .. k0 + kw of dW, and db.
+static int launch_reduce_partials(const float* workspace, int nblk, int H, int kw, int k0, float* dW, int ldw, float* db,
+                                  hipStream_t s) {
+    const long long stride = (long long)H * kw + H;
+    const int count = H * kw + H;
+    hipLaunchKernelGGL(gnm_reduce_partials_kernel, dim3((count + 31) / 32), dim3(1024), 0, s, workspace, nblk, stride,
+                       H, kw, k0, dW, ldw, db);
+    GNM_CHECK_LAUNCH();
+    return GNM_OK;
+}
+
 // ------------------------------------------------------------------------------
 // Fused backward of one Linear that is followed by a train/eval BatchNorm (mlp.py:48,
 // graphcnn.py:163): replaces  gnm_bn_bwd_apply -> gnm_linear_wgrad -> gnm_linear_fwd(dgrad)
@@ -1927,6 +1938,23 @@ struct LbArgs {
     const float* bias;            // gnm_linear_bwd_rz_kernel only: Z is not read but recomputed as f(X) W^T + bias
     int part_rows;                // ... and the rows of `partial` / `s_partial` its launch writes (two per workgroup)
 };
+
+// What both fused-backward entries fill the same way.  Every other field is zero: gnm_linear_bwd_fused then sets Z,
+// gnm_linear_bwd_fused_rz the bias and part_rows.
+static inline LbArgs lb_args(const float* G, int ldg, const float* mean, const float* rstd, const float* cA,
+                             const float* m1, const float* m2, const float* X, int ldx, const float* pro_scale,
+                             const float* pro_shift, int pro_relu, const float* W, int ldw, float* dA, int lda,
+                             float* workspace, int N, int K, int H, const float* sZ, int ldsz, const float* s_scale,
+                             const float* s_shift, const float* s_mean, const float* s_rstd, double* s_partial) {
+    LbArgs a = {};
+    a.sZ = sZ; a.s_scale = s_scale; a.s_shift = s_shift; a.s_mean = s_mean; a.s_rstd = s_rstd;
+    a.s_partial = s_partial; a.ldsz = ldsz;
+    a.G = G; a.X = X; a.W = W; a.mean = mean; a.rstd = rstd; a.cA = cA; a.m1 = m1; a.m2 = m2;
+    a.pro_scale = pro_scale; a.pro_shift = pro_shift; a.dA = dA; a.partial = workspace;
+    a.ldg = ldg; a.ldx = ldx; a.ldw = ldw; a.lda = lda; a.N = N; a.K = K; a.H = H; a.pro_relu = pro_relu;
+    a.stamps = g_lin_stamps;
+    return a;
+}
 
 // NARROW: K < 32 (the first Linear of layer 0, K = F0): one zero-padded 32-column tile, guarded scalar
 // accesses to X / W / dX, which are small next to the [N,H] streams G and Z.
@@ -3246,18 +3274,9 @@ extern "C" int gnm_linear_bwd_fused(const float* G, int ldg, const float* Z, int
                               reinterpret_cast<uintptr_t>(s_rstd);
         if (al2 & 15) return GNM_ERR_UNSUPPORTED;
     }
-    LbArgs a;
-    a.sZ = sZ; a.s_scale = s_scale; a.s_shift = s_shift; a.s_mean = s_mean; a.s_rstd = s_rstd;
-    a.s_partial = s_partial; a.ldsz = ldsz;
-    a.G = G; a.Z = Z; a.X = X; a.W = W; a.mean = mean; a.rstd = rstd; a.cA = cA; a.m1 = m1; a.m2 = m2;
-    a.pro_scale = pro_scale; a.pro_shift = pro_shift; a.dA = dA; a.partial = workspace;
-    a.ldg = ldg; a.ldz = ldz; a.ldx = ldx; a.ldw = ldw; a.lda = lda; a.N = N; a.K = K; a.H = H; a.pro_relu = pro_relu;
-    a.bias = nullptr; a.part_rows = 0;
-#ifdef GNM_LIN_TUNING
-    a.stamps = g_lin_stamps;
-#else
-    a.stamps = nullptr;
-#endif
+    LbArgs a = lb_args(G, ldg, mean, rstd, cA, m1, m2, X, ldx, pro_scale, pro_shift, pro_relu, W, ldw, dA, lda, workspace,
+                       N, K, H, sZ, ldsz, s_scale, s_shift, s_mean, s_rstd, s_partial);
+    a.Z = Z; a.ldz = ldz;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int grid = gnm_linear_bwd_grid(N);
     int rc = GNM_ERR_UNSUPPORTED;
@@ -3281,14 +3300,8 @@ extern "C" int gnm_linear_bwd_fused(const float* G, int ldg, const float* Z, int
         rc = samez ? (lin_no_split() ? launch_lb<2, 2, true, false, true>(a, grid, s)
                                      : launch_lb<2, 2, true, false, true, true>(a, grid, s))
                    : launch_lb<2, 2, true>(a, grid, s);
-    if (rc != GNM_OK) return rc;
-    if (!dW) return GNM_OK;      // deferred: the partials stay in `workspace` for gnm_reduce_partials_multi
-    const long long stride = (long long)H * K + H;
-    const int count = H * K + H;
-    hipLaunchKernelGGL(gnm_reduce_partials_kernel, dim3((count + 31) / 32), dim3(1024), 0, s, workspace, grid, stride,
-                       H, K, 0, dW, lddw, db);
-    GNM_CHECK_LAUNCH();
-    return GNM_OK;
+    if (rc != GNM_OK || !dW) return rc;      // dW = NULL: the partials stay in `workspace` for gnm_reduce_partials_multi
+    return launch_reduce_partials(workspace, grid, H, K, 0, dW, lddw, db, s);
 }
 
 // gnm_linear_bwd_fused for a Linear whose output Z the caller does NOT pass: Z = f(X) W^T + bias is recomputed
@@ -3311,30 +3324,14 @@ extern "C" int gnm_linear_bwd_fused_rz(const float* G, int ldg, const float* bia
     if (!narrow && ((ldx & 3) || (lda & 3))) return GNM_ERR_UNSUPPORTED;
     if (!narrow && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(dA)) & 15)) return GNM_ERR_UNSUPPORTED;
     if ((long long)32 * (ldg > ldx ? (ldg > lda ? ldg : lda) : (ldx > lda ? ldx : lda)) * 4 >= (1LL << 31)) return GNM_ERR_UNSUPPORTED;
-    LbArgs a;
-    a.sZ = sZ; a.s_scale = s_scale; a.s_shift = s_shift; a.s_mean = s_mean; a.s_rstd = s_rstd;
-    a.s_partial = s_partial; a.ldsz = ldsz;
-    a.G = G; a.Z = nullptr; a.X = X; a.W = W; a.mean = mean; a.rstd = rstd; a.cA = cA; a.m1 = m1; a.m2 = m2;
-    a.pro_scale = pro_scale; a.pro_shift = pro_shift; a.dA = dA; a.partial = workspace;
-    a.ldg = ldg; a.ldz = 0; a.ldx = ldx; a.ldw = ldw; a.lda = lda; a.N = N; a.K = K; a.H = H; a.pro_relu = pro_relu;
-#ifdef GNM_LIN_TUNING
-    a.stamps = g_lin_stamps;
-#else
-    a.stamps = nullptr;
-#endif
-    a.bias = bias;
+    LbArgs a = lb_args(G, ldg, mean, rstd, cA, m1, m2, X, ldx, pro_scale, pro_shift, pro_relu, W, ldw, dA, lda, workspace,
+                       N, K, H, sZ, ldsz, s_scale, s_shift, s_mean, s_rstd, s_partial);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int grid = gnm_linear_bwd_grid(N);
-    a.part_rows = grid;
+    a.bias = bias; a.part_rows = grid;
     const int rc = narrow ? launch_lb_rzn(a, grid, s) : launch_lb_rz(a, grid, s);
-    if (rc != GNM_OK) return rc;
-    if (!dW) return GNM_OK;
-    const long long stride = (long long)H * K + H;
-    const int count = H * K + H;
-    hipLaunchKernelGGL(gnm_reduce_partials_kernel, dim3((count + 31) / 32), dim3(1024), 0, s, workspace, grid, stride,
-                       H, K, 0, dW, lddw, db);
-    GNM_CHECK_LAUNCH();
-    return GNM_OK;
+    if (rc != GNM_OK || !dW) return rc;
+    return launch_reduce_partials(workspace, grid, H, K, 0, dW, lddw, db, s);
 }
 
 // The dW / db partial reductions of several gnm_linear_bwd_fused calls (dW = NULL there) in ONE launch: nothing in
@@ -3441,12 +3438,8 @@ extern "C" int gnm_linear_wgrad(const float* dZ, int ldd, const float* X, int ld
         GNM_WG_CASE(2, 1, 2, 1) GNM_WG_CASE(2, 2, 2, 1) GNM_WG_CASE(2, 2, 2, 2)
 #undef GNM_WG_CASE
         }
+        if (rc == GNM_OK) rc = launch_reduce_partials(workspace, grid, H, kw, k0, dW, ldw, db, s);
         if (rc != GNM_OK) return rc;
-        const long long stride = (long long)H * kw + H;
-        const int count = H * kw + H;
-        hipLaunchKernelGGL(gnm_reduce_partials_kernel, dim3((count + 31) / 32), dim3(1024), 0, s, workspace, grid,
-                           stride, H, kw, k0, dW, ldw, db);
-        GNM_CHECK_LAUNCH();
     }
     return GNM_OK;
 }

@@ -11,6 +11,7 @@ tiny [B, .] dense ops (classifier Linear(H, C), U = sigmoid(g_f) W^T).
 Every N-sized array op runs in libgnm_hip.so.  There is no CPU or eager-PyTorch fallback
 for the sum/average path: on a non-GPU tensor the calls raise.
 """
+import collections
 import contextlib
 import ctypes as C
 import types
@@ -328,6 +329,79 @@ def _linear_wide(x, W, w_kmajor, bias, z, N, K, H, pro, stats):
         _linear(x, Wv, w_kmajor, bias[h0:h0 + hw] if bias is not None else None, z[:, h0:h0 + hw], N, K, hw, pro, None)
 
 
+# What a kernel leaves in place of gnm_bn_relu_bwd_stats: G, the gradient under the ReLU mask of the BatchNorm + ReLU it
+# arrives at, and that BatchNorm's backward sums in `rows` partial rows [2, width] (fp64)
+_BnSums = collections.namedtuple("_BnSums", "G part rows")
+# a fused Linear backward's dW / db partials in its workspace: reduced by gnm_reduce_partials_multi after the loop
+_ReduceJob = collections.namedtuple("_ReduceJob", "ws dW db H K")
+# linear_bwd_launch's result: dX or None, the _BnSums of the BatchNorm below or None, the deferred _ReduceJob or None
+_LinBwd = collections.namedtuple("_LinBwd", "dA lo_sums job")
+
+
+def linear_bwd_launch(sv, lo, G, coef, W, bias, dW, db, need_dA, N, stream):
+    """The one place that routes a Linear's backward (mlp.py:43,48-49 under autograd).  sv: the Linear's _LinSave, lo:
+    the one below it in the MLP or None; G: the masked gradient at the BatchNorm after the Linear, coef = (cA, m1, m2)
+    that BatchNorm's backward coefficients (gnm_bn_bwd_finalize); dW / db: where the parameter gradients go.  In order:
+    gnm_linear_bwd_fused_rz (Z recomputed), gnm_linear_bwd_fused (stored Z; with `lo` and need_dA it also masks dA and
+    takes lo's BatchNorm-backward sums), each one pass whose dW / db partials are reduced later (job); after two
+    declines (-2) gnm_bn_bwd_apply in place, gnm_linear_wgrad, and for dA gnm_linear_dgrad_masked (K = H = 128 over a
+    BatchNorm) or the plain product _linear_wide.  Returns a _LinBwd."""
+    K, Hk, (cA, m1, m2) = sv.K, sv.H, coef
+    f32 = dict(dtype=torch.float32, device=G.device)
+    pro = (sv.pro[0].data_ptr(), sv.pro[1].data_ptr(), 1) if sv.pro else (None, None, 0)
+    dA = torch.empty((N, K), **f32) if need_dA else None
+    ws = torch.empty(int(lib.gnm_linear_bwd_workspace_floats(N, Hk, K)), **f32)
+    lo_part, los = None, (None, 0, None, None, None, None)
+    if lo is not None and need_dA:
+        lo_part = torch.empty((lib.gnm_linear_bwd_grid(N), 2, K), dtype=torch.float64, device=G.device)
+        los = (lo.z.data_ptr(), lo.z.stride(0), lo.scale.data_ptr(), lo.shift.data_ptr(), lo.mean.data_ptr(),
+               lo.rstd.data_ptr())
+    with _timed("linbwd_K%d_H%d" % (K, Hk), N=N, K=K, H=Hk) as tm:
+        # every argument after Z (dW = NULL: the partials are reduced by ONE launch after the loop)
+        args = (sv.mean.data_ptr(), sv.rstd.data_ptr(), cA.data_ptr(), m1.data_ptr(), m2.data_ptr(), sv.x_in.data_ptr(),
+                sv.x_in.stride(0), *pro, W.data_ptr(), W.stride(0), ptr(dA), dA.stride(0) if need_dA else 0, None,
+                dW.stride(0), db.data_ptr(), ws.data_ptr(), N, K, Hk, *los, ptr(lo_part), stream)
+        rc = -2
+        # (mirrors gnm_linear_bwd_fused_rz's own decline rules in csrc/linear.hip: a foreign call less per Linear)
+        if Hk == 64 and lo_part is None and ((K == 64 and need_dA) or (K <= 16 and not sv.pro)):
+            # sv.z = Linear(sv.x_in) as gnm_linear_fwd left it: the pass recomputes it instead of reading it
+            rc = lib.gnm_linear_bwd_fused_rz(G.data_ptr(), G.stride(0), bias.data_ptr(), *args)
+        if rc == -2:
+            rc = lib.gnm_linear_bwd_fused(G.data_ptr(), G.stride(0), sv.z.data_ptr(), sv.z.stride(0), *args)
+        if rc != 0:
+            tm.cancel()
+    if rc == 0:
+        return _LinBwd(dA, _BnSums(dA, lo_part, lo_part.shape[0]) if lo_part is not None else None,
+                       _ReduceJob(ws, dW, db, Hk, K))
+    if rc != -2:
+        check(rc, "gnm_linear_bwd_fused")
+    # GNM_ERR_UNSUPPORTED: the generic three-kernel path, dZ in place of G
+    check(lib.gnm_bn_bwd_apply(G.data_ptr(), G.stride(0), sv.z.data_ptr(), sv.z.stride(0), sv.mean.data_ptr(),
+                               sv.rstd.data_ptr(), cA.data_ptr(), m1.data_ptr(), m2.data_ptr(), G.data_ptr(),
+                               G.stride(0), N, Hk, stream), "gnm_bn_bwd_apply")
+    ws = torch.empty(int(lib.gnm_wgrad_workspace_floats(N, Hk, K)), **f32)
+    with _timed("wgrad_K%d_H%d" % (K, Hk), N=N, K=K, H=Hk):
+        check(lib.gnm_linear_wgrad(G.data_ptr(), G.stride(0), sv.x_in.data_ptr(), sv.x_in.stride(0), N, Hk, K, *pro,
+                                   dW.data_ptr(), dW.stride(0), db.data_ptr(), ws.data_ptr(), stream),
+              "gnm_linear_wgrad")
+    lo_sums = None
+    if need_dA:
+        rc = -2
+        if lo is not None and K == 128 and Hk == 128:
+            # dX = dZ W with the ReLU mask of the BatchNorm + ReLU below and that BatchNorm's backward sums taken in
+            # the epilogue (replaces its gnm_bn_relu_bwd_stats pass)
+            lo_part = torch.empty((int(lib.gnm_linear_grid(N)), 2, K), dtype=torch.float64, device=G.device)
+            rc = lib.gnm_linear_dgrad_masked(G.data_ptr(), G.stride(0), W.data_ptr(), W.stride(0), dA.data_ptr(),
+                                             dA.stride(0), N, K, Hk, *los, lo_part.data_ptr(), stream)
+            if rc == 0:
+                lo_sums = _BnSums(dA, lo_part, lo_part.shape[0])
+            elif rc != -2:
+                check(rc, "gnm_linear_dgrad_masked")
+        if rc == -2:
+            _linear_wide(G, W, 1, None, dA, N, Hk, K, None, None)      # dX = dZ W
+    return _LinBwd(dA, lo_sums, None)
+
+
 # the three [B, L*H]-sized products of the Infomax tail run on the hand-written kernel (csrc/sgemm.hip)
 def _small_gemm(A, a_cols, B, b_cols, out, M, N, K):
     """out[M,N] = A' B' (csrc/sgemm.hip: gnm_small_gemm); False when the kernel declines and the caller uses torch."""
@@ -343,6 +417,11 @@ def _small_gemm(A, a_cols, B, b_cols, out, M, N, K):
 
 class _LinSave:
     __slots__ = ("x_in", "pro", "z", "scale", "shift", "mean", "rstd", "K", "H", "Ng")
+
+
+# what encoder_forward keeps of one layer.  h_in: the layer's input (X, an array, or a ZAct); pooled: its aggregation;
+# lins: the _LinSave of each Linear of its MLP; aux: what max pooling's backward needs
+_LayerSave = collections.namedtuple("_LayerSave", "h_in pooled lins aux")
 
 
 def encoder_forward(spec, batch, X, P, training, update_running, P0=None):
@@ -438,7 +517,7 @@ def encoder_forward(spec, batch, X, P, training, update_running, P0=None):
             hout = torch.empty((N, H), **f32) if getattr(spec, "keep_hidden", False) else None
             readout(x_in, pro[0], pro[1], hout, gslice)
             hnew = hout if hout is not None else ZAct(x_in, pro[0], pro[1])
-        saved.append((h, pooled, lins, aux))
+        saved.append(_LayerSave(h, pooled, lins, aux))
         hidden.append(hnew)
         h = hnew
     return hidden, g_f, saved
@@ -489,9 +568,8 @@ def hidden_tensor(h):
     return h.tensor() if isinstance(h, ZAct) else h
 
 
-def _hptr_array(hidden):
-    arr = (C.c_void_p * len(hidden))(*[t.data_ptr() for t in hidden])
-    return arr
+def _ptr_array(tensors):
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
 def _hidden_ptr_arrays(hidden):
@@ -511,9 +589,6 @@ def _hidden_ptr_arrays(hidden):
             raise GnmError("hidden layers with different leading dimensions (%d, %d)" % (ld, stride))
         ld = stride
     return hp, sp, tp, ld
-
-
-_ptr_array = _hptr_array
 
 
 def eval_fused_ok(spec, batch, X, P, mode=True):
@@ -605,41 +680,20 @@ def eval_forward_fused(spec, batch, perm, P, X, want_disc, mode=True):
     g_f = torch.empty((B, L * H), **f32)
     c = torch.empty_like(g_f) if want_disc else None
     c_logit = torch.empty((B, Cn), **f32)
-    if mode == "layers":
-        scratch = torch.empty(int(lib.gnm_eval_layers_scratch_floats(B, batch.n_max, H, L)), **f32)
-        with _stream_scope(dev):
-            check(lib.gnm_eval_layers(
-                *batch.bits_ptrs(), batch.node_off.data_ptr(), *batch.deg_ptrs(), B, batch.n_max, X.data_ptr(),
-                X.stride(0), X.shape[1], H, L, m, Cn, int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS,
-                table.data_ptr(),
-                P["eps"].data_ptr() if spec.learn_eps else None, hidden_all.data_ptr(), hidden_all.stride(0), H,
-                scratch.data_ptr(), g_f.data_ptr(), g_f.stride(0), ptr(c), c_logit.data_ptr(), c_logit.stride(0),
-                _stream()), "gnm_eval_layers")
-    else:
-      s0, s1 = torch.empty((N, H), **f32), torch.empty((N, H), **f32)
-      with _stream_scope(dev):
-        check(lib.gnm_eval_encoder(
-            *batch.bits_ptrs(), batch.node_off.data_ptr(), *batch.deg_ptrs(), B, batch.n_max, X.data_ptr(), X.stride(0),
-            X.shape[1], H, L, m, Cn, int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS, table.data_ptr(),
-            P["eps"].data_ptr() if spec.learn_eps else None, hidden_all.data_ptr(), hidden_all.stride(0), H,
-            s0.data_ptr(), s1.data_ptr(), H, g_f.data_ptr(), g_f.stride(0), ptr(c), c_logit.data_ptr(),
-            c_logit.stride(0), _stream()), "gnm_eval_encoder")
+    shared = (*batch.bits_ptrs(), batch.node_off.data_ptr(), *batch.deg_ptrs(), B, batch.n_max, X.data_ptr(), X.stride(0),
+              X.shape[1], H, L, m, Cn, int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS, table.data_ptr(),
+              P["eps"].data_ptr() if spec.learn_eps else None, hidden_all.data_ptr(), hidden_all.stride(0), H)
     with _stream_scope(dev):
+        outs = (g_f.data_ptr(), g_f.stride(0), ptr(c), c_logit.data_ptr(), c_logit.stride(0), _stream())
+        if mode == "layers":
+            scratch = torch.empty(int(lib.gnm_eval_layers_scratch_floats(B, batch.n_max, H, L)), **f32)
+            check(lib.gnm_eval_layers(*shared, scratch.data_ptr(), *outs), "gnm_eval_layers")
+        else:
+            s0, s1 = torch.empty((N, H), **f32), torch.empty((N, H), **f32)
+            check(lib.gnm_eval_encoder(*shared, s0.data_ptr(), s1.data_ptr(), H, *outs), "gnm_eval_encoder")
         d_logit = torch.zeros((0, 1), **f32)
         if want_disc:
-            if not batch.equal_n:
-                raise RuntimeError("Discriminator expands each graph summary N//B times (discriminator.py:24): "
-                                   "all graphs of a batch must have the same number of nodes")
-            Wd = P["disc.f_k.weight"][0]
-            U = torch.empty((B, Wd.shape[0]), **f32)
-            if not _small_gemm(c, 0, Wd, 0, U, B, Wd.shape[0], Wd.shape[1]):
-                U = c @ Wd.t()                                                # U[g] = W c_g
-            perm_rows = perm_to_device(perm, B, dev)
-            d_logit = torch.empty((2 * N, 1), **f32)
-            hp_, sp_, tp_, ldh_ = _hidden_ptr_arrays(hidden)
-            check(lib.gnm_disc_score_fwd(hp_, sp_, tp_, ldh_, L, H, U.data_ptr(), U.stride(0), perm_rows.data_ptr(),
-                                         P["disc.f_k.bias"].data_ptr(), batch.node_off.data_ptr(), N, B,
-                                         d_logit.data_ptr(), _stream()), "gnm_disc_score_fwd")
+            d_logit = _disc_forward(spec, batch, P, hidden, c, perm, timed=False)[0]
     return c_logit, d_logit, g_f
 
 
@@ -675,7 +729,7 @@ def _saliency_table_words(spec, P, saved):
         for k in range(m):
             wn = f"mlps.{l}.linear" if m == 1 else f"mlps.{l}.linears.{k}"
             W = P[wn + ".weight"]
-            sv = saved[l][2][k]
+            sv = saved[l].lins[k]
             if W.stride(1) != 1 or sv.z.stride(1) != 1:
                 raise GnmError("Linear weights and outputs must be row-contiguous")
             words += [W.data_ptr(), W.stride(0), sv.z.data_ptr(), sv.z.stride(0), sv.scale.data_ptr(),
@@ -756,7 +810,7 @@ def class_activation_hip(spec, batch, X, P, classes, out=None):
         _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
         words = []
         for l in range(L):
-            sv = saved[l][2][m - 1]
+            sv = saved[l].lins[m - 1]
             wp = P[f"linears_prediction.{l}.weight"]
             if sv.z.stride(1) != 1 or wp.stride(1) != 1:
                 raise GnmError("layer outputs and classifier weights must be row-contiguous")
@@ -818,6 +872,326 @@ def edge_saliency_hip(spec, batch, X, P, classes, out=None):
     return out
 
 
+class _Grads:
+    """The parameter gradients of one backward.  With a sink (spec.grad_sink) the kernels write into its tensors,
+    overwriting them, and autograd gets None; without one, into fresh tensors that autograd gets."""
+
+    def __init__(self, sink):
+        self.sink, self.fresh = sink, {}
+
+    def out(self, name, like):
+        """the tensor a kernel writes gradient `name` into"""
+        if self.sink is not None:
+            return self.sink[name]
+        t = self.fresh[name] = torch.empty_like(like)
+        return t
+
+    def put(self, name, value):
+        """record a gradient computed by a torch op"""
+        if self.sink is not None:
+            self.sink[name].copy_(value.reshape(self.sink[name].shape))
+        else:
+            self.fresh[name] = value
+
+    def result(self, names, needs):
+        """one entry per parameter name: its fresh tensor where `needs` asks for one, else None"""
+        return tuple(self.fresh.get(name) if need else None for name, need in zip(names, needs))
+
+
+def _head_forward(spec, P, g_f, H, training, dropout_p, want_c):
+    """Classifier head (graphcnn.py:224-231) and c = sigmoid(g_f) (:239, only when want_c): one launch (csrc/head.hip),
+    or batched matrix products for shapes outside the kernel.  Returns (c_logit, c, masks, Wp, fused_head, wps)."""
+    L, B, dev = spec.L, g_f.shape[0], g_f.device
+    wps = [P[f"linears_prediction.{l}.weight"] for l in range(L)]
+    bps = [P[f"linears_prediction.{l}.bias"] for l in range(L)]
+    Cn = wps[0].shape[0]
+    masks = None
+    if training and dropout_p > 0:
+        # (F.dropout of a cached tensor of ones: the fill it would otherwise need is a launch per step)
+        ones = getattr(spec, "_ones_mask", None)
+        if ones is None or ones.shape != (L, B, Cn) or ones.device != dev:
+            ones = spec._ones_mask = torch.ones((L, B, Cn), dtype=torch.float32, device=dev)
+        masks = F.dropout(ones, dropout_p, True)                                                      # :230
+    c_logit = torch.empty((B, Cn), dtype=torch.float32, device=dev)
+    c = torch.empty_like(g_f) if want_c else None
+    fused_head = all(w.is_contiguous() for w in wps) and all(b_.is_contiguous() for b_ in bps)
+    if fused_head:
+        rc = lib.gnm_head_fwd(g_f.data_ptr(), g_f.stride(0), B, L, H, Cn, _ptr_array(wps), _ptr_array(bps),
+                              ptr(masks), c_logit.data_ptr(), c_logit.stride(0), ptr(c),
+                              c.stride(0) if c is not None else 0, _stream())
+        if rc == -2:
+            fused_head = False
+        else:
+            check(rc, "gnm_head_fwd")
+    Wp = None
+    if not fused_head:          # shapes outside the head kernel (C > 256 classes): batched matrix products
+        Wp = torch.stack(wps)                                                            # [L,C,H]
+        G3 = g_f.view(B, L, H).transpose(0, 1)                                           # [L,B,H] view
+        lg = torch.baddbmm(torch.stack(bps).unsqueeze(1), G3, Wp.transpose(1, 2))        # [L,B,C]
+        if masks is not None:
+            lg = lg * masks
+        c_logit = lg.sum(0)
+        if want_c:
+            c = torch.sigmoid(g_f)
+    return c_logit, c, masks, Wp, fused_head, wps
+
+
+def _disc_forward(spec, batch, P, hidden, c, perm, unit=None, timed=True):
+    """The Infomax discriminator scores (discriminator.py:20-36 on graphcnn.py:198-201,239-248): U = c W^T, then one
+    score kernel over the hidden layers, which also fills the DiscUnit `unit` when given one and the shape allows.
+    Returns (d_logit, U, perm_rows, `unit` if it was filled else None)."""
+    if not batch.equal_n:
+        raise RuntimeError("Discriminator expands each graph summary N//B times (discriminator.py:24): "
+                           "all graphs of a batch must have the same number of nodes")
+    L, N, B, dev = spec.L, batch.N, batch.B, c.device
+    H = hidden[0].shape[1]
+    Wd = P["disc.f_k.weight"][0]
+    U = torch.empty((B, Wd.shape[0]), dtype=torch.float32, device=dev)
+    if not _small_gemm(c, 0, Wd, 0, U, B, Wd.shape[0], Wd.shape[1]):
+        U = c @ Wd.t()                                                # U[g] = W c_g
+    # row index = perm[g] (:198-201,242): validated on the host, pinned staging + async copy (a device tensor --
+    # a captured step's static buffer -- passes as it is: graph-capture safe)
+    perm_rows = perm_to_device(perm, B, dev)
+    d_logit = torch.empty((2 * N, 1), dtype=torch.float32, device=dev)
+    hp_, sp_, tp_, ldh_ = _hidden_ptr_arrays(hidden)
+    score_args = (hp_, sp_, tp_, ldh_, L, H, U.data_ptr(), U.stride(0), perm_rows.data_ptr(),
+                  P["disc.f_k.bias"].data_ptr(), batch.node_off.data_ptr(), N, B, d_logit.data_ptr())
+    disc_unit = None
+    with _timed("disc_score" if timed else None, N=N, L=L, H=H):
+        rc = -2
+        if unit is not None:
+            # also leave the backward's per-graph reductions (up to the loss's scalar factor): see DiscUnit
+            ldunit = (L * H + 2 + 3) & ~3
+            sums = torch.empty((B, ldunit), dtype=torch.float32, device=dev)
+            inv_perm = torch.empty(B, dtype=torch.int32, device=dev)
+            rc = lib.gnm_disc_score_fwd_unit(*score_args, sums.data_ptr(), ldunit, inv_perm.data_ptr(), _stream())
+            if rc == 0:
+                unit.unit, unit.inv_perm = sums, inv_perm
+                disc_unit = unit
+            elif rc != -2:
+                check(rc, "gnm_disc_score_fwd_unit")
+        if rc == -2:
+            check(lib.gnm_disc_score_fwd(*score_args, _stream()), "gnm_disc_score_fwd")
+    return d_logit, U, perm_rows, disc_unit
+
+
+class _Backward:
+    """What the stages of one GinInfoMaxFn.backward share: the forward's context, the gradient collector, and what one
+    stage leaves for a later one."""
+
+    def __init__(self, ctx):
+        self.ctx, self.spec, self.batch, self.P = ctx, ctx.spec, ctx.batch, ctx.P
+        self.H, self.st, self.need_dx = ctx.hidden[0].shape[1], _stream(), ctx.needs_input_grad[9]
+        self.f32 = dict(dtype=torch.float32, device=ctx.g_f.device)
+        self.grads = _Grads(ctx.spec.grad_sink)
+        # the discriminator's terms of every layer's gradient (_disc_backward): d sc_1, U, the inverse permutation, s2sum
+        self.dsc1 = self.U = self.inv_perm = self.s2sum = None
+        self.dph = [None] * ctx.spec.L      # d loss / d (layer l's readout)  (_head_backward)
+        self.deps = self.eps_parts = None   # d eps, and its fp64 partials [L, .] from the L aggregation backwards ...
+        self.eps_counts = [0] * ctx.spec.L  # ... with how many each wrote: summed by ONE launch at the end
+        self.jobs = []                      # the _ReduceJob of every fused Linear backward
+
+    def disc_args(self, l):
+        """(d sc_1, layer l's columns of U, its leading dimension, inverse permutation, s2sum) as the kernels that add
+        the discriminator's term to a layer's gradient take them; NULLs for l = None or without a discriminator"""
+        if l is None or self.dsc1 is None:
+            return None, None, 0, None, None
+        return (self.dsc1.data_ptr(), self.U[:, l * self.H:(l + 1) * self.H].data_ptr(), self.U.stride(0),
+                self.inv_perm.data_ptr(), self.s2sum.data_ptr())
+
+
+def _disc_backward(s, dD):
+    """Discriminator backward (discriminator.py:28-36): the per-graph reductions -- scaled from what the forward left
+    (DiscUnit) or by gnm_disc_score_bwd over the hidden layers --, the Bilinear's gradients, and T = d loss /
+    d sigmoid(g_f), which it returns.  Leaves the per-node terms in s (disc_args)."""
+    ctx, spec, batch, st = s.ctx, s.spec, s.batch, s.st
+    L, N, B, H = spec.L, batch.N, batch.B, s.H
+    dD = dD.contiguous().view(-1)
+    U, c = ctx.U, ctx.c
+    dU = torch.empty_like(U)
+    s2sum = torch.empty(B, **s.f32)
+    dsum = torch.empty(B, **s.f32)
+    dbias = None
+    hold = ctx.disc_unit
+    if (hold is not None and hold.k is not None and hold.dD_ptr == dD.data_ptr()
+            and hold.dD_version == dD._version):      # (same tensor AND untouched since the loss wrote it)
+        # dD = k (sigmoid(d_logit) - target) came straight from the loss that recorded k: the reductions are k
+        # times what the forward left (DiscUnit) -- no second pass over the hidden layers
+        inv_perm = hold.inv_perm
+        # (the Bilinear bias gradient -- the total of dsum -- comes out of the same launch)
+        dbias = s.grads.out("disc.f_k.bias", s.P["disc.f_k.bias"])
+        check(lib.gnm_disc_unit_scale(hold.unit.data_ptr(), hold.unit.stride(0), L * H, hold.k.data_ptr(),
+                                      float(getattr(hold, "kscale", 1.0)), B,
+                                      dU.data_ptr(), dU.stride(0), s2sum.data_ptr(), dsum.data_ptr(),
+                                      dbias.data_ptr(), st),
+              "gnm_disc_unit_scale")
+    else:
+        inv_perm = torch.empty(B, dtype=torch.int32, device=U.device)      # inverse permutation, on the device
+        hp_, sp_, tp_, ldh_ = _hidden_ptr_arrays(ctx.hidden)
+        with _timed("disc_du", N=N, L=L, H=H):
+            check(lib.gnm_disc_score_bwd(hp_, sp_, tp_, ldh_, L, H, dD.data_ptr(),
+                                         ctx.perm_rows.data_ptr(), batch.node_off.data_ptr(), N, B,
+                                         dU.data_ptr(), dU.stride(0), s2sum.data_ptr(), dsum.data_ptr(),
+                                         inv_perm.data_ptr(), st), "gnm_disc_score_bwd")
+    if hold is not None:
+        hold.k = hold.dD_ptr = hold.dD_version = None
+    Wd = s.P["disc.f_k.weight"][0]
+    dWd = s.grads.out("disc.f_k.weight", s.P["disc.f_k.weight"])[0]       # ([0] of the Bilinear's 3-D parameter)
+    if not _small_gemm(dU, 1, c, 1, dWd, dU.shape[1], c.shape[1], B):          # dWd = dU^T c
+        torch.mm(dU.t(), c, out=dWd)
+    if dbias is None:
+        if s.grads.sink is not None:
+            torch.sum(dsum, 0, keepdim=True, out=s.grads.sink["disc.f_k.bias"])
+        else:
+            s.grads.put("disc.f_k.bias", dsum.sum().reshape(1))
+    T = torch.empty((B, Wd.shape[1]), **s.f32)
+    if not _small_gemm(dU, 0, Wd, 1, T, B, Wd.shape[1], Wd.shape[0]):            # d loss / d sigmoid(g_f) = dU Wd
+        T = dU @ Wd
+    s.dsc1, s.U, s.inv_perm, s.s2sum = dD, U, inv_perm, s2sum                 # first N entries of dD = d sc_1
+    return T
+
+
+def _head_backward(s, dC, T):
+    """Classifier head backward (graphcnn.py:224-231, :239): the classifier gradients and s.dph, d loss / d g_f through
+    both the classifier and the sigmoid (T, from _disc_backward) -- one launch, or torch for the forward's fallback."""
+    ctx, g_f, grads = s.ctx, s.ctx.g_f, s.grads
+    L, B, H = s.spec.L, s.batch.B, s.H
+    if ctx.fused_head and (dC is not None or T is not None):
+        wps = ctx.wps
+        Cn = wps[0].shape[0]
+        dCc = dC.contiguous() if dC is not None else torch.zeros((B, Cn), **s.f32)
+        dws = [grads.out(f"linears_prediction.{l}.weight", wps[l]) for l in range(L)]
+        dbs = [grads.out(f"linears_prediction.{l}.bias", wps[l][:, 0]) for l in range(L)]
+        dph_all = torch.empty((B, L * H), **s.f32)
+        check(lib.gnm_head_bwd(dCc.data_ptr(), dCc.stride(0), ptr(ctx.masks), g_f.data_ptr(), g_f.stride(0),
+                               ptr(ctx.c), ctx.c.stride(0) if ctx.c is not None else 0, ptr(T),
+                               T.stride(0) if T is not None else 0, B, L, H, Cn, _ptr_array(wps),
+                               _ptr_array(dws), _ptr_array(dbs), dph_all.data_ptr(), dph_all.stride(0), s.st),
+              "gnm_head_bwd")
+        s.dph = [dph_all[:, l * H:(l + 1) * H] for l in range(L)]
+    elif not ctx.fused_head:
+        dg_f = T * ctx.c * (1 - ctx.c) if T is not None else None                        # sigmoid backward
+        dph_all = None
+        G3 = g_f.view(B, L, H).transpose(0, 1)                                           # [L,B,H]
+        if dC is not None:
+            dlg = dC.unsqueeze(0).expand(L, -1, -1)
+            if ctx.masks is not None:
+                dlg = dlg * ctx.masks
+            dWp = torch.bmm(dlg.transpose(1, 2), G3)                                     # [L,C,H]
+            dbp = dlg.sum(1)                                                             # [L,C]
+            for l in range(L):
+                grads.put(f"linears_prediction.{l}.weight", dWp[l])
+                grads.put(f"linears_prediction.{l}.bias", dbp[l])
+            if dg_f is not None:
+                dph_all = torch.baddbmm(dg_f.view(B, L, H).transpose(0, 1), dlg, ctx.Wp)   # [L,B,H] contiguous
+            else:
+                dph_all = torch.bmm(dlg, ctx.Wp)
+        elif dg_f is not None:
+            dph_all = dg_f.view(B, L, H).transpose(0, 1).contiguous()
+        s.dph = [dph_all[l] if dph_all is not None else None for l in range(L)]
+
+
+def _bn_backward_coefs(s, sv, bn, sums, incoming, dp, disc_l):
+    """One train/eval BatchNorm + ReLU (mlp.py:48, graphcnn.py:163-166) up to its backward coefficients.  Unless the
+    kernel that produced the incoming gradient left `sums` (_BnSums), gnm_bn_relu_bwd_stats forms G = the gradient
+    (incoming + the readout's dp + layer disc_l's discriminator term) under the ReLU mask with its sums; then
+    gnm_bn_bwd_finalize: d gamma, d beta and dZ = cA (G - m1 - xhat m2).  Returns (G, (cA, m1, m2))."""
+    spec, batch, st = s.spec, s.batch, s.st
+    N, B, Hk = batch.N, batch.B, sv.H
+    if sums is not None:
+        G, part, nblk = sums
+    else:
+        G = torch.empty((N, Hk), **s.f32)
+        part = torch.empty((B, 2, Hk), dtype=torch.float64, device=G.device)
+        nblk = B
+        check(lib.gnm_bn_relu_bwd_stats(
+            ptr(incoming), incoming.stride(0) if incoming is not None else 0,
+            ptr(dp), dp.stride(0) if dp is not None else 0, int(spec.g_avg), *s.disc_args(disc_l),
+            sv.z.data_ptr(), sv.z.stride(0), sv.scale.data_ptr(), sv.shift.data_ptr(), sv.mean.data_ptr(),
+            sv.rstd.data_ptr(), 1, G.data_ptr(), G.stride(0), batch.node_off.data_ptr(), B, Hk,
+            part.data_ptr(), st), "gnm_bn_relu_bwd_stats")
+    gamma = s.P[bn + ".weight"]
+    dgamma, dbeta = s.grads.out(bn + ".weight", sv.scale), s.grads.out(bn + ".bias", sv.scale)
+    cA, m1, m2 = (torch.empty(Hk, **s.f32) for _ in range(3))
+    check(lib.gnm_bn_bwd_finalize(part.data_ptr(), nblk, Hk, N, gamma.data_ptr(), sv.rstd.data_ptr(),
+                                  int(s.ctx.training), dgamma.data_ptr(), dbeta.data_ptr(), cA.data_ptr(),
+                                  m1.data_ptr(), m2.data_ptr(), st), "gnm_bn_bwd_finalize")
+    if spec.sync_bn is not None and s.ctx.training:
+        # d gamma / d beta stay LOCAL sums (the gradient all-reduce averages them, as for every other
+        # parameter); the two means inside dZ = cA (G - m1 - xhat m2) are over the union batch
+        red = part.view(-1, 2, Hk)[:nblk].sum(0, keepdim=True)
+        spec.sync_bn.all_reduce(red)
+        scratch = torch.empty((2, Hk), **s.f32)
+        check(lib.gnm_bn_bwd_finalize(red.data_ptr(), 1, Hk, sv.Ng, gamma.data_ptr(), sv.rstd.data_ptr(), 1,
+                                      scratch[0].data_ptr(), scratch[1].data_ptr(), cA.data_ptr(), m1.data_ptr(),
+                                      m2.data_ptr(), st), "gnm_bn_bwd_finalize")
+    return G, (cA, m1, m2)
+
+
+def _agg_backward(s, l, dpooled):
+    """Layer l's aggregation backward (graphcnn.py:137-161, 173-182 under autograd): d h_{l-1} = A^T (dpooled [/deg]) +
+    (1 + eps) dpooled and the partials of d eps[l].  Over a lower layer the fused form also runs pass 1 of that layer's
+    outer BatchNorm backward; with no consumer of d h only the d-eps dot product runs.  Returns (d h or None, the
+    _BnSums the fused form left or None)."""
+    spec, batch, st = s.spec, s.batch, s.st
+    N, B = batch.N, batch.B
+    h_in, aux = s.ctx.saved[l].h_in, s.ctx.saved[l].aux
+    F_l = h_in.shape[1]
+    want_dh = l > 0 or s.need_dx
+    dh = torch.empty((N, F_l), **s.f32) if want_dh else None
+    part = s.eps_parts[l] if spec.learn_eps else None
+    eps_ptr = s.P["eps"].data_ptr() + 4 * l if spec.learn_eps else None
+    if l > 0 and want_dh and not spec.n_max:
+        lo = s.ctx.saved[l - 1].lins[-1]
+        dplo = s.dph[l - 1]
+        spart = torch.empty((B, 2, F_l), dtype=torch.float64, device=dh.device)
+        rc, cnt = agg_launch(batch, "bwd_stats", F_l, (
+            dpooled.data_ptr(), dpooled.stride(0), dh.data_ptr(), dh.stride(0), F_l, eps_ptr,
+            int(spec.n_avg), int(not spec.learn_eps),
+            None, 0,      # h_in is recomputed from lo.z in the epilogue (d eps)
+            ptr(part), lo.z.data_ptr(), lo.z.stride(0), lo.scale.data_ptr(), lo.shift.data_ptr(),
+            lo.mean.data_ptr(), lo.rstd.data_ptr(), ptr(dplo), dplo.stride(0) if dplo is not None else 0,
+            int(spec.g_avg), *s.disc_args(l - 1), spart.data_ptr()), spec, backward=True, stream=st)
+        if rc == 0:
+            if spec.learn_eps:
+                s.eps_counts[l] = cnt
+            return dh, _BnSums(dh, spart, B)
+    if dh is None:
+        # nothing below consumes d h: only d eps[l] = sum dpooled . h is needed -- a flat dot product
+        cnt = int(lib.gnm_rowdot_num_partials())
+        with _timed("deps_dot_F%d" % F_l, N=N, F=F_l):
+            hin_t = hidden_tensor(h_in)
+            check(lib.gnm_rowdot_partials(dpooled.data_ptr(), dpooled.stride(0), hin_t.data_ptr(),
+                                          hin_t.stride(0), N, F_l, part.data_ptr(), st),
+                  "gnm_rowdot_partials")
+    elif spec.n_max:
+        cnt = _max_bwd(batch, dpooled, dh, F_l, eps_ptr, aux, hidden_tensor(h_in) if spec.learn_eps else None, part)
+    else:
+        cnt = _agg(batch, dpooled, dh, F_l, eps_ptr, spec, backward=True,
+                   hfwd=hidden_tensor(h_in) if spec.learn_eps else None, deps_partial=part)
+    if spec.learn_eps:
+        s.eps_counts[l] = cnt
+    return dh, None
+
+
+def _reduce_deferred(s):
+    """The reductions nothing in the backward waits for, after its last kernel: the dW / db partials of the fused
+    Linear backwards (gnm_reduce_partials_multi, 32 jobs per launch) and the d eps partials (gnm_sum_partials_multi)."""
+    L, N = s.spec.L, s.batch.N
+    for j0 in range(0, len(s.jobs), 32):
+        jb = s.jobs[j0:j0 + 32]
+        nj = len(jb)
+        check(lib.gnm_reduce_partials_multi(
+            (C.c_void_p * nj)(*[j.ws.data_ptr() for j in jb]), (C.c_void_p * nj)(*[j.dW.data_ptr() for j in jb]),
+            (C.c_int * nj)(*[j.dW.stride(0) for j in jb]), (C.c_void_p * nj)(*[j.db.data_ptr() for j in jb]),
+            (C.c_int * nj)(*[j.H for j in jb]), (C.c_int * nj)(*[j.K for j in jb]), nj, N, s.st),
+            "gnm_reduce_partials_multi")
+    if s.spec.learn_eps:
+        # layers whose aggregation backward did not run (no incoming gradient) have count 0 -> d eps = 0
+        check(lib.gnm_sum_partials_multi(s.eps_parts.data_ptr(), s.eps_parts.stride(0), (C.c_int * L)(*s.eps_counts), L,
+                                         s.deps.data_ptr(), s.st), "gnm_sum_partials_multi")
+
+
 class GinInfoMaxFn(torch.autograd.Function):
     """(P0, X, *params) -> (c_logit [B,C], d_logit [2N,1], g_f [B,L*H])."""
 
@@ -834,94 +1208,20 @@ class GinInfoMaxFn(torch.autograd.Function):
 
     @staticmethod
     def _forward(ctx, spec, batch, perm, names, buffers, training, dropout_p, want_disc, P0, X, tensors):
-        P = dict(zip(names, tensors))
-        P.update(buffers)
-        L = spec.L
-        N, B = batch.N, batch.B
+        P = {**dict(zip(names, tensors)), **buffers}
         X = X.contiguous()
         hidden, g_f, saved = encoder_forward(spec, batch, X, P, training, update_running=training, P0=P0)
-        H = hidden[0].shape[1]
-        # classifier head (graphcnn.py:224-231) and sigmoid(g_f) (:239): one launch (csrc/head.hip)
-        wps = [P[f"linears_prediction.{l}.weight"] for l in range(L)]
-        bps = [P[f"linears_prediction.{l}.bias"] for l in range(L)]
-        Cn = wps[0].shape[0]
-        masks = None
-        if training and dropout_p > 0:
-            # (F.dropout of a cached tensor of ones: the fill it would otherwise need is a launch per step)
-            ones = getattr(spec, "_ones_mask", None)
-            if ones is None or ones.shape != (L, B, Cn) or ones.device != X.device:
-                ones = spec._ones_mask = torch.ones((L, B, Cn), dtype=torch.float32, device=X.device)
-            masks = F.dropout(ones, dropout_p, True)                                                      # :230
-        c_logit = torch.empty((B, Cn), dtype=torch.float32, device=X.device)
-        c = torch.empty_like(g_f) if want_disc else None
-        fused_head = all(w.is_contiguous() for w in wps) and all(b_.is_contiguous() for b_ in bps)
-        if fused_head:
-            rc = lib.gnm_head_fwd(g_f.data_ptr(), g_f.stride(0), B, L, H, Cn, _ptr_array(wps), _ptr_array(bps),
-                                  ptr(masks), c_logit.data_ptr(), c_logit.stride(0), ptr(c),
-                                  c.stride(0) if c is not None else 0, _stream())
-            if rc == -2:
-                fused_head = False
-            else:
-                check(rc, "gnm_head_fwd")
-        Wp = None
-        if not fused_head:          # shapes outside the head kernel (C > 256 classes): batched matrix products
-            Wp = torch.stack(wps)                                                            # [L,C,H]
-            G3 = g_f.view(B, L, H).transpose(0, 1)                                           # [L,B,H] view
-            lg = torch.baddbmm(torch.stack(bps).unsqueeze(1), G3, Wp.transpose(1, 2))        # [L,B,C]
-            if masks is not None:
-                lg = lg * masks
-            c_logit = lg.sum(0)
-            if want_disc:
-                c = torch.sigmoid(g_f)
-        d_logit = None
-        U = perm_rows = None
-        disc_unit = None
+        c_logit, c, masks, Wp, fused_head, wps = _head_forward(spec, P, g_f, hidden[0].shape[1], training, dropout_p,
+                                                               want_disc)
+        d_logit, U, perm_rows, disc_unit = torch.zeros((0, 1), dtype=torch.float32, device=X.device), None, None, None
         if want_disc:
-            if not batch.equal_n:
-                raise RuntimeError("Discriminator expands each graph summary N//B times (discriminator.py:24): "
-                                   "all graphs of a batch must have the same number of nodes")
-            Wd = P["disc.f_k.weight"][0]
-            LH = Wd.shape[1]
-            U = torch.empty((B, Wd.shape[0]), dtype=torch.float32, device=X.device)
-            if not _small_gemm(c, 0, Wd, 0, U, B, Wd.shape[0], LH):
-                U = c @ Wd.t()                                                # U[g] = W c_g
-            # row index = perm[g] (:198-201,242): validated on the host, pinned staging + async copy (a device tensor --
-            # a captured step's static buffer -- passes as it is: graph-capture safe)
-            perm_rows = perm_to_device(perm, B, X.device)
-            d_logit = torch.empty((2 * N, 1), dtype=torch.float32, device=X.device)
-            hp_, sp_, tp_, ldh_ = _hidden_ptr_arrays(hidden)
-            rc = -2
-            tm_ = _timed("disc_score", N=N, L=L, H=H)
-            tm_.__enter__()
-            if isinstance(want_disc, DiscUnit) and training:
-                # also leave the backward's per-graph reductions (up to the loss's scalar factor): see DiscUnit
-                ldunit = (L * H + 2 + 3) & ~3
-                unit = torch.empty((B, ldunit), dtype=torch.float32, device=X.device)
-                inv_perm = torch.empty(B, dtype=torch.int32, device=X.device)
-                rc = lib.gnm_disc_score_fwd_unit(hp_, sp_, tp_, ldh_, L, H, U.data_ptr(), U.stride(0),
-                                                 perm_rows.data_ptr(), P["disc.f_k.bias"].data_ptr(),
-                                                 batch.node_off.data_ptr(), N, B, d_logit.data_ptr(), unit.data_ptr(),
-                                                 ldunit, inv_perm.data_ptr(), _stream())
-                if rc == 0:
-                    want_disc.unit, want_disc.inv_perm = unit, inv_perm
-                    disc_unit = want_disc
-                elif rc != -2:
-                    check(rc, "gnm_disc_score_fwd_unit")
-            if rc == -2:
-                check(lib.gnm_disc_score_fwd(hp_, sp_, tp_, ldh_, L, H, U.data_ptr(), U.stride(0),
-                                             perm_rows.data_ptr(), P["disc.f_k.bias"].data_ptr(),
-                                             batch.node_off.data_ptr(), N, B, d_logit.data_ptr(), _stream()),
-                      "gnm_disc_score_fwd")
-            tm_.__exit__(None, None, None)
-        ctx.spec, ctx.batch, ctx.names, ctx.P = spec, batch, names, P
+            d_logit, U, perm_rows, disc_unit = _disc_forward(
+                spec, batch, P, hidden, c, perm, want_disc if training and isinstance(want_disc, DiscUnit) else None)
+        ctx.spec, ctx.batch, ctx.names, ctx.P, ctx.training, ctx.X = spec, batch, names, P, training, X
         ctx.hidden, ctx.saved, ctx.g_f, ctx.masks, ctx.Wp = hidden, saved, g_f, masks, Wp
         ctx.fused_head, ctx.wps = fused_head, wps
-        ctx.c, ctx.U, ctx.perm_rows, ctx.perm = c, U, perm_rows, perm
-        ctx.training, ctx.X = training, X
-        ctx.disc_unit = disc_unit
+        ctx.c, ctx.U, ctx.perm_rows, ctx.perm, ctx.disc_unit = c, U, perm_rows, perm, disc_unit
         ctx.mark_non_differentiable(g_f)
-        if d_logit is None:
-            d_logit = torch.zeros((0, 1), dtype=torch.float32, device=X.device)
         return c_logit, d_logit, g_f
 
     @staticmethod
@@ -931,323 +1231,36 @@ class GinInfoMaxFn(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, dC, dD):
-        spec, batch, P = ctx.spec, ctx.batch, ctx.P
-        L, m = spec.L, spec.m
-        N, B = batch.N, batch.B
-        hidden, saved, g_f = ctx.hidden, ctx.saved, ctx.g_f
-        H = hidden[0].shape[1]
-        dev = g_f.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        st = _stream()
-        grads = {}
-        need_dx = ctx.needs_input_grad[9]
-        sink = spec.grad_sink
-
-        def out_like(name, ref):
-            """tensor the kernel should write gradient `name` into"""
-            return sink[name] if sink is not None else torch.empty_like(ref)
-
-        def put(name, value):
-            """record a gradient computed by a torch op"""
-            if sink is not None:
-                sink[name].copy_(value.reshape(sink[name].shape))
-            else:
-                grads[name] = value
-
-        # ---- discriminator (discriminator.py:28-36) --------------------------------
-        dsc1 = U = inv_perm = s2sum = None
-        dg_f = T = None
-        if dD is not None and ctx.U is not None:
-            dD = dD.contiguous().view(-1)
-            U, c = ctx.U, ctx.c
-            dU = torch.empty_like(U)
-            s2sum = torch.empty(B, **f32)
-            dsum = torch.empty(B, **f32)
-            dbias = None
-            hold = ctx.disc_unit
-            if (hold is not None and hold.k is not None and hold.dD_ptr == dD.data_ptr()
-                    and hold.dD_version == dD._version):      # (same tensor AND untouched since the loss wrote it)
-                # dD = k (sigmoid(d_logit) - target) came straight from the loss that recorded k: the reductions are k
-                # times what the forward left (DiscUnit) -- no second pass over the hidden layers
-                inv_perm = hold.inv_perm
-                # (the Bilinear bias gradient -- the total of dsum -- comes out of the same launch)
-                dbias = sink["disc.f_k.bias"] if sink is not None else torch.empty(1, **f32)
-                check(lib.gnm_disc_unit_scale(hold.unit.data_ptr(), hold.unit.stride(0), L * H, hold.k.data_ptr(),
-                                              float(getattr(hold, "kscale", 1.0)), B,
-                                              dU.data_ptr(), dU.stride(0), s2sum.data_ptr(), dsum.data_ptr(),
-                                              dbias.data_ptr(), st),
-                      "gnm_disc_unit_scale")
-            else:
-                inv_perm = torch.empty(B, dtype=torch.int32, device=dev)      # inverse permutation, on the device
-                hp_, sp_, tp_, ldh_ = _hidden_ptr_arrays(hidden)
-                with _timed("disc_du", N=N, L=L, H=H):
-                    check(lib.gnm_disc_score_bwd(hp_, sp_, tp_, ldh_, L, H, dD.data_ptr(),
-                                                 ctx.perm_rows.data_ptr(), batch.node_off.data_ptr(), N, B,
-                                                 dU.data_ptr(), dU.stride(0), s2sum.data_ptr(), dsum.data_ptr(),
-                                                 inv_perm.data_ptr(), st), "gnm_disc_score_bwd")
-            if hold is not None:
-                hold.k = hold.dD_ptr = hold.dD_version = None
-            Wd = P["disc.f_k.weight"][0]
-            # (the three [B, L*H]-sized products of the tail: csrc/sgemm.hip -- one workgroup per 32 x 32 output tile, the
-            #  contraction split over its four waves, split-precision bf16 products.  A first hand-written version on the
-            #  fp32 matrix instruction measured 48 us per product against hipBLASLt's 9-12 us.)
-            Bc = dU.shape[0]
-            dWd = sink["disc.f_k.weight"][0] if sink is not None else torch.empty_like(Wd)
-            if not _small_gemm(dU, 1, c, 1, dWd, dU.shape[1], c.shape[1], Bc):          # dWd = dU^T c
-                torch.mm(dU.t(), c, out=dWd)
-            if sink is not None:
-                if dbias is None:
-                    torch.sum(dsum, 0, keepdim=True, out=sink["disc.f_k.bias"])
-            else:
-                grads["disc.f_k.weight"] = dWd.unsqueeze(0)
-                grads["disc.f_k.bias"] = dbias if dbias is not None else dsum.sum().reshape(1)
-            T = torch.empty((Bc, Wd.shape[1]), **f32)
-            if not _small_gemm(dU, 0, Wd, 1, T, Bc, Wd.shape[1], Wd.shape[0]):            # d loss / d sigmoid(g_f) = dU Wd
-                T = dU @ Wd
-            dsc1 = dD                                                         # first N entries = d sc_1
-
-        # ---- classifier head: d g_f (classifier + sigmoid paths) and the classifier gradients ------------
-        dph = [None] * L
-        if ctx.fused_head and (dC is not None or T is not None):
-            wps = ctx.wps
-            Cn = wps[0].shape[0]
-            dCc = dC.contiguous() if dC is not None else torch.zeros((B, Cn), **f32)
-            dws = [out_like(f"linears_prediction.{l}.weight", wps[l]) for l in range(L)]
-            dbs = [out_like(f"linears_prediction.{l}.bias", wps[l][:, 0]) for l in range(L)]
-            dph_all = torch.empty((B, L * H), **f32)
-            check(lib.gnm_head_bwd(dCc.data_ptr(), dCc.stride(0), ptr(ctx.masks), g_f.data_ptr(), g_f.stride(0),
-                                   ptr(ctx.c), ctx.c.stride(0) if ctx.c is not None else 0, ptr(T),
-                                   T.stride(0) if T is not None else 0, B, L, H, Cn, _ptr_array(wps),
-                                   _ptr_array(dws), _ptr_array(dbs), dph_all.data_ptr(), dph_all.stride(0), st),
-                  "gnm_head_bwd")
-            if sink is None:
-                for l in range(L):
-                    grads[f"linears_prediction.{l}.weight"] = dws[l]
-                    grads[f"linears_prediction.{l}.bias"] = dbs[l]
-            dph = [dph_all[:, l * H:(l + 1) * H] for l in range(L)]
-        elif not ctx.fused_head:
-            if T is not None:
-                dg_f = T * ctx.c * (1 - ctx.c)                                # sigmoid backward
-            dph_all = None
-            G3 = g_f.view(B, L, H).transpose(0, 1)                                           # [L,B,H]
-            if dC is not None:
-                dlg = dC.unsqueeze(0).expand(L, -1, -1)
-                if ctx.masks is not None:
-                    dlg = dlg * ctx.masks
-                dWp = torch.bmm(dlg.transpose(1, 2), G3)                                     # [L,C,H]
-                dbp = dlg.sum(1)                                                             # [L,C]
-                for l in range(L):
-                    put(f"linears_prediction.{l}.weight", dWp[l])
-                    put(f"linears_prediction.{l}.bias", dbp[l])
-                if dg_f is not None:
-                    dph_all = torch.baddbmm(dg_f.view(B, L, H).transpose(0, 1), dlg, ctx.Wp)   # [L,B,H] contiguous
-                else:
-                    dph_all = torch.bmm(dlg, ctx.Wp)
-            elif dg_f is not None:
-                dph_all = dg_f.view(B, L, H).transpose(0, 1).contiguous()
-            dph = [dph_all[l] if dph_all is not None else None for l in range(L)]
-
-        deps = eps_parts = None
-        eps_counts = [0] * L
+        s = _Backward(ctx)
+        spec, batch, P, grads = s.spec, s.batch, s.P, s.grads
+        L, m, N = spec.L, spec.m, batch.N
+        T = _disc_backward(s, dD) if dD is not None and ctx.U is not None else None
+        _head_backward(s, dC, T)
         if spec.learn_eps:
-            deps = sink["eps"] if sink is not None else torch.empty(L, **f32)
-            # fp64 partials of d eps[l] from the L aggregation backwards, summed by ONE launch at the end
-            eps_stride = max([agg_partials_capacity(batch, sv_[0].shape[1]) for sv_ in saved] +
+            s.deps = grads.out("eps", P["eps"])
+            eps_stride = max([agg_partials_capacity(batch, sv.h_in.shape[1]) for sv in ctx.saved] +
                              [int(lib.gnm_rowdot_num_partials())])
-            eps_parts = torch.empty((L, eps_stride), dtype=torch.float64, device=dev)
-        dH_next = None
-        dX = None
-        pre_outer = None
-        wjobs = []          # (workspace, dW, db, H, K) of the fused Linear backwards whose partial reduction is deferred
+            s.eps_parts = torch.empty((L, eps_stride), dtype=torch.float64, device=ctx.g_f.device)
+        dh = None           # the gradient arriving at the BatchNorm + ReLU in turn, from the layer or the Linear above ...
+        sums = None         # ... and that BatchNorm's _BnSums when the kernel that produced the gradient took them
         for l in reversed(range(L)):
-            h_in, pooled, lins, aux = saved[l]       # h_in: this layer's input (X, an array, or a ZAct)
-            F_l = h_in.shape[1]
-            incoming = dH_next                       # grad wrt this layer's output from the layer above
-            # (G, partial, nblk) when the producer of this gradient already applied the ReLU mask and reduced
-            # the BatchNorm-backward sums: the aggregation backward of the layer above (outer BatchNorm) or
-            # the fused backward of the Linear above (inner BatchNorms)
-            pre_stats, pre_outer = pre_outer, None
+            lins = ctx.saved[l].lins
             for k in reversed(range(m)):
-                sv = lins[k]
-                Hk, K = sv.H, sv.K
-                last = k == m - 1
+                sv, last = lins[k], k == m - 1
                 bn = f"batch_norms.{l}" if last else f"mlps.{l}.batch_norms.{k}"
-                dp = dph[l] if last else None
-                use_disc = last and dsc1 is not None
-                Ul = U[:, l * H:(l + 1) * H] if use_disc else None
-                if pre_stats is not None:
-                    G, part, nblk = pre_stats
-                    pre_stats = None
-                else:
-                    G = torch.empty((N, Hk), **f32)
-                    part = torch.empty((B, 2, Hk), dtype=torch.float64, device=dev)
-                    nblk = B
-                    check(lib.gnm_bn_relu_bwd_stats(
-                        ptr(incoming), incoming.stride(0) if incoming is not None else 0,
-                        ptr(dp), dp.stride(0) if dp is not None else 0, int(spec.g_avg),
-                        ptr(dsc1) if use_disc else None, ptr(Ul), U.stride(0) if use_disc else 0,
-                        ptr(inv_perm) if use_disc else None, ptr(s2sum) if use_disc else None,
-                        sv.z.data_ptr(), sv.z.stride(0), sv.scale.data_ptr(), sv.shift.data_ptr(), sv.mean.data_ptr(),
-                        sv.rstd.data_ptr(), 1, G.data_ptr(), G.stride(0), batch.node_off.data_ptr(), B, Hk,
-                        part.data_ptr(), st), "gnm_bn_relu_bwd_stats")
-                dgamma, dbeta = out_like(bn + ".weight", sv.scale), out_like(bn + ".bias", sv.scale)
-                cA, m1, m2 = (torch.empty(Hk, **f32) for _ in range(3))
-                check(lib.gnm_bn_bwd_finalize(part.data_ptr(), nblk, Hk, N, P[bn + ".weight"].data_ptr(),
-                                              sv.rstd.data_ptr(), int(ctx.training), dgamma.data_ptr(),
-                                              dbeta.data_ptr(), cA.data_ptr(), m1.data_ptr(), m2.data_ptr(), st),
-                      "gnm_bn_bwd_finalize")
-                if spec.sync_bn is not None and ctx.training:
-                    # d gamma / d beta stay LOCAL sums (the gradient all-reduce averages them, as for every other
-                    # parameter); the two means inside dZ = cA (G - m1 - xhat m2) are over the union batch
-                    red = part.view(-1, 2, Hk)[:nblk].sum(0, keepdim=True)
-                    spec.sync_bn.all_reduce(red)
-                    scratch = torch.empty((2, Hk), **f32)
-                    check(lib.gnm_bn_bwd_finalize(red.data_ptr(), 1, Hk, sv.Ng, P[bn + ".weight"].data_ptr(),
-                                                  sv.rstd.data_ptr(), 1, scratch[0].data_ptr(),
-                                                  scratch[1].data_ptr(), cA.data_ptr(), m1.data_ptr(),
-                                                  m2.data_ptr(), st), "gnm_bn_bwd_finalize")
-                if sink is None:
-                    grads[bn + ".weight"], grads[bn + ".bias"] = dgamma, dbeta
+                G, coef = _bn_backward_coefs(s, sv, bn, sums, dh, s.dph[l] if last else None, l if last else None)
                 wname = f"mlps.{l}.linear" if m == 1 else f"mlps.{l}.linears.{k}"
                 W = P[wname + ".weight"]
-                dW = out_like(wname + ".weight", W)
-                db = out_like(wname + ".bias", sv.scale)
+                dW, db = grads.out(wname + ".weight", W), grads.out(wname + ".bias", sv.scale)
                 # dX of this Linear: always for inner Linears; for the first one only when the
                 # aggregation backward below has a consumer (a lower layer, dX, or d eps[l])
-                need_dA = k > 0 or l > 0 or need_dx or spec.learn_eps
-                dA = torch.empty((N, K), **f32) if need_dA else None
-                # one fused pass (BatchNorm-backward apply + dX + dW + db) when the shape is eligible
-                ws = torch.empty(int(lib.gnm_linear_bwd_workspace_floats(N, Hk, K)), **f32)
-                # if a BatchNorm+ReLU feeds this Linear (k > 0), let the same pass mask dX with that ReLU and
-                # reduce that BatchNorm's backward sums (replaces its gnm_bn_relu_bwd_stats launch)
-                lo = lins[k - 1] if k > 0 else None
-                lo_part = None
-                if lo is not None and need_dA:
-                    lo_part = torch.empty((lib.gnm_linear_bwd_grid(N), 2, K), dtype=torch.float64, device=dev)
-                with _timed("linbwd_K%d_H%d" % (K, Hk), N=N, K=K, H=Hk) as tm:
-                    # every argument after Z (dW = NULL: the partials are reduced by ONE launch after the loop)
-                    args = (sv.mean.data_ptr(), sv.rstd.data_ptr(), cA.data_ptr(), m1.data_ptr(), m2.data_ptr(),
-                            sv.x_in.data_ptr(), sv.x_in.stride(0), ptr(sv.pro[0]) if sv.pro else None,
-                            ptr(sv.pro[1]) if sv.pro else None, 1 if sv.pro else 0, W.data_ptr(), W.stride(0), ptr(dA),
-                            dA.stride(0) if need_dA else 0, None, dW.stride(0), db.data_ptr(), ws.data_ptr(), N, K, Hk,
-                            lo.z.data_ptr() if lo_part is not None else None,
-                            lo.z.stride(0) if lo_part is not None else 0,
-                            lo.scale.data_ptr() if lo_part is not None else None,
-                            lo.shift.data_ptr() if lo_part is not None else None,
-                            lo.mean.data_ptr() if lo_part is not None else None,
-                            lo.rstd.data_ptr() if lo_part is not None else None, ptr(lo_part), st)
-                    rc = -2
-                    if Hk == 64 and lo_part is None and ((K == 64 and need_dA) or (K <= 16 and not sv.pro)):
-                        # sv.z = Linear(sv.x_in) as gnm_linear_fwd left it: the pass recomputes it instead of reading it
-                        rc = lib.gnm_linear_bwd_fused_rz(G.data_ptr(), G.stride(0), P[wname + ".bias"].data_ptr(), *args)
-                    if rc == -2:
-                        rc = lib.gnm_linear_bwd_fused(G.data_ptr(), G.stride(0), sv.z.data_ptr(), sv.z.stride(0), *args)
-                    if rc != 0:
-                        tm.cancel()
-                if rc == 0:
-                    wjobs.append((ws, dW, db, Hk, K))       # its dW / db partials: one reduction launch after the loop
-                if rc == 0 and lo_part is not None:
-                    pre_stats = (dA, lo_part, lo_part.shape[0])
-                if rc == -2:        # GNM_ERR_UNSUPPORTED: generic three-kernel path
-                    check(lib.gnm_bn_bwd_apply(G.data_ptr(), G.stride(0), sv.z.data_ptr(), sv.z.stride(0),
-                                               sv.mean.data_ptr(), sv.rstd.data_ptr(), cA.data_ptr(), m1.data_ptr(),
-                                               m2.data_ptr(), G.data_ptr(), G.stride(0), N, Hk, st),
-                          "gnm_bn_bwd_apply")
-                    dZ = G
-                    ws = torch.empty(int(lib.gnm_wgrad_workspace_floats(N, Hk, K)), **f32)
-                    with _timed("wgrad_K%d_H%d" % (K, Hk), N=N, K=K, H=Hk):
-                        check(lib.gnm_linear_wgrad(dZ.data_ptr(), dZ.stride(0), sv.x_in.data_ptr(),
-                                                   sv.x_in.stride(0), N, Hk, K, ptr(sv.pro[0]) if sv.pro else None,
-                                                   ptr(sv.pro[1]) if sv.pro else None, 1 if sv.pro else 0,
-                                                   dW.data_ptr(), dW.stride(0), db.data_ptr(), ws.data_ptr(), st),
-                              "gnm_linear_wgrad")
-                    if need_dA:
-                        rc2 = -2
-                        if lo is not None and K == 128 and Hk == 128:
-                            # dX = dZ W with the ReLU mask of the BatchNorm + ReLU below and that BatchNorm's backward
-                            # sums taken in the epilogue (replaces its gnm_bn_relu_bwd_stats pass)
-                            lo_part = torch.empty((int(lib.gnm_linear_grid(N)), 2, K), dtype=torch.float64, device=dev)
-                            rc2 = lib.gnm_linear_dgrad_masked(
-                                dZ.data_ptr(), dZ.stride(0), W.data_ptr(), W.stride(0), dA.data_ptr(), dA.stride(0), N, K,
-                                Hk, lo.z.data_ptr(), lo.z.stride(0), lo.scale.data_ptr(), lo.shift.data_ptr(),
-                                lo.mean.data_ptr(), lo.rstd.data_ptr(), lo_part.data_ptr(), st)
-                            if rc2 == 0:
-                                pre_stats = (dA, lo_part, lo_part.shape[0])
-                            elif rc2 != -2:
-                                check(rc2, "gnm_linear_dgrad_masked")
-                        if rc2 == -2:
-                            _linear_wide(dZ, W, 1, None, dA, N, Hk, K, None, None)      # dX = dZ W
-                else:
-                    check(rc, "gnm_linear_bwd_fused")
-                if sink is None:
-                    grads[wname + ".weight"], grads[wname + ".bias"] = dW, db
-                incoming = dA
-            # aggregation backward: d h_{l-1} = A^T (dpooled [/deg]) + (1+eps) dpooled ; d eps[l]
-            if incoming is not None:
-                dpooled = incoming
-                want_dh = l > 0 or need_dx
-                dh = torch.empty((N, F_l), **f32) if want_dh else None
-                part = eps_parts[l] if spec.learn_eps else None
-                eps_ptr = P["eps"].data_ptr() + 4 * l if spec.learn_eps else None
-                fused = False
-                if l > 0 and want_dh and not spec.n_max:
-                    # also do the layer below's outer-BatchNorm backward pass 1 in the same kernel
-                    lo = saved[l - 1][2][-1]
-                    use_disc = dsc1 is not None
-                    Ulo = U[:, (l - 1) * H:l * H] if use_disc else None
-                    dplo = dph[l - 1]
-                    spart = torch.empty((B, 2, F_l), dtype=torch.float64, device=dev)
-                    rc, cnt = agg_launch(batch, "bwd_stats", F_l, (
-                        dpooled.data_ptr(), dpooled.stride(0), dh.data_ptr(), dh.stride(0), F_l, eps_ptr,
-                        int(spec.n_avg), int(not spec.learn_eps),
-                        None, 0,      # h_in is recomputed from lo.z in the epilogue (d eps)
-                        ptr(part), lo.z.data_ptr(), lo.z.stride(0), lo.scale.data_ptr(), lo.shift.data_ptr(),
-                        lo.mean.data_ptr(), lo.rstd.data_ptr(), ptr(dplo), dplo.stride(0) if dplo is not None else 0,
-                        int(spec.g_avg), ptr(dsc1) if use_disc else None, ptr(Ulo), U.stride(0) if use_disc else 0,
-                        ptr(inv_perm) if use_disc else None, ptr(s2sum) if use_disc else None, spart.data_ptr()),
-                        spec, backward=True, stream=st)
-                    if rc == 0:
-                        fused = True
-                        pre_outer = (dh, spart, B)
-                        if spec.learn_eps:
-                            eps_counts[l] = cnt
-                if not fused and dh is None:
-                    # nothing below consumes d h: only d eps[l] = sum dpooled . h is needed -- a flat dot product
-                    eps_counts[l] = int(lib.gnm_rowdot_num_partials())
-                    with _timed("deps_dot_F%d" % F_l, N=N, F=F_l):
-                        hin_t = hidden_tensor(h_in)
-                        check(lib.gnm_rowdot_partials(dpooled.data_ptr(), dpooled.stride(0), hin_t.data_ptr(),
-                                                      hin_t.stride(0), N, F_l, part.data_ptr(), st),
-                              "gnm_rowdot_partials")
-                elif spec.n_max:
-                    cnt = _max_bwd(batch, dpooled, dh, F_l, eps_ptr, aux,
-                                   hidden_tensor(h_in) if spec.learn_eps else None, part)
-                    if spec.learn_eps:
-                        eps_counts[l] = cnt
-                elif not fused:
-                    cnt = _agg(batch, dpooled, dh, F_l, eps_ptr, spec, backward=True,
-                               hfwd=hidden_tensor(h_in) if spec.learn_eps else None, deps_partial=part)
-                    if spec.learn_eps:
-                        eps_counts[l] = cnt
-                if l > 0:
-                    dH_next = dh
-                else:
-                    dX = dh
-        for j0 in range(0, len(wjobs), 32):
-            jb = wjobs[j0:j0 + 32]
-            nj = len(jb)
-            check(lib.gnm_reduce_partials_multi(
-                (C.c_void_p * nj)(*[j[0].data_ptr() for j in jb]), (C.c_void_p * nj)(*[j[1].data_ptr() for j in jb]),
-                (C.c_int * nj)(*[j[1].stride(0) for j in jb]), (C.c_void_p * nj)(*[j[2].data_ptr() for j in jb]),
-                (C.c_int * nj)(*[j[3] for j in jb]), (C.c_int * nj)(*[j[4] for j in jb]), nj, N, st),
-                "gnm_reduce_partials_multi")
-        if spec.learn_eps:
-            # layers whose aggregation backward did not run (no incoming gradient) have count 0 -> d eps = 0
-            check(lib.gnm_sum_partials_multi(eps_parts.data_ptr(), eps_parts.stride(0), (C.c_int * L)(*eps_counts), L,
-                                             deps.data_ptr(), st), "gnm_sum_partials_multi")
-            if sink is None:
-                grads["eps"] = deps
-        out = [None] * 9 + [dX if need_dx else None]
-        for i, name in enumerate(ctx.names):
-            out.append(grads.get(name) if ctx.needs_input_grad[10 + i] else None)
-        return tuple(out)
+                need_dA = k > 0 or l > 0 or s.need_dx or spec.learn_eps
+                r = linear_bwd_launch(sv, lins[k - 1] if k > 0 else None, G, coef, W, P[wname + ".bias"], dW, db,
+                                      need_dA, N, s.st)
+                if r.job is not None:
+                    s.jobs.append(r.job)
+                dh, sums = r.dA, r.lo_sums
+            if dh is not None:
+                dh, sums = _agg_backward(s, l, dh)
+        _reduce_deferred(s)
+        return (None,) * 9 + (dh if s.need_dx else None,) + grads.result(ctx.names, ctx.needs_input_grad[10:])

@@ -423,3 +423,187 @@ def test_aggregation_routing_table(monkeypatch, dense, iso, F):
                         assert calls == want_calls, what
                         assert [(r[0], r[1]) for r in timer.records] == \
                             ([(tag, rec)] if rec is not None and tag is not None else []), what
+
+
+_LINBWD_SPIES = ("gnm_linear_bwd_fused_rz", "gnm_linear_bwd_fused", "gnm_bn_bwd_apply", "gnm_linear_wgrad",
+                 "gnm_linear_dgrad_masked", "gnm_linear_fwd")
+
+
+def _fake_lin_save(core, N, K, H, pro):
+    """a Linear [K -> H] as encoder_forward saves it, on CPU tensors"""
+    sv = core._LinSave()
+    sv.x_in, sv.z, sv.K, sv.H, sv.Ng = torch.zeros(N, K), torch.zeros(N, H), K, H, N
+    sv.pro = (torch.zeros(K), torch.zeros(K)) if pro else None
+    sv.scale, sv.shift, sv.mean, sv.rstd = (torch.zeros(H) for _ in range(4))
+    return sv
+
+
+@pytest.mark.parametrize("K,H", ((7, 64), (16, 64), (64, 64), (32, 64), (64, 32), (128, 128), (400, 64)))
+@pytest.mark.parametrize("pro", (False, True))
+@pytest.mark.parametrize("below", (False, True))
+@pytest.mark.parametrize("need_dA", (False, True))
+def test_linear_backward_routing_table(monkeypatch, K, H, pro, below, need_dA):
+    """core.linear_bwd_launch, the one place that routes a Linear's backward, against the rules the training step
+    applied inline before it:
+      * gnm_linear_bwd_fused_rz is asked only when H = 64, no lower-BatchNorm sums are wanted, and K = 64 with dA or
+        K <= 16 without a prologue; after its decline, or straight away, gnm_linear_bwd_fused with the stored Z; both
+        with dW = NULL and a workspace of gnm_linear_bwd_workspace_floats, their dW / db reduction deferred;
+      * the lower BatchNorm's sums ride on those entries when there is a Linear below and dA is wanted, in
+        gnm_linear_bwd_grid(N) rows;
+      * after -2 from the last of them: gnm_bn_bwd_apply in place, gnm_linear_wgrad with its own workspace, and for dA
+        gnm_linear_dgrad_masked (K = H = 128 over a Linear below; gnm_linear_grid(N) rows) or, after its decline, the
+        k-major gnm_linear_fwd in column windows of 128;
+      * one linbwd_K<K>_H<H> record only when a fused entry ran, wgrad_K<K>_H<H> and lin_dgrad_K<H>_H<window> records
+        for the kernels of the generic path; any other status raises under gnm_linear_bwd_fused /
+        gnm_linear_dgrad_masked.
+    The entries are spies returning programmed statuses; every tensor the function allocates is caught in order."""
+    from gnm import core
+    from gnm._cabi import SIGNATURES, GnmError
+    monkeypatch.setattr(core, "_new_event", _FakeEvent)
+    monkeypatch.setattr(core, "_STREAM", _STREAM)
+    status, calls, allocs = dict.fromkeys(_LINBWD_SPIES, 0), [], []
+
+    def spy(name):
+        def call(*argv):
+            calls.append((name, argv))
+            return status[name]
+        return call
+    for name in _LINBWD_SPIES:
+        monkeypatch.setattr(core.lib, name, spy(name), raising=False)
+    real_empty = torch.empty
+
+    def empty(*a, **k):
+        allocs.append(real_empty(*a, **k))
+        return allocs[-1]
+
+    N = 100
+    lib = core.lib
+    sv = _fake_lin_save(core, N, K, H, pro)
+    lo = _fake_lin_save(core, N, 5, K, False) if below else None
+    G, W, bias, dW, db = torch.zeros(N, H), torch.zeros(H, K), torch.zeros(H), torch.zeros(H, K), torch.zeros(H)
+    cA, m1, m2 = (torch.zeros(H) for _ in range(3))
+    p = lambda t: t.data_ptr()      # noqa: E731
+    pro_args = (p(sv.pro[0]), p(sv.pro[1]), 1) if pro else (None, None, 0)
+    lo_args = (p(lo.z), K, p(lo.scale), p(lo.shift), p(lo.mean), p(lo.rstd)) if below else None
+    shape = {"N": N, "K": K, "H": H}
+    monkeypatch.setattr(torch, "empty", empty)
+    for rc_rz in (0, -2, -1):
+        for rc_f in (0, -2, -1):
+            for rc_m in (0, -2, -1):
+                what = (rc_rz, rc_f, rc_m)
+                status.update(gnm_linear_bwd_fused_rz=rc_rz, gnm_linear_bwd_fused=rc_f, gnm_linear_dgrad_masked=rc_m)
+                calls.clear()
+                allocs.clear()
+                timer = core.KernelTimer()
+                monkeypatch.setattr(core, "TIMER", timer)
+                raises, got = None, None
+                try:
+                    got = core.linear_bwd_launch(sv, lo, G, (cA, m1, m2), W, bias, dW, db, need_dA, N, _STREAM)
+                except GnmError as e:
+                    raises = str(e).split(" failed")[0]
+                for name, argv in calls:
+                    assert len(argv) == len(SIGNATURES[name][1]), (name, what)
+                # ---- what the rules above give ----
+                a = iter(allocs)
+                dA = next(a) if need_dA else None
+                ws = next(a)
+                assert ws.shape == (lib.gnm_linear_bwd_workspace_floats(N, H, K),) and ws.dtype == torch.float32
+                sums = next(a) if below and need_dA else None
+                if sums is not None:
+                    assert sums.shape == (lib.gnm_linear_bwd_grid(N), 2, K) and sums.dtype == torch.float64
+                if need_dA:
+                    assert dA.shape == (N, K) and dA.dtype == torch.float32
+                rest = (p(sv.mean), p(sv.rstd), p(cA), p(m1), p(m2), p(sv.x_in), K) + pro_args + (
+                    p(W), K, p(dA) if need_dA else None, K if need_dA else 0, None, K, p(db), p(ws), N, K, H) + (
+                    lo_args if sums is not None else (None, 0, None, None, None, None)) + (
+                    p(sums) if sums is not None else None, _STREAM)
+                want_calls, want_rec, want_raise, want = [], [], None, None
+                rc = -2
+                if H == 64 and sums is None and ((K == 64 and need_dA) or (K <= 16 and not pro)):
+                    want_calls.append(("gnm_linear_bwd_fused_rz", (p(G), H, p(bias)) + rest))
+                    rc = rc_rz
+                if rc == -2:
+                    want_calls.append(("gnm_linear_bwd_fused", (p(G), H, p(sv.z), H) + rest))
+                    rc = rc_f
+                if rc == 0:
+                    want_rec.append(("linbwd_K%d_H%d" % (K, H), shape))
+                    want = (dA, sums, lib.gnm_linear_bwd_grid(N), (ws, dW, db, H, K))
+                elif rc == -1:
+                    want_raise = "gnm_linear_bwd_fused"
+                else:
+                    want_calls.append(("gnm_bn_bwd_apply", (p(G), H, p(sv.z), H, p(sv.mean), p(sv.rstd), p(cA), p(m1),
+                                                            p(m2), p(G), H, N, H, _STREAM)))
+                    ws2 = next(a)
+                    assert ws2.shape == (lib.gnm_wgrad_workspace_floats(N, H, K),) and ws2.dtype == torch.float32
+                    want_calls.append(("gnm_linear_wgrad", (p(G), H, p(sv.x_in), K, N, H, K) + pro_args + (
+                        p(dW), K, p(db), p(ws2), _STREAM)))
+                    want_rec.append(("wgrad_K%d_H%d" % (K, H), shape))
+                    sums2, rc2 = None, -2
+                    if need_dA and below and K == 128 and H == 128:
+                        sums2 = next(a)
+                        assert sums2.shape == (lib.gnm_linear_grid(N), 2, K) and sums2.dtype == torch.float64
+                        want_calls.append(("gnm_linear_dgrad_masked", (p(G), H, p(W), K, p(dA), K, N, K, H) + lo_args + (
+                            p(sums2), _STREAM)))
+                        rc2 = rc_m
+                    if rc2 == -1:
+                        want_raise = "gnm_linear_dgrad_masked"
+                    elif need_dA and rc2 == -2:
+                        for k0 in range(0, K, 128):           # dX = dZ W: the weight k-major, 128 columns at a time
+                            kw = min(128, K - k0)
+                            want_calls.append(("gnm_linear_fwd", (p(G), H, p(W) + 4 * k0, K, 1, None, p(dA) + 4 * k0, K,
+                                                                  N, H, kw, None, None, 0, None, _STREAM)))
+                            want_rec.append(("lin_dgrad_K%d_H%d" % (H, kw), {"N": N, "K": H, "H": kw}))
+                    if want_raise is None:
+                        want = (dA, sums2 if rc2 == 0 else None, lib.gnm_linear_grid(N), None)
+                assert next(a, None) is None, what           # nothing else was allocated
+                assert calls == want_calls, what
+                assert [(r[0], r[1]) for r in timer.records] == want_rec, what
+                assert raises == want_raise, what
+                if want is not None:
+                    w_dA, w_sums, w_rows, w_job = want
+                    assert got.dA is w_dA, what
+                    if w_sums is None:
+                        assert got.lo_sums is None, what
+                    else:
+                        assert got.lo_sums.G is w_dA and got.lo_sums.part is w_sums and got.lo_sums.rows == w_rows, what
+                    if w_job is None:
+                        assert got.job is None, what
+                    else:
+                        assert all(x is y for x, y in zip(got.job[:3], w_job[:3])) and tuple(got.job[3:]) == w_job[3:], what
+                        assert (got.job.ws, got.job.dW, got.job.db, got.job.H, got.job.K) == tuple(got.job), what
+
+
+def test_gradient_collector():
+    """core._Grads, where the backward's kernels and torch ops leave the parameter gradients: with a sink
+    (GinSpec.grad_sink) they go into its tensors and autograd gets None for every parameter; without one they are
+    fresh tensors; needs_input_grad masks both."""
+    from gnm import core
+    like = {"a": torch.zeros(3, 2), "b": torch.zeros(4), "c": torch.zeros(1, 2, 2)}
+    names, needs = ("a", "b", "c", "d"), (True, False, True, True)
+
+    def fill(g):
+        """as a backward does: a kernel writes into out(), a torch result is put(), `c` is written as [0] of a 3-D one"""
+        a = g.out("a", like["a"])
+        a.copy_(torch.arange(6.).view(3, 2))
+        g.put("b", torch.arange(4.) + 10)
+        g.out("c", like["c"])[0].copy_(torch.eye(2))
+        return a
+
+    sink = {k: torch.full_like(v, -1.0) for k, v in like.items()}
+    g = core._Grads(sink)
+    assert fill(g) is sink["a"]
+    assert g.result(names, needs) == (None, None, None, None)
+    assert torch.equal(sink["a"], torch.arange(6.).view(3, 2)) and torch.equal(sink["b"], torch.arange(4.) + 10)
+    assert torch.equal(sink["c"], torch.eye(2).unsqueeze(0))
+    g.put("a", torch.ones(6))                       # a torch result of another shape is reshaped into the sink's tensor
+    assert torch.equal(sink["a"], torch.ones(3, 2))
+
+    g = core._Grads(None)
+    t = fill(g)
+    assert t is not like["a"] and t.shape == like["a"].shape and t.dtype == like["a"].dtype
+    res = g.result(names, needs)
+    assert res[0] is t and torch.equal(res[0], torch.arange(6.).view(3, 2))
+    assert res[1] is None                           # computed, but not asked for
+    assert res[2].shape == (1, 2, 2) and torch.equal(res[2][0], torch.eye(2))
+    assert res[3] is None                           # asked for, never produced
+    assert g.result(names, (True,) * 4)[1] is not None
