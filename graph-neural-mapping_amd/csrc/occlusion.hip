@@ -1,0 +1,420 @@
+// Per-ROI occlusion (virtual lesioning): the eval-mode class scores of every node-deleted copy G \ v of every graph of a
+// batch (GIN_InfoMaxReg.occlusion(); the reference's forward in eval(), graphcnn.py:194-231, on a graph with node v, its
+// edges in both directions and its feature row removed), without building a single copy.
+//
+// A VIRTUAL graph is (source graph g, deleted node v): it reads g's bit rows, rowptr and node_off and owns n_g rows of
+// two ping-pong activation arrays.  Virtual graph q of a batch is node q of the batch (v = q - node_off[g]), so there
+// are N of them.  Deleting v is three things in csrc/evallayer.hip's layer (whose structure this file keeps: bits as
+// the B operand of the aggregation, three exact bf16 planes of the activations, six-term split Linears from the LDS
+// tile, folded BatchNorm, the NaN-propagating ReLU):
+//   * row v of every layer's output is written as ZEROS, so the next layer's product A h drops column v by itself;
+//   * row v is left out of the graph readout (which then runs over n - 1 nodes);
+//   * a row's degree under neighbour "average" is its rowptr degree minus bit (r, v).
+// Layer 0 never multiplies by the features: they are shared by the n virtual graphs of a source graph and the first
+// Linear is linear, so the caller forms XW = X W0^T and S = (A + I) XW once per SOURCE graph (gnm_linear_fwd, gnm_agg /
+// gnm_aggm at width H -- any input width) and the first pre-activation of row r != v of (g, v) is
+//     self loops:   (S[r] - a_rv XW[v]) [/ (deg_r + 1 - a_rv)] + b
+//     learned eps:  (S[r] - a_rv XW[v]) + eps0 XW[r] + b                              (sum)
+//                   (S[r] - XW[r] - a_rv XW[v]) / (deg_r - a_rv) + (1 + eps0) XW[r] + b   (average; 0/0 -> NaN as in
+//                                                                                        the reference: a leaf of v)
+// One launch per layer over (virtual graph, 32-row block), then a launch that adds the readout shares in fixed order,
+// scales by the fp32 1/(n - 1) under graph "average" and applies the classifier head.  No float atomics; every sum has
+// a fixed order, so results are bitwise reproducible and do not depend on how the caller chunks the graphs.
+#include "gnm_common.h"
+#include <string.h>
+
+typedef __bf16 oc_bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int oc_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int oc_u32x2 __attribute__((ext_vector_type(2)));
+
+static constexpr int kOcMaxN = 416;               // 13 row blocks, 26 steps (csrc/evallayer.hip)
+static constexpr int kOcMaxH = 128;
+static constexpr int kOcLinWords = 7;             // the parameter table of evalfwd.hip (gnm_eval_table_words)
+static constexpr int kOcTS = kOcMaxH + 4;         // row stride of the LDS tiles (floats)
+static constexpr int kOcMaxClasses = 8;           // classes per finish launch
+
+struct OcArgs {
+    const uint32_t* adj_bits; const int64_t* b_bits_off; const int32_t* node_off;
+    const int32_t* rowptr; const int64_t* b_rp_off;
+    const int32_t* vgraph;                        // [V]: source graph of virtual graph q
+    const int64_t* vrow_off;                      // [B]: first activation row of graph g's virtual graphs (sum of n^2 before g)
+    const float* XW; int ldxw;                    // layer 0: X W0^T and (A + I) X W0^T of the SOURCE graphs, [N, H]
+    const float* S; int lds;
+    const float* Hin;                             // layers >= 1: [rows, H]
+    int V, wmax, L, m, l, H;
+    int average, self_loop;
+    float bn_eps;
+    const float* eps;                             // [L] on the device, or null (learn_eps False)
+    const long long* table;
+    float* Hout;                                  // [rows, H]
+    float* rpart;                                 // [V][wmax][H]: this layer's readout shares
+};
+
+__device__ __forceinline__ void oc_split8(const float* f, oc_bf16x8& p1, oc_bf16x8& p2, oc_bf16x8& p3) {
+    unsigned a1[8], a2[8], a3[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        a1[j] = __float_as_uint(f[j]) & 0xFFFF0000u;
+        const float r1 = f[j] - __uint_as_float(a1[j]);
+        a2[j] = __float_as_uint(r1) & 0xFFFF0000u;
+        a3[j] = __float_as_uint(r1 - __uint_as_float(a2[j]));
+    }
+    oc_u32x4 q1, q2, q3;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        q1[j] = __builtin_amdgcn_perm(a1[2 * j + 1], a1[2 * j], 0x07060302u);
+        q2[j] = __builtin_amdgcn_perm(a2[2 * j + 1], a2[2 * j], 0x07060302u);
+        q3[j] = __builtin_amdgcn_perm(a3[2 * j + 1], a3[2 * j], 0x07060302u);
+    }
+    p1 = __builtin_bit_cast(oc_bf16x8, q1); p2 = __builtin_bit_cast(oc_bf16x8, q2); p3 = __builtin_bit_cast(oc_bf16x8, q3);
+}
+
+// FIRST: layer 0 (the first pre-activation from XW and S, see the file header; no product with the adjacency and no
+// first Linear); otherwise a layer >= 1 on the virtual graph's own activations (input width H).
+template <bool FIRST>
+__global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p) {
+    __shared__ __attribute__((aligned(16))) float T0[32 * kOcTS];
+    __shared__ __attribute__((aligned(16))) float T1[32 * kOcTS];
+    __shared__ __attribute__((aligned(16))) float part[4][32][33];
+    __shared__ __attribute__((aligned(16))) char lut[128];
+    __shared__ unsigned bitsw[8][256];            // word j of thread t's half row of the block's adjacency bits
+    __shared__ float aff[3][3][kOcMaxH];          // per Linear of the MLP: bias, scale, shift (the BatchNorm behind it, folded)
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 31, h = lane >> 5;
+    const int q = blockIdx.x / p.wmax, rb = blockIdx.x - q * p.wmax;
+    const int b = p.vgraph[q];
+    const int node0 = p.node_off[b];
+    const int n = p.node_off[b + 1] - node0;
+    const int v = q - node0;                                      // the deleted node
+    const int W = (n + 31) >> 5;
+    if (rb >= W) return;
+    const size_t row0 = (size_t)p.vrow_off[b] + (size_t)v * n;    // the virtual graph's rows of Hin / Hout
+    const int H = p.H;
+    const int HPW = (((W + 1) >> 1) + 3) & ~3;
+    const uint32_t* gbits = p.adj_bits + p.b_bits_off[b];
+    if (!FIRST && tid < 16) {  // nibble e -> bf16 (bit 0, bit 1, bit 2, bit 3) as two words
+        const unsigned one = 0x3F80u;
+        oc_u32x2 t;
+        t.x = ((tid & 1) ? one : 0u) | ((tid & 2) ? one << 16 : 0u);
+        t.y = ((tid & 4) ? one : 0u) | ((tid & 8) ? one << 16 : 0u);
+        *reinterpret_cast<oc_u32x2*>(lut + 8 * tid) = t;
+    }
+    // ---- what the MLP needs that does not depend on the tile, requested now (csrc/evallayer.hip)
+    const int NCT = H >> 5, KSB = 4 / NCT;
+    const int ctB = wave % NCT, khB = wave / NCT;
+    const int ncolB = 32 * ctB + i;                               // output column of this lane = row of W
+    const float* Wk[3];
+    int ldwk[3];
+    float fbw[3][2][8];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        Wk[k] = nullptr; ldwk[k] = 0;
+        if (k < p.m) {
+            const long long* te = p.table + (size_t)(p.l * p.m + k) * kOcLinWords;
+            Wk[k] = reinterpret_cast<const float*>(te[0]);
+            ldwk[k] = (int)te[6];
+            if (tid < H) {
+                const float gam = reinterpret_cast<const float*>(te[2])[tid], bet = reinterpret_cast<const float*>(te[3])[tid];
+                const float rm = reinterpret_cast<const float*>(te[4])[tid], rv = reinterpret_cast<const float*>(te[5])[tid];
+                const float rstd = (float)(1.0 / sqrt((double)rv + (double)p.bn_eps));
+                const float sc = gam * rstd;
+                aff[k][0][tid] = reinterpret_cast<const float*>(te[1])[tid];
+                aff[k][1][tid] = sc;
+                aff[k][2][tid] = bet - rm * sc;
+            }
+            if (!(FIRST && k == 0)) {                             // (layer 0's first Linear ran on the source graphs)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int k0 = 16 * (khB + KSB * u) + 8 * h;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) fbw[k][u][j] = k0 + j < H ? Wk[k][(size_t)ncolB * ldwk[k] + k0 + j] : 0.f;
+                }
+            }
+        }
+    }
+    // the combine pass's operands (8 threads per tile row): the row, whether it is a row of the deleted graph, bit
+    // (row, v) of the adjacency and the row's reduced degree
+    const int row = tid >> 3, c8 = tid & 7;
+    const int vr = min(rb * 32 + row, n - 1);
+    const bool vrow = rb * 32 + row < n;
+    const bool keep = vrow && vr != v;
+    const unsigned arv = (gbits[(size_t)vr * (2 * HPW) + ((v >> 3) & 1) * HPW + (v >> 6)] >> ((((v >> 4) & 3) << 3) + (v & 7))) & 1u;
+    float deg = 1.f;
+    if (p.average) {
+        const int32_t* rp = p.rowptr + p.b_rp_off[b];
+        deg = (float)(rp[vr + 1] - rp[vr] - (int)arv + p.self_loop);
+    }
+    const float eps_l = p.eps ? p.eps[p.l] : 0.f;
+    if (FIRST) {
+        // ---- layer 0: the first Linear's output of the deleted graph from the source graph's XW and S ----------------
+        __syncthreads();                                          // the vectors
+        const float* xwr = p.XW + (size_t)(node0 + vr) * p.ldxw;
+        const float* xwv = p.XW + (size_t)(node0 + v) * p.ldxw;
+        const float* sr = p.S + (size_t)(node0 + vr) * p.lds;
+        const float selfw = 1.f + eps_l;                          // graphcnn.py:161 (1 + eps[layer]) h
+        const bool last = p.m == 1;
+        for (int c = c8; c < H; c += 8) {
+            const float xw = xwr[c];
+            float t = sr[c];
+            if (!p.self_loop && p.average) t -= xw;
+            if (arv) t -= xwv[c];
+            if (p.average) {
+                if (deg == 0.f) t = 0.f;                          // no neighbour left: 0 / 0 -> NaN as in the reference
+                t /= deg;
+            }
+            if (!p.self_loop) t += p.average ? selfw * xw : eps_l * xw;
+            float y = gnm_relu((t + aff[0][0][c]) * aff[0][1][c] + aff[0][2][c]);
+            if (last) {
+                if (!keep) y = 0.f;                               // the deleted row (and rows past n): zeros, not in the readout
+                if (vrow && p.l + 1 < p.L) p.Hout[(row0 + vr) * H + c] = y;
+            }
+            T1[row * kOcTS + c] = y;
+        }
+    } else {
+        // ---- A. aggregation over the virtual graph's activations (row v of them is zero) ---------------------------
+        const int NCA = NCT;
+        const float* Hg = p.Hin + row0 * H;
+        for (int c = c8; c < H; c += 8) T1[row * kOcTS + c] = Hg[(size_t)vr * H + c];       // the self term, parked
+        {
+            const int ksteps = (n + 15) >> 4;
+            const int ct = wave % NCA, kh = wave / NCA, KS = 4 / NCA;
+            {   // this lane's half row of the block's adjacency bits -> LDS, one word per (word index, thread)
+                const oc_u32x4* rp4 = reinterpret_cast<const oc_u32x4*>(gbits + (size_t)(rb * 32 + i) * (2 * HPW) + h * HPW);
+                const oc_u32x4 z4 = {0u, 0u, 0u, 0u};
+                const oc_u32x4 a0 = rp4[0];
+                const oc_u32x4 a1 = HPW > 4 ? rp4[1] : z4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { bitsw[j][tid] = a0[j]; bitsw[4 + j][tid] = a1[j]; }
+            }
+            const unsigned xbytes = (unsigned)(((size_t)(n - 1) * H + H) * 4);
+            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Hg), 0, (int)xbytes, 0x00020000);
+            const int c = 32 * ct + i;
+            const unsigned xvo = (unsigned)((8 * h * H + c) * 4);
+            const int xrow = H * 4;
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            __syncthreads();                                      // the table
+            auto request = [&](float (&d)[8], int s) {            // rows past n: offsets past the descriptor, zeros
+#pragma unroll
+                for (int j = 0; j < 8; ++j) d[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xvo, (16 * s + j) * xrow, 0));
+            };
+            auto multiply = [&](const float (&d)[8], int s) {
+                oc_bf16x8 a1, a2, a3;
+                oc_split8(d, a1, a2, a3);
+                // the 8 bits of (row 32 rb + i, columns 16 s + 8 h ..): byte s & 3 of word s >> 2 of this lane's half row
+                const unsigned pkw = bitsw[s >> 2][tid];
+                const unsigned byte3 = ((pkw >> (8 * (s & 3))) & 0xFFu) << 3;
+                const unsigned lo = byte3 & 0x78u, hi = (byte3 >> 4) & 0x78u;
+                const oc_u32x2 l2 = *reinterpret_cast<const oc_u32x2*>(lut + lo);
+                const oc_u32x2 h2 = *reinterpret_cast<const oc_u32x2*>(lut + hi);
+                const oc_u32x4 qq = {l2.x, l2.y, h2.x, h2.y};
+                const oc_bf16x8 bq = __builtin_bit_cast(oc_bf16x8, qq);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, bq, acc, 0, 0, 0);      // small planes first
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bq, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bq, acc, 0, 0, 0);
+            };
+            // this wave's steps s = kh + KS u, four to an iteration, three requests ahead of the one being multiplied
+            float hb0[8], hb1[8], hb2[8], hb3[8];
+            request(hb0, kh); request(hb1, kh + KS); request(hb2, kh + 2 * KS);
+#pragma nounroll
+            for (int s = kh; s < ksteps; s += 4 * KS) {           // wave-uniform
+                request(hb3, s + 3 * KS);
+                multiply(hb0, s);
+                if (s + KS < ksteps) { request(hb0, s + 4 * KS); multiply(hb1, s + KS); }
+                if (s + 2 * KS < ksteps) { request(hb1, s + 5 * KS); multiply(hb2, s + 2 * KS); }
+                if (s + 3 * KS < ksteps) { request(hb2, s + 6 * KS); multiply(hb3, s + 3 * KS); }
+            }
+            // accumulator (r, lane): input column 32 ct + (r & 3) + 8 (r >> 2) + 4 h, output row i
+#pragma unroll
+            for (int r = 0; r < 16; ++r) part[wave][i][(r & 3) + 8 * (r >> 2) + 4 * h] = acc[r];
+        }
+        __syncthreads();
+        {
+            const int KS = 4 / NCA;
+            const float selfw = 1.f + eps_l;                      // graphcnn.py:161 (1 + eps[layer]) h
+            for (int c = c8; c < H; c += 8) {
+                float t = 0.f;
+                for (int k = 0; k < KS; ++k) t += part[(c >> 5) + NCA * k][row][c & 31];
+                const float hin = T1[row * kOcTS + c];
+                if (p.self_loop) t += hin;
+                if (p.average) {
+                    if (deg == 0.f) t = 0.f;                      // no neighbour left: 0 / 0 -> NaN as in the reference
+                    t /= deg;
+                }
+                if (!p.self_loop) t += selfw * hin;
+                T0[row * kOcTS + c] = vrow ? t : 0.f;
+            }
+        }
+    }
+    // ---- B. the MLP (layer 0: from its second Linear) ----------------------------------------------------------
+    float* Tin = FIRST ? T1 : T0;
+    float* Tout = FIRST ? T0 : T1;
+#pragma unroll
+    for (int k = FIRST ? 1 : 0; k < 3; ++k) {
+        if (k >= p.m) break;                                      // workgroup-uniform
+        const int ct = ctB, kh = khB, ncol = ncolB;
+        const int nst = H >> 4;
+        __syncthreads();                                          // the input tile (and, the first time, the vectors) complete
+        {
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            auto stepB = [&](const float (&fb)[8], int s) {
+                const int k0 = 16 * s + 8 * h;
+                float fa[8];
+                const float4 v0 = *reinterpret_cast<const float4*>(Tin + i * kOcTS + k0);
+                const float4 v1 = *reinterpret_cast<const float4*>(Tin + i * kOcTS + k0 + 4);
+                fa[0] = v0.x; fa[1] = v0.y; fa[2] = v0.z; fa[3] = v0.w; fa[4] = v1.x; fa[5] = v1.y; fa[6] = v1.z; fa[7] = v1.w;
+                oc_bf16x8 a1, a2, a3, b1, b2, b3;
+                oc_split8(fa, a1, a2, a3);
+                oc_split8(fb, b1, b2, b3);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc, 0, 0, 0);      // small terms first
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
+            };
+            if (kh < nst) stepB(fbw[k][0], kh);
+            if (kh + KSB < nst) stepB(fbw[k][1], kh + KSB);
+#pragma nounroll
+            for (int s = kh + 2 * KSB; s < nst; s += KSB) {
+                const int k0 = 16 * s + 8 * h;
+                float fb[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) fb[j] = k0 + j < H ? Wk[k][(size_t)ncol * ldwk[k] + k0 + j] : 0.f;
+                stepB(fb, s);
+            }
+            // accumulator (r, lane): tile row (r & 3) + 8 (r >> 2) + 4 h, output column 32 ct + i
+#pragma unroll
+            for (int r = 0; r < 16; ++r) part[wave][(r & 3) + 8 * (r >> 2) + 4 * h][i] = acc[r];
+        }
+        __syncthreads();
+        const bool last = k == p.m - 1;
+        for (int c = c8; c < H; c += 8) {
+            float z = aff[k][0][c];
+            for (int u = 0; u < KSB; ++u) z += part[(c >> 5) + NCT * u][row][c & 31];
+            float y = gnm_relu(z * aff[k][1][c] + aff[k][2][c]);        // mlp.py:48 (inner) / graphcnn.py:163-166, 187-190 (outer)
+            if (last) {
+                if (!keep) y = 0.f;                               // the deleted row (and rows past n): zeros, not in the readout
+                if (vrow && p.l + 1 < p.L) p.Hout[(row0 + vr) * H + c] = y;
+            }
+            Tout[row * kOcTS + c] = y;
+        }
+        float* t = Tin; Tin = Tout; Tout = t;
+    }
+    __syncthreads();
+    // the block's share of the deleted graph's readout (graphcnn.py:228-229): column sums of its rows, fixed order
+    if (tid < H) {
+        float ssum = 0.f;
+        for (int r = 0; r < 32; ++r) ssum += Tin[r * kOcTS + tid];
+        p.rpart[((size_t)q * p.wmax + rb) * H + tid] = ssum;
+    }
+}
+
+struct OcFinArgs {
+    const int32_t* node_off; const int32_t* vgraph;
+    const float* rpart;                           // [L][V][wmax][H]
+    const long long* table;
+    int V, wmax, L, m, H, graph_avg;
+    int ncls; int cls[kOcMaxClasses];
+    float* out; long long ldo;                    // out[ci * ldo + q]
+};
+
+__global__ void __launch_bounds__(256) gnm_occlusion_finish_kernel(const OcFinArgs p) {
+    extern __shared__ float gfl[];                // [L * H]
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const int b = p.vgraph[q];
+    const int n = p.node_off[b + 1] - p.node_off[b];
+    const int W = (n + 31) >> 5, H = p.H, LH = p.L * p.H;
+    for (int e = tid; e < LH; e += 256) {
+        const int l = e / H, c = e - l * H;
+        float s = 0.f;
+        for (int rb = 0; rb < W; ++rb) s += p.rpart[(((size_t)l * p.V + q) * p.wmax + rb) * H + c];
+        if (p.graph_avg) s *= 1.0f / (float)(n - 1);    // the reference stores 1./len(graph.g) as fp32 (graphcnn.py:123,130)
+        gfl[e] = s;
+    }
+    __syncthreads();
+    // classifier head (graphcnn.py:224-231, eval: no dropout): a wave per class, lanes over the L*H products
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int ci = wave; ci < p.ncls; ci += 4) {
+        const int cls = p.cls[ci];
+        float acc = 0.f;
+        for (int e = lane; e < LH; e += 64) {
+            const int l = e / H, c = e - l * H;
+            const long long* th = p.table + (size_t)p.L * p.m * kOcLinWords + 2 * l;
+            acc += gfl[e] * reinterpret_cast<const float*>(th[0])[(size_t)cls * H + c];
+        }
+        if (lane < p.L) acc += reinterpret_cast<const float*>((p.table + (size_t)p.L * p.m * kOcLinWords + 2 * lane)[1])[cls];
+        acc = wave_sum(acc);
+        if (lane == 0) p.out[(size_t)ci * p.ldo + q] = acc;
+    }
+}
+
+// Floats of scratch gnm_occlusion needs: two [rows, H] activation arrays (rows = sum of n_g^2 over the batch) and the
+// readout shares [L][V][ceil(n_max / 32)][H] (V = N virtual graphs).
+extern "C" long long gnm_occlusion_scratch_floats(long long rows, long long V, int n_max, int H, int L) {
+    if (rows < 0 || V < 0 || n_max < 0 || H < 0 || L < 0) return 0;
+    return 2 * rows * H + (long long)L * V * ((n_max + 31) / 32) * H;
+}
+
+// The class scores of every node-deleted copy of every graph of a batch (see the file header and include/gnm_hip.h).
+extern "C" int gnm_occlusion(const uint32_t* adj_bits, const int64_t* b_bits_off, const int32_t* node_off,
+                             const int32_t* rowptr, const int64_t* b_rp_off, const int32_t* vgraph,
+                             const int64_t* vrow_off, int B, int n_max, long long V, long long rows, const float* XW,
+                             int ldxw, const float* S, int lds, int H, int L, int m, int C, const int* classes_host,
+                             int n_classes, int average, int self_loop, int graph_avg, float bn_eps,
+                             const long long* table, const float* eps, float* scratch, float* out, long long ldo,
+                             void* stream) {
+    if (B == 0 || V == 0) return GNM_OK;
+    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || C < 1 || C > 256 || n_max < 2 ||
+        n_max > kOcMaxN)
+        return GNM_ERR_UNSUPPORTED;
+    if (B < 0 || V < 0 || rows < V || ldo < V || !classes_host || n_classes < 1) return GNM_ERR_BAD_ARG;
+    for (int k = 0; k < n_classes; ++k)
+        if (classes_host[k] < 0 || classes_host[k] >= C) return GNM_ERR_BAD_ARG;
+    if (!adj_bits || !b_bits_off || !node_off || !rowptr || !b_rp_off || !vgraph || !vrow_off || !XW || !S || !table ||
+        !scratch || !out)
+        return GNM_ERR_BAD_ARG;
+    if (ldxw < H || lds < H) return GNM_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(adj_bits) & 15) return GNM_ERR_UNSUPPORTED;
+    const int wmax = (n_max + 31) / 32;
+    if (V * wmax >= (1LL << 31)) return GNM_ERR_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float* act[2] = {scratch, scratch + (size_t)rows * H};
+    float* rpart = scratch + 2 * (size_t)rows * H;
+    for (int l = 0; l < L; ++l) {
+        OcArgs a;
+        memset(&a, 0, sizeof(a));
+        a.adj_bits = adj_bits; a.b_bits_off = b_bits_off; a.node_off = node_off; a.rowptr = rowptr; a.b_rp_off = b_rp_off;
+        a.vgraph = vgraph; a.vrow_off = vrow_off;
+        a.XW = XW; a.ldxw = ldxw; a.S = S; a.lds = lds;
+        a.Hin = act[(l + 1) & 1];
+        a.V = (int)V; a.wmax = wmax; a.L = L; a.m = m; a.l = l; a.H = H;
+        a.average = average; a.self_loop = self_loop; a.bn_eps = bn_eps;
+        a.eps = eps;
+        a.table = table;
+        a.Hout = act[l & 1];
+        a.rpart = rpart + (size_t)l * V * wmax * H;
+        if (l == 0)
+            hipLaunchKernelGGL(gnm_occlusion_layer_kernel<true>, dim3((unsigned)(V * wmax)), dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL(gnm_occlusion_layer_kernel<false>, dim3((unsigned)(V * wmax)), dim3(256), 0, s, a);
+        GNM_CHECK_LAUNCH();
+    }
+    for (int c0 = 0; c0 < n_classes; c0 += kOcMaxClasses) {
+        OcFinArgs f;
+        memset(&f, 0, sizeof(f));
+        f.node_off = node_off; f.vgraph = vgraph; f.rpart = rpart; f.table = table;
+        f.V = (int)V; f.wmax = wmax; f.L = L; f.m = m; f.H = H; f.graph_avg = graph_avg;
+        f.ncls = n_classes - c0 < kOcMaxClasses ? n_classes - c0 : kOcMaxClasses;
+        for (int k = 0; k < f.ncls; ++k) f.cls[k] = classes_host[c0 + k];
+        f.out = out + (size_t)c0 * ldo; f.ldo = ldo;
+        hipLaunchKernelGGL(gnm_occlusion_finish_kernel, dim3((unsigned)V), dim3(256), (size_t)L * H * 4, s, f);
+        GNM_CHECK_LAUNCH();
+    }
+    return GNM_OK;
+}

@@ -639,18 +639,10 @@ def perm_to_device(perm, B, dev, out=None):
     return host.to(dev, non_blocking=True)
 
 
-def eval_forward_fused(spec, batch, perm, P, X, want_disc, mode=True):
-    """GIN_InfoMaxReg.forward in eval() mode (graphcnn.py:194-251 with BatchNorm on its running statistics and dropout
-    off) as ONE encoder launch (gnm_eval_encoder: layers + readout + classifier, a workgroup per graph) plus, for the
-    Infomax scores, U = sigmoid(g_f) W^T and the score kernel.  No autograd graph: callers use it under no_grad only
-    (models/graphcnn.py).  Returns (c_logit, d_logit, g_f) like GinInfoMaxFn."""
-    dev = launch_device(X, *[t for t in P.values() if torch.is_tensor(t)][:1])
+def _eval_table(spec, P, dev):
+    """The DEVICE table of parameter addresses gnm_eval_encoder / gnm_eval_layers / gnm_occlusion read
+    (include/gnm_hip.h), cached on the spec."""
     L, m = spec.L, spec.m
-    N, B = batch.N, batch.B
-    H = P["batch_norms.0.weight"].shape[0]
-    Cn = P["linears_prediction.0.weight"].shape[0]
-    f32 = dict(dtype=torch.float32, device=dev)
-    X = X.contiguous()
     words = []
     for l in range(L):
         for k in range(m):
@@ -674,7 +666,22 @@ def eval_forward_fused(spec, batch, perm, P, X, want_disc, mode=True):
     if cached is None or cached[0] != key or cached[1].device != dev:
         host = torch.tensor(words, dtype=torch.int64).pin_memory()
         cached = spec._eval_table = (key, host.to(dev, non_blocking=True), host)
-    table = cached[1]
+    return cached[1]
+
+
+def eval_forward_fused(spec, batch, perm, P, X, want_disc, mode=True):
+    """GIN_InfoMaxReg.forward in eval() mode (graphcnn.py:194-251 with BatchNorm on its running statistics and dropout
+    off) as ONE encoder launch (gnm_eval_encoder: layers + readout + classifier, a workgroup per graph) plus, for the
+    Infomax scores, U = sigmoid(g_f) W^T and the score kernel.  No autograd graph: callers use it under no_grad only
+    (models/graphcnn.py).  Returns (c_logit, d_logit, g_f) like GinInfoMaxFn."""
+    dev = launch_device(X, *[t for t in P.values() if torch.is_tensor(t)][:1])
+    L, m = spec.L, spec.m
+    N, B = batch.N, batch.B
+    H = P["batch_norms.0.weight"].shape[0]
+    Cn = P["linears_prediction.0.weight"].shape[0]
+    f32 = dict(dtype=torch.float32, device=dev)
+    X = X.contiguous()
+    table = _eval_table(spec, P, dev)
     hidden_all = torch.empty((L, N, H), **f32)
     hidden = [hidden_all[l] for l in range(L)]
     g_f = torch.empty((B, L * H), **f32)
@@ -869,6 +876,92 @@ def edge_saliency_hip(spec, batch, X, P, classes, out=None):
                                             k.table.data_ptr(), k.eps, k.scratch.data_ptr(), Y.data_ptr(), Y.stride(0),
                                             out[ci].data_ptr(), out.stride(1), _stream()),
                       "gnm_edge_saliency")
+    return out
+
+
+def occlusion_decline(spec, batch, X, P):
+    """None if csrc/occlusion.hip takes this batch, else the condition it declines.  Unlike saliency_decline an isolated
+    node under average pooling with learned eps is taken: a deleted graph's NaN stays in its own score."""
+    H = P["batch_norms.0.weight"].shape[0]
+    if spec.n_max:
+        return "max neighbour pooling"
+    if not getattr(batch, "has_bits", False) or batch.n_max > 416:
+        return "a graph of more than 416 nodes or without a bit adjacency"
+    if H not in (32, 64, 128):
+        return "hidden_dim %d not in {32, 64, 128}" % H
+    if not 1 <= spec.m <= 3 or spec.L > 16:
+        return "num_mlp_layers outside 1..3 or more than 16 layers"
+    if spec.sync_bn is not None:
+        return "synchronised BatchNorm"
+    if not X.is_cuda or batch.B < 1:
+        return "an empty batch or one off the GPU"
+    if batch.n_min < 2:
+        return "a graph of fewer than 2 nodes"
+    if not 1 <= X.shape[1] <= int(lib.gnm_linear_max_k(H)):
+        return "input width %d outside 1..%d" % (X.shape[1], int(lib.gnm_linear_max_k(H)))
+    return None
+
+
+# occlusion_hip's scratch (two [sum n^2, H] activation arrays and the readout shares) stays under this many bytes: the
+# source graphs of a batch are run in chunks.  One 416-node graph at H = 128, L = 16 needs 0.22 GB.
+OCCLUSION_SCRATCH_BYTES = 2 << 30
+
+
+def occlusion_hip(spec, batch, X, P, classes, out=None):
+    """The eval-mode class scores of every node-deleted copy of every graph of a batch (csrc/occlusion.hip,
+    include/gnm_hip.h gnm_occlusion): out[ci, node_off[g] + v] = c_logit[classes[ci]] of graph g without node v.  Per
+    batch XW = X W0^T (the split-precision Linear, any input width) and S = (A + I) XW (the CSR gather: one kernel
+    whatever the batch's density, so a graph's result does not depend on its batch-mates); then, per chunk of source
+    graphs whose scratch fits OCCLUSION_SCRATCH_BYTES, L layer launches and the finish launch.  The shapes
+    occlusion_decline takes.  Parameters, buffers and the numpy RNG are not touched; the device parameter table is
+    eval_forward_fused's.  Returns a float32 [len(classes), N] tensor (`out` when given)."""
+    dev = launch_device(X, P["eps"])
+    L, m = spec.L, spec.m
+    N, B = batch.N, batch.B
+    H = P["batch_norms.0.weight"].shape[0]
+    Cn = P["linears_prediction.0.weight"].shape[0]
+    F0 = X.shape[1]
+    X = X.contiguous()
+    out = _out_array(out, (len(classes), N), dev)
+    cls = (C.c_int * len(classes))(*[int(c) for c in classes])
+    offs = np.asarray(batch.node_off_host, dtype=np.int64)
+    ns = np.diff(offs)
+    with torch.no_grad(), _stream_scope(dev):
+        table = _eval_table(spec, P, dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        W0 = P["mlps.0.linear.weight" if m == 1 else "mlps.0.linears.0.weight"]
+        XW, S = torch.empty((N, H), **f32), torch.empty((N, H), **f32)
+        _linear(X, W0, 0, None, XW, N, F0, H, None, None)
+        check(lib.gnm_agg(*batch.csr_ptrs(), *batch.deg_ptrs(), batch.node_off.data_ptr(), B, batch.n_max,
+                          batch.nnz_max, XW.data_ptr(), XW.stride(0), S.data_ptr(), S.stride(0), H, None, 0, 1, 0,
+                          None, 0, None, _stream()), "gnm_agg")
+        g0 = 0
+        while g0 < B:
+            g1, rows, need = g0, 0, 0
+            while g1 < B:                   # the longest run of graphs whose scratch fits the budget (at least one)
+                r = rows + int(ns[g1]) ** 2
+                k = int(lib.gnm_occlusion_scratch_floats(r, int(offs[g1 + 1] - offs[g0]), int(ns[g0:g1 + 1].max()), H, L))
+                if g1 > g0 and 4 * k > OCCLUSION_SCRATCH_BYTES:
+                    break
+                g1, rows, need = g1 + 1, r, k
+            nc = ns[g0:g1]
+            V, r0 = int(nc.sum()), int(offs[g0])
+            up = batch.arena._upload
+            node_off = up(torch.as_tensor((offs[g0:g1 + 1] - offs[g0]).astype(np.int32)))
+            vrow_off = up(torch.as_tensor(np.concatenate([[0], np.cumsum(nc * nc)[:-1]]).astype(np.int64)))
+            vgraph = up(torch.as_tensor(np.repeat(np.arange(g1 - g0, dtype=np.int32), nc)))
+            bits_off, rp_off = batch.bits_off[g0:g1], batch.rp_off[g0:g1]
+            scratch = torch.empty(need, **f32)
+            dst = out[:, r0:r0 + V]
+            with _timed("occlusion_hip", B=g1 - g0, N=V, H=H, L=L):
+                check(lib.gnm_occlusion(batch.arena.bits.buf.data_ptr(), bits_off.data_ptr(), node_off.data_ptr(),
+                                        batch.arena.rowptr.buf.data_ptr(), rp_off.data_ptr(), vgraph.data_ptr(),
+                                        vrow_off.data_ptr(), g1 - g0, int(nc.max()), V, rows, XW[r0:].data_ptr(),
+                                        XW.stride(0), S[r0:].data_ptr(), S.stride(0), H, L, m, Cn, cls, len(classes),
+                                        int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS,
+                                        table.data_ptr(), P["eps"].data_ptr() if spec.learn_eps else None,
+                                        scratch.data_ptr(), dst.data_ptr(), out.stride(0), _stream()), "gnm_occlusion")
+            g0 = g1
     return out
 
 

@@ -34,7 +34,8 @@ from mlp import MLP  # noqa: E402
 from discriminator import Discriminator  # noqa: E402
 from gnm.arena import GraphArena  # noqa: E402
 from gnm.core import (DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, edge_saliency_hip,  # noqa: E402
-                      eval_forward_fused, eval_fused_ok, launch_device, saliency_decline, saliency_hip, saliency_maps_hip)
+                      eval_forward_fused, eval_fused_ok, launch_device, occlusion_decline, occlusion_hip,
+                      saliency_decline, saliency_hip, saliency_maps_hip)
 
 __all__ = ["GIN_InfoMaxReg", "GraphCNN", "MLP", "Discriminator"]
 
@@ -487,6 +488,73 @@ class GIN_InfoMaxReg(nn.Module):
             return edge_saliency_hip(self._spec, batch, X, P, classes, out=dst)
         return self._clean_graphs_apart(chunk, batch, bad, dst, (len(classes), batch.N, batch.n_max),
                                         lambda sub, Xs: edge_saliency_hip(self._spec, sub, Xs, P, classes))
+
+    def occlusion(self, graphs, cls, batch_size=8, return_scores=False):
+        """Per-ROI occlusion maps (virtual lesioning) of many graphs in batches: how far the class score moves when a
+        node is taken out of the graph -- the fidelity check of the gradient maps above.  With G \\ v the graph without
+        node v (the node, its feature row and its edges in both directions removed; the other nodes keep their feature
+        rows) and score_c the eval logit c_logit[:, c] of forward() (BatchNorm on its running statistics, no dropout;
+        the readout over n - 1 nodes, graph "average" with the fp32 1/(n - 1), neighbour "average" by the reduced
+        graph's own degree, self loops kept):
+
+            occluded[c, g, v] = score_c(G_g \\ v),   base[c, g] = score_c(G_g),   delta = base - occluded  (fp32)
+
+        a positive delta: the ROI supports the class.  No copy of a graph is built: csrc/occlusion.hip runs every
+        (graph, deleted node) pair as a virtual graph over the source graph's bit adjacency (include/gnm_hip.h
+        gnm_occlusion); base is the model's ordinary eval forward.  delta is a difference of two nearly equal numbers,
+        so accuracy is a statement about base and occluded (return_scores=True returns (delta, base, occluded)).
+
+        cls: an int, or a sequence of ints; one pass per batch serves all of them.  Returns a float32 device tensor
+        [len(graphs), n] for an int `cls` and [len(cls), len(graphs), n] for a sequence; for graphs of different node
+        counts a list of [n_g] tensors (a list of such lists for a sequence `cls`), as class_activation() lays them out.
+        base: [len(graphs)] / [len(cls), len(graphs)].
+
+        If G \\ v leaves a node without neighbours under neighbour "average" with learned eps, the reference's 0/0 row
+        makes that score NaN: occluded[:, g, v] is NaN and no other entry is.  A graph with a non-finite feature gets
+        an all-NaN map; its batch-mates are unaffected.  The shapes class_activation(kind="gradient") takes, at any
+        input width the model is built with; any other batch raises ValueError naming the condition (max pooling,
+        n > 416 or no bit adjacency, hidden_dim not in {32, 64, 128}, num_mlp_layers outside 1..3, more than 16 layers,
+        synchronised BatchNorm), and so does a graph of fewer than 2 nodes.
+
+        The n deleted copies of an n-node graph need 2 n^2 hidden_dim floats of scratch: the default batch_size keeps a
+        batch of 400-node graphs at hidden_dim 128 under 2 GiB (8 x 0.16 GiB + the readout shares), and a larger batch
+        is run in chunks under that budget (gnm/core.py OCCLUSION_SCRATCH_BYTES).  The result is bitwise the same run to
+        run and for any batch_size.  No parameter .grad, BatchNorm buffer or numpy RNG state is touched, and the
+        train / eval mode is restored on exit."""
+        for g in graphs:
+            if len(g.g) < 2:
+                raise ValueError("occlusion: a graph of fewer than 2 nodes has no node-deleted copy")
+        bases = []
+        occ = self._interpret("occlusion", graphs, cls, batch_size, (),
+                              functools.partial(self._occlusion_batch, bases=bases))
+        single = isinstance(cls, (int, np.integer))
+        base = torch.cat(bases, 1)                          # [len(classes), len(graphs)]
+        if single:
+            base = base[0]
+        if torch.is_tensor(occ):
+            delta = base.unsqueeze(-1) - occ
+        elif single:
+            delta = [base[j] - o for j, o in enumerate(occ)]
+        else:
+            delta = [[base[ci, j] - o for j, o in enumerate(row)] for ci, row in enumerate(occ)]
+        return (delta, base, occ) if return_scores else delta
+
+    def _occlusion_batch(self, chunk, batch, P, classes, dst, bases):
+        """occlusion() of one batch: the occluded scores [len(classes), N] (dst when given); the batch's base scores
+        [len(classes), B] are appended to `bases`"""
+        X = batch.arena.features(batch).detach()
+        launch_device(X, P["eps"])                          # no CPU fallback: GnmError before any shape question
+        why = occlusion_decline(self._spec, batch, X, P)
+        if why is not None:
+            raise ValueError("occlusion does not cover this batch: %s" % why)
+        with torch.no_grad():
+            c_logit, _, _ = self._run(batch, X, np.arange(batch.B, dtype=np.int64), want_disc=False)
+        bases.append(c_logit.detach()[:, classes].t().contiguous())
+        bad = _nonfinite_graphs(batch, X)
+        if bad is None:
+            return occlusion_hip(self._spec, batch, X, P, classes, out=dst)
+        return self._clean_graphs_apart(chunk, batch, bad, dst, (len(classes), batch.N),
+                                        lambda sub, Xs: occlusion_hip(self._spec, sub, Xs, P, classes))
 
     def _clean_graphs_apart(self, chunk, batch, bad, dst, shape, run):
         """The gradient class activation and edge maps of a batch with non-finite graphs (`bad`): an all-NaN map for

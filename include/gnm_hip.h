@@ -383,6 +383,30 @@ int gnm_edge_saliency(const uint32_t* adj_bits, const int64_t* b_bits_off, const
                       const long long* table, const float* eps, float* scratch, const float* Y, int ldy, float* out,
                       long long ldo, void* stream);
 
+/* ---- Eval-mode per-node occlusion (virtual lesioning; csrc/occlusion.hip) -------------------------------------------
+ * out[ci * ldo + q] = the eval-mode class score c_logit[classes_host[ci]] (graphcnn.py:194-231 with BatchNorm on its
+ * running statistics, no dropout) of graph g WITHOUT node v -- the node, its feature row and its edges in both
+ * directions removed, so the readout runs over n_g - 1 nodes (graph "average": the fp32 1 / (n_g - 1)) and neighbour
+ * "average" divides by the reduced graph's own degree (0 / 0 -> NaN for a node whose only neighbour was v, as the
+ * reference computes it).  q = node_off[g] + v: one VIRTUAL graph per node of the batch, V = N of them; no copy of a
+ * graph is built.  L launches over (virtual graph, 32-row block) and one finish launch per 8 classes.
+ * vgraph: [V] int32, the source graph of virtual graph q; vrow_off: [B] int64, the first row of graph g's virtual graphs
+ * in the activation arrays = sum of n_k^2 over k < g; rows = that sum over the whole batch.
+ * XW: [N, H] = X W0^T of the SOURCE graphs (the first Linear of layer 0 WITHOUT its bias, gnm_linear_fwd) and
+ * S: [N, H] = (A + I) XW (the plain aggregation with average = 0, self_loop = 1): layer 0 is formed from these two per
+ * virtual graph, so any input width F0 is taken.  table / eps: as gnm_eval_layers (the same DEVICE parameter table).
+ * scratch: gnm_occlusion_scratch_floats(rows, V, n_max, H, L) floats.  classes_host: n_classes HOST ints in [0, C).
+ * GNM_ERR_UNSUPPORTED (nothing launched): H not in {32, 64, 128}, m outside 1..3, L outside 1..16, C > 256, n_max < 2 or
+ * > 416 (every graph needs a bit adjacency).  GNM_ERR_BAD_ARG: a class outside [0, C), n_classes < 1, ldo < V,
+ * ldxw / lds < H, a NULL array.  Every sum has a fixed order and no atomics are used: bitwise reproducible, and a graph's
+ * result does not depend on the other graphs of the batch. */
+long long gnm_occlusion_scratch_floats(long long rows, long long V, int n_max, int H, int L);
+int gnm_occlusion(const uint32_t* adj_bits, const int64_t* b_bits_off, const int32_t* node_off, const int32_t* rowptr,
+                  const int64_t* b_rp_off, const int32_t* vgraph, const int64_t* vrow_off, int B, int n_max, long long V,
+                  long long rows, const float* XW, int ldxw, const float* S, int lds, int H, int L, int m, int C,
+                  const int* classes_host, int n_classes, int average, int self_loop, int graph_avg, float bn_eps,
+                  const long long* table, const float* eps, float* scratch, float* out, long long ldo, void* stream);
+
 /* ---- Infomax discriminator (discriminator.py:19-38, graphcnn.py:233-246) ------------
  * hptrs_host: HOST array of L device pointers to the per-layer [N,H] hidden states
  * (n_f is never concatenated).  A layer may instead be given as the pre-BatchNorm output Z_l of its last Linear
