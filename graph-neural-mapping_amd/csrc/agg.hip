@@ -569,10 +569,10 @@ __global__ void __launch_bounds__(1024) gnm_agg_kernel(const AggArgs p) {
                         const float4 uq = *reinterpret_cast<const float4*>(p.s_U + (size_t)gq * p.ld_U + col0 + 4 * sub);
                         tot.x += s2 * uq.x; tot.y += s2 * uq.y; tot.z += s2 * uq.z; tot.w += s2 * uq.w;
                     }
-                    if (!(zrow.x * lsc.x + lsh.x > 0.f)) tot.x = 0.f;
-                    if (!(zrow.y * lsc.y + lsh.y > 0.f)) tot.y = 0.f;
-                    if (!(zrow.z * lsc.z + lsh.z > 0.f)) tot.z = 0.f;
-                    if (!(zrow.w * lsc.w + lsh.w > 0.f)) tot.w = 0.f;
+                    if (zrow.x * lsc.x + lsh.x <= 0.f) tot.x = 0.f;
+                    if (zrow.y * lsc.y + lsh.y <= 0.f) tot.y = 0.f;
+                    if (zrow.z * lsc.z + lsh.z <= 0.f) tot.z = 0.f;
+                    if (zrow.w * lsc.w + lsh.w <= 0.f) tot.w = 0.f;
                     ss1.x += tot.x; ss1.y += tot.y; ss1.z += tot.z; ss1.w += tot.w;
                     ss2.x += tot.x * (zrow.x - lmu.x); ss2.y += tot.y * (zrow.y - lmu.y);
                     ss2.z += tot.z * (zrow.z - lmu.z); ss2.w += tot.w * (zrow.w - lmu.w);
@@ -1432,10 +1432,10 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
                     const float4 uq = *reinterpret_cast<const float4*>(p.s_U + (size_t)gq * p.ld_U + 4 * sub);
                     tot.x += s2 * uq.x; tot.y += s2 * uq.y; tot.z += s2 * uq.z; tot.w += s2 * uq.w;
                 }
-                if (!(zrow.x * lsc.x + lsh.x > 0.f)) tot.x = 0.f;
-                if (!(zrow.y * lsc.y + lsh.y > 0.f)) tot.y = 0.f;
-                if (!(zrow.z * lsc.z + lsh.z > 0.f)) tot.z = 0.f;
-                if (!(zrow.w * lsc.w + lsh.w > 0.f)) tot.w = 0.f;
+                if (zrow.x * lsc.x + lsh.x <= 0.f) tot.x = 0.f;
+                if (zrow.y * lsc.y + lsh.y <= 0.f) tot.y = 0.f;
+                if (zrow.z * lsc.z + lsh.z <= 0.f) tot.z = 0.f;
+                if (zrow.w * lsc.w + lsh.w <= 0.f) tot.w = 0.f;
                 ss1.x += tot.x; ss1.y += tot.y; ss1.z += tot.z; ss1.w += tot.w;
                 ss2.x += tot.x * (zrow.x - lmu.x); ss2.y += tot.y * (zrow.y - lmu.y);
                 ss2.z += tot.z * (zrow.z - lmu.z); ss2.w += tot.w * (zrow.w - lmu.w);

@@ -461,7 +461,8 @@ __global__ void __launch_bounds__(kAggmThreads, 4) gnm_aggm_kernel(const AggArgs
                     tot += ex[q];
                     // the ReLU mask of the layer below; rows past n (their loads returned 0) count as masked, so the
                     // column sums need no guard of their own (the store of such a row is clipped anyway)
-                    if (!(pre > 0.f && vrow < n)) tot = 0.f;
+                    // (pre <= 0, as torch's threshold backward: a NaN pre-activation lets the gradient through)
+                    if (pre <= 0.f || vrow >= n) tot = 0.f;
                     ss1 += tot;
                     ss2 = fmaf(tot, zrow - lmu, ss2);
                 }

@@ -1229,7 +1229,7 @@ __global__ void __launch_bounds__(kSplit128Waves * 64) gnm_lin_split128_kernel(c
                     const int lrow = (r & 3) + 8 * (r >> 2) + 4 * h;
                     const float zv = zm[c & 1][r];
                     float g = acc[c][r];
-                    if (!(zv * msc + msh > 0.f)) g = 0.f;
+                    if (zv * msc + msh <= 0.f) g = 0.f;
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g), rz, zvo, (((r & 3) + 8 * (r >> 2)) * p.ldz + 32 * c) * 4, 0);
                     if (lrow < rows) {
                         s1 += g;
@@ -2191,7 +2191,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
                     for (int r = 0; r < 16; ++r) {
                         const float z = xv[r][c];
                         float g = dacc[c][r];
-                        if (!(z * psc[c] + psh[c] > 0.f)) g = 0.f;
+                        if (z * psc[c] + psh[c] <= 0.f) g = 0.f;
                         if (r0 + (r & 3) + 8 * (r >> 2) + 4 * h < p.N) {
                             cs1[c] += g;
                             cs2[c] += g * ((z - cmu[c]) * crs[c]);
@@ -2228,10 +2228,10 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
                     const int row = orow0 + (j0 + j) * OR;
                     float4 g = *reinterpret_cast<const float4*>(Xs + row * XS + 4 * oc4);
                     const float4 z = zl[j];
-                    if (!(z.x * lsc.x + lsh.x > 0.f)) g.x = 0.f;
-                    if (!(z.y * lsc.y + lsh.y > 0.f)) g.y = 0.f;
-                    if (!(z.z * lsc.z + lsh.z > 0.f)) g.z = 0.f;
-                    if (!(z.w * lsc.w + lsh.w > 0.f)) g.w = 0.f;
+                    if (z.x * lsc.x + lsh.x <= 0.f) g.x = 0.f;
+                    if (z.y * lsc.y + lsh.y <= 0.f) g.y = 0.f;
+                    if (z.z * lsc.z + lsh.z <= 0.f) g.z = 0.f;
+                    if (z.w * lsc.w + lsh.w <= 0.f) g.w = 0.f;
                     if (r0 + row < p.N) {
                         *reinterpret_cast<float4*>(p.dA + (size_t)(r0 + row) * p.lda + 4 * oc4) = g;
                         ss1.x += g.x; ss1.y += g.y; ss1.z += g.z; ss1.w += g.w;

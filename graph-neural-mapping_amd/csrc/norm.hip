@@ -219,7 +219,7 @@ extern "C" int gnm_gather_graph_rows(const float* src, const float* src2, int ld
 //              + dsc1[v] * U[b,c]                          (discriminator positive branch)
 //              + [v < B] s2sum[inv[v]] * U[inv[v],c]       (negative branch: n_f[idx] gathers ROWS
 //                                                           perm[g] < B, graphcnn.py:242 quirk)
-//   g = total * (z*scale+shift > 0);  partial[b] = (sum g, sum g*xhat) per column
+//   g = total where z*scale+shift > 0 or NaN (torch threshold backward: 0 only where <= 0);  partial[b] = (sum g, sum g*xhat) per column
 // ---------------------------------------------------------------------------------
 __global__ void __launch_bounds__(1024) gnm_bn_relu_bwd_stats_kernel(
     const float* __restrict__ dH, int lddh, const float* __restrict__ dpool, int ldp, int average,
@@ -263,10 +263,10 @@ __global__ void __launch_bounds__(1024) gnm_bn_relu_bwd_stats_kernel(
                 }
             }
             if (relu) {
-                if (!(z.x * sc.x + sh.x > 0.f)) t.x = 0.f;
-                if (!(z.y * sc.y + sh.y > 0.f)) t.y = 0.f;
-                if (!(z.z * sc.z + sh.z > 0.f)) t.z = 0.f;
-                if (!(z.w * sc.w + sh.w > 0.f)) t.w = 0.f;
+                if (z.x * sc.x + sh.x <= 0.f) t.x = 0.f;
+                if (z.y * sc.y + sh.y <= 0.f) t.y = 0.f;
+                if (z.z * sc.z + sh.z <= 0.f) t.z = 0.f;
+                if (z.w * sc.w + sh.w <= 0.f) t.w = 0.f;
             }
             *reinterpret_cast<float4*>(G + (size_t)v * ldg + 4 * c4) = t;
             a1.x += t.x; a1.y += t.y; a1.z += t.z; a1.w += t.w;

@@ -1,4 +1,5 @@
 """Shared test helpers: golden loading and tolerance checks."""
+import contextlib
 import glob
 import os
 
@@ -41,6 +42,20 @@ TRUE_SHAPE_GRAD_ANCHOR_GAP = 5e-2
 # sums in BatchNorm, sequential fp32 spmm): its own deep-layer activations get this factor instead of
 # TRUE_SHAPE_FACTOR.  It is not the product; the pin is the fp64 oracle against the goldens.
 ORACLE32_FACTOR = 10.0
+
+
+@contextlib.contextmanager
+def fixed_dropout(masks):
+    """F.dropout patched to multiply by `masks` (a float32 array of keep / (1 - p) factors, the shape of the classifier
+    head's [L, B, C] logits) so that the model and the oracle apply the same ones (graphcnn.py:230)"""
+    import torch
+    import torch.nn.functional as F
+    orig = F.dropout
+    F.dropout = lambda x, p, training=True, inplace=False: torch.from_numpy(masks).to(x.device) * x
+    try:
+        yield
+    finally:
+        F.dropout = orig
 
 
 def golden_cases(prefix=""):

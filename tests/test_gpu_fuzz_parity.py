@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import RTOL, assert_close
+from helpers import RTOL, assert_close, fixed_dropout
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -74,14 +74,9 @@ def test_random_configuration_vs_fp64_oracle(cfg):
     perm = rng.permutation(B)
     # fixed dropout masks so that both sides apply the same ones (graphcnn.py:230): F.dropout is patched
     masks = ((rng.random((L, B, C)) >= p_drop) / (1 - p_drop)).astype(np.float32)
-    import torch.nn.functional as F
-    orig_dropout = F.dropout
-    F.dropout = lambda x, p, training=True, inplace=False: torch.from_numpy(masks).to(x.device) * x
-    try:
+    with fixed_dropout(masks):
         bt = model.arena().batch(graphs)
         c_logit, d_logit = model.forward_batch(bt, perm=perm)
-    finally:
-        F.dropout = orig_dropout
     N = B * n
     labels = torch.tensor([g.label for g in graphs], device=dev)
     y = torch.cat([torch.ones(N, 1), torch.zeros(N, 1)]).to(dev)
