@@ -17,7 +17,7 @@ import gc
 import torch
 
 from .arena import PackedStaticBatch, StaticBatch
-from .core import perm_to_device
+from .core import eval_fused_ok, perm_to_device
 
 
 
@@ -214,7 +214,8 @@ class CapturedEval:
     The reference evaluates one graph per forward over the whole training set every epoch (main.py:49-57, 154;
     also get_latent_space, main.py:71-82).  Eager, such a forward is ~110 launches = ~1.4 ms of Python for ~0.15 ms
     of GPU work; replayed it is one pinned descriptor copy + one graph launch.  The kernels, their launch
-    parameters and their order are the eager path's, so results are bitwise identical (tests/test_gpu_eval_replay.py).
+    parameters and their order are the eager path's, so results are bitwise identical (tests/test_gpu_eval_replay.py,
+    tests/test_gpu_replay_envelope.py).
     Outputs live in static buffers that the next run() overwrites: callers clone what they keep."""
 
     def __init__(self, model, gids_host, warmup=2):
@@ -222,6 +223,8 @@ class CapturedEval:
         gh = np.asarray(gids_host, dtype=np.int64)
         self.model = model
         self._fused = getattr(model, "eval_fused", False)
+        # (keep_hidden makes the evaluation encoders decline: which path was captured depends on it)
+        self._keep_hidden = bool(model._spec.keep_hidden)
         self.static = PackedStaticBatch(arena, arena.class_of(gh))
         self.static.load_gids(gh)
         dev = arena.device
@@ -236,11 +239,20 @@ class CapturedEval:
         m = self.model
         bt = self.static.batch
         with torch.no_grad():
+            X, P0 = None, None
             if getattr(m, "eval_fused", False):
-                # the evaluation encoders aggregate layer 0 themselves (a shape they decline takes the differentiable
-                # path, which then does so too): no gather from the arena's layer-0 cache
-                X, P0 = bt.arena.features(bt), None
-            else:
+                # the evaluation encoders aggregate layer 0 themselves: no gather from the arena's layer-0 cache.  A
+                # shape they decline takes the differentiable path, and that one reads the cache as the eager forward
+                # does (forward_batch): aggregating layer 0 inside the replay instead gave other bits than eager
+                # (tests/test_gpu_replay_envelope.py: H = 32 or 128 under eval_fused = True, C > 256, isolated nodes
+                # under neighbour average with learned eps)
+                names, tensors, buffers = m._param_lists()
+                P = dict(zip(names, tensors))
+                P.update(buffers)
+                X = bt.arena.features(bt)
+                if not eval_fused_ok(m._spec, bt, X, P, m.eval_fused):
+                    X = None
+            if X is None:
                 X, P0 = bt.arena.features_and_agg0(bt, m._spec.n_avg, not m._spec.learn_eps)
             return m._run(bt, X, self.perm, want_disc=True, P0=P0)
 
@@ -249,7 +261,8 @@ class CapturedEval:
         choice between the layer-by-layer kernels and the one-launch encoder)"""
         return (self.static.fits(gh) and _arena_ptrs(self.static.arena) == self._arena_ptrs
                 and tuple(t.data_ptr() for t in self._params) == self._param_ptrs
-                and getattr(self.model, "eval_fused", False) == self._fused)
+                and getattr(self.model, "eval_fused", False) == self._fused
+                and bool(self.model._spec.keep_hidden) == self._keep_hidden)
 
     def run(self, gh, perm):
         """replay on the graphs with arena ids gh (host int64 [B]) and the permutation of graphcnn.py:199;

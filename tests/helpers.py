@@ -45,13 +45,25 @@ ORACLE32_FACTOR = 10.0
 
 
 @contextlib.contextmanager
-def fixed_dropout(masks):
+def fixed_dropout(masks, device=None):
     """F.dropout patched to multiply by `masks` (a float32 array of keep / (1 - p) factors, the shape of the classifier
-    head's [L, B, C] logits) so that the model and the oracle apply the same ones (graphcnn.py:230)"""
+    head's [L, B, C] logits) so that the model and the oracle apply the same ones (graphcnn.py:230).
+
+    device: the masks are uploaded once, here, and the patch multiplies by that resident tensor (`masks` may also be a
+    tensor already on the device).  The form for a forward that is captured into a hipGraph: the default uploads
+    pageable host memory inside F.dropout, which synchronises a capturing stream."""
     import torch
     import torch.nn.functional as F
     orig = F.dropout
-    F.dropout = lambda x, p, training=True, inplace=False: torch.from_numpy(masks).to(x.device) * x
+    resident = None
+    if torch.is_tensor(masks):
+        resident = masks if device is None else masks.to(device)
+    elif device is not None:
+        resident = torch.from_numpy(masks).to(device)
+    if resident is not None:
+        F.dropout = lambda x, p, training=True, inplace=False: resident * x
+    else:
+        F.dropout = lambda x, p, training=True, inplace=False: torch.from_numpy(masks).to(x.device) * x
     try:
         yield
     finally:

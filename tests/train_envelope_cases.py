@@ -31,9 +31,14 @@ width rules), so the table cannot drift from the routing code unnoticed.
 Parameters are never trivial (drawn BatchNorm affines and running statistics, drawn eps, labels, a perm that is not the
 identity) and every Linear is rescaled on the case's own data in fp64 so that activations stay O(1).  A small case
 (L <= 5, n <= 64) whose smallest |pre-activation| under a ReLU is below RELU_MARGIN x the layer's largest is redrawn
-with the next parameter seed (case_data, `draw`): no small case sits on a mask boundary."""
+with the next parameter seed (case_data, `draw`): no small case sits on a mask boundary.
+
+The last section builds, per case, a pool of graphs of the case's class and a sequence of five batches drawn from it
+(case_pool), the table of what keeps a case out of a replay kind (replay_exclusion), and the fp64 anchor of a replayed
+step (anchor): what tests/test_gpu_replay_envelope.py and tests/test_replay_envelope_host.py share."""
 import collections
 import functools
+import itertools
 import zlib
 
 import numpy as np
@@ -221,24 +226,31 @@ def _own_graph(rng, n, kind, dens, f0, feats):
     return EG(n, src, dst, X)
 
 
+def _case_graph(case, rng, kind):
+    """one graph of the case's class from `rng`: the per-kind generator, then the label and graph.neighbors"""
+    if case.dens is None and case.kind in ("sym", "dir", "iso", "multi"):
+        g = make_graph(rng, case.n, kind, case.F0, case.feats)
+    else:
+        g = _own_graph(rng, case.n, case.kind, case.dens, case.F0, case.feats)
+    g.label = int(rng.integers(0, case.C))
+    _set_neighbors(g)
+    return g
+
+
+def _set_neighbors(g):
+    em = g.edge_mat.numpy()
+    # graph.neighbors as util.py:86-90 leaves them, read by neighbour "max" only
+    nb = [[] for _ in range(g.num_nodes)]
+    for a, b in zip(em[0].tolist(), em[1].tolist()):
+        nb[a].append(b)
+    g.neighbors = nb
+    g.max_neighbor = max((len(x) for x in nb), default=0)
+
+
 def case_graphs(case):
     rng = np.random.default_rng(zlib.crc32((case.data or case.id).encode()))
-    gs = []
-    for j in range(case.B):
-        if case.dens is None and case.kind in ("sym", "dir", "iso", "multi"):
-            # (isolated nodes in the first graph only, as the eval envelope has them)
-            g = make_graph(rng, case.n, case.kind if case.kind != "iso" or j == 0 else "sym", case.F0, case.feats)
-        else:
-            g = _own_graph(rng, case.n, case.kind, case.dens, case.F0, case.feats)
-        g.label = int(rng.integers(0, case.C))
-        em = g.edge_mat.numpy()
-        # graph.neighbors as util.py:86-90 leaves them, read by neighbour "max" only
-        nb = [[] for _ in range(case.n)]
-        for a, b in zip(em[0].tolist(), em[1].tolist()):
-            nb[a].append(b)
-        g.neighbors = nb
-        g.max_neighbor = max((len(x) for x in nb), default=0)
-        gs.append(g)
+    # (isolated nodes in the first graph only, as the eval envelope has them)
+    gs = [_case_graph(case, rng, case.kind if case.kind != "iso" or j == 0 else "sym") for j in range(case.B)]
     return gs, rng
 
 
@@ -470,3 +482,173 @@ def expected_route(case):
     # the hand-over is used by the loss that recognises it; any other loss, and a declined unit, re-reads the layers
     disc.append("gnm_disc_unit_scale:0" if case.disc == "unit" and case.loss == "infomax" else "gnm_disc_score_bwd:0")
     return dict(fwd=fwd, lin=lin, bwd=bwd, head=["gnm_head_fwd:%d" % case.head], disc=disc)
+
+
+# --------------------------------------------------------------------------- pools and selection sequences (replays)
+# tests/test_gpu_replay_envelope.py replays every case's step from captured hipGraphs on a SEQUENCE of batches and
+# compares each replay with the eager step byte for byte; tests/test_replay_envelope_host.py checks the pools.
+REPLAY_KINDS = ("step", "fused", "train", "eval")
+# the product condition that keeps a case out of a replay kind; None: the case replays.  The one table both halves read.
+#   step   gnm.graphs.CapturedTrainStep, both buffer forms       fused  gnm.train.FusedTrainStep(capture=True)
+#   train  model(batch) in train mode (gnm.graphs.CapturedTrain)  eval   model(batch) in eval mode (CapturedEval)
+
+
+def replay_exclusion(case, kind):
+    assert kind in REPLAY_KINDS, kind
+    if case.npool == "max":
+        # models/graphcnn.py forward(): `not self._spec.n_max` guards both replays; a StaticBatch carries no neighbour
+        # lists (Batch.maxnb); gnm/train.py FusedTrainStep: "needs the sum/average neighbour-pooling model"
+        return "max neighbour pooling never replays (graphcnn.py forward: not _spec.n_max; FusedTrainStep raises)"
+    if kind == "train" and case.keep:
+        return "keep_hidden: _forward_train_replay declines (graphcnn.py: sp.keep_hidden)"
+    if kind == "train" and case.sink:
+        return "a gradient sink is installed: _forward_train_replay declines (graphcnn.py: sp.grad_sink is not None)"
+    if kind == "train" and case.B > 128:
+        return "B > TRAIN_REPLAY_MAX_B"
+    if kind == "eval" and case.B > 64:
+        return "B > EVAL_REPLAY_MAX_B"
+    return None
+
+
+def pool_size(case):
+    """max(6, 3 B); six graphs where they are large (n >= 400)"""
+    return 6 if case.n >= 400 else max(6, 3 * case.B)
+
+
+Pool = collections.namedtuple("Pool", "graphs heavy selections labels perms template redraw")
+
+
+def _nnz(g):
+    return int(g.edge_mat.shape[1])
+
+
+def _heavier(case, rng, floor):
+    """a graph of the case's class with more than `floor` edges: one more of the case's generator, then single edges
+    (both directions of a pair for the undirected kinds) added where there is none"""
+    g = _case_graph(case, rng, case.kind)
+    n = case.n
+    A = np.zeros((n, n), dtype=bool)
+    em = g.edge_mat.numpy()
+    A[em[0], em[1]] = True
+    directed = case.kind in ("dir", "sparse-dir")
+    while int(A.sum()) <= floor:
+        a, b = (int(x) for x in rng.integers(0, n, 2))
+        if a == b or A[a, b]:
+            continue
+        A[a, b] = True
+        if not directed:
+            A[b, a] = True
+    src, dst = np.nonzero(A)
+    g.edge_mat = torch.from_numpy(np.ascontiguousarray(np.stack([src, dst]).astype(np.int64)))
+    _set_neighbors(g)
+    return g
+
+
+def _build_pool(key, id_, redraw):
+    case = BY_ID[id_]
+    B, count = case.B, pool_size(case)
+    graphs = list(_data(key).graphs)                 # the first B ARE the case's own graphs
+    _, rng = case_graphs(case)                       # ... and the rest continue the stream that drew them
+    for _ in range(redraw * (count - B)):            # (an anchor case's earlier draws, see _pool)
+        _case_graph(case, rng, case.kind)
+    for j in range(B, count):
+        # (kind "iso": every third pool graph has isolated nodes, so that selections of the template's class can carry
+        # one at different batch positions)
+        graphs.append(_case_graph(case, rng, case.kind if case.kind != "iso" or j % 3 == 0 else "sym"))
+    heavy = None
+    if case.kind not in ("iso", "multi"):
+        heavy = _heavier(case, rng, max(_nnz(g) for g in graphs))
+    if B == 1:
+        sel = [[0], [1], [2], [0], [5]]
+    elif case.kind == "iso":                         # (B = 2; the graphs with isolated nodes: 0 and 3)
+        sel = [[0, 1], [2, 3], [0, 0], [0, 1], [3, 1]]
+    else:
+        r = min(range(B), key=lambda j: _nnz(graphs[j]))      # (the lighter one twice: nnz_max moves as well)
+        sel = [list(range(B)), list(range(B, 2 * B)), [r, r] + list(range(2 * B, 3 * B - 2)), list(range(B)),
+               list(range(3 * B - 1, 2 * B - 1, -1))]
+    if case.kind != "regular" and B > 1:
+        # at least two of the selections 1, 2, 4 differ from the case's own batch in total edge count AND in nnz_max
+        # (the launch-sizing argument a capture freezes).  Two graphs drawn with the same edge count can spoil that: the
+        # first other choice of graphs outside the own batch takes the selection's place, 4 (descending) before 1
+        own = ([_nnz(graphs[j]) for j in sel[0]])
+        moved = lambda ids: (sum(_nnz(graphs[j]) for j in ids) != sum(own)            # noqa: E731
+                             and max(_nnz(graphs[j]) for j in ids) != max(own)
+                             and (case.kind != "iso" or 3 in ids))
+        for s, order in ((4, range(count - 1, B - 1, -1)), (1, range(B, count))):
+            if sum(moved(sel[k]) for k in (1, 2, 4)) >= 2:
+                break
+            if not moved(sel[s]):
+                sel[s] = next((list(c) for c in itertools.combinations(order, B) if moved(c)), sel[s])
+    srng = np.random.default_rng(zlib.crc32((id_ + "/selections").encode()))
+    labels, perms = [], []
+    for _ in sel:
+        labels.append(srng.integers(0, case.C, B).astype(np.int64))
+        perm = srng.permutation(B)
+        while B > 1 and np.array_equal(perm, np.arange(B)):
+            perm = srng.permutation(B)
+        perms.append(perm.astype(np.int64))
+    # the StaticBatch form is captured on the selection with the most edges in one graph: it admits every other one
+    template = max(range(len(sel)), key=lambda s: (max(_nnz(graphs[j]) for j in sel[s]), -s))
+    return Pool(tuple(graphs), heavy, tuple(tuple(s) for s in sel), tuple(labels), tuple(perms), template, redraw)
+
+
+@functools.lru_cache(maxsize=None)
+def _pool(key, id_):
+    """the pool as drawn; for an ANCHOR_CASES case the graphs beyond the case's own are redrawn further down the same
+    stream until one of the selections 1, 2, 4 keeps RELU_MARGIN under the case's parameters (which were drawn for the
+    case's own batch): the replayed step on it is compared with the fp64 oracle"""
+    if id_ not in ANCHOR_CASES:
+        return _build_pool(key, id_, 0)
+    for redraw in range(200):
+        pool = _build_pool(key, id_, redraw)
+        if any(selection_oracle(BY_ID[id_], s, pool)[1] >= RELU_MARGIN for s in (1, 2, 4)):
+            return pool
+    raise AssertionError("%s: no pool draw has a selection that keeps the ReLU margin" % id_)
+
+
+def case_pool(case):
+    """Pool(graphs, heavy, selections, labels, perms, template): pool_size(case) graphs whose first B are
+    case_data(case).graphs; `heavy`, one more graph with more edges than any of them (None for kinds "iso" and
+    "multi"), arena id len(graphs) once `graphs + [heavy]` were added in order; the selection sequence as tuples of
+    pool indices -- 0 the case's own batch, 1 disjoint from it, 2 overlapping it with one graph twice, 3 the case's own
+    batch again, 4 in descending order -- each with its own labels and non-identity permutation; and the index of the
+    selection a StaticBatch capture takes as its template.  Built once per case and never modified."""
+    return _pool(case.data or case.id, case.id)
+
+
+def selection_oracle(case, s, pool=None):
+    """(the fp64 oracle's train_step_grads on selection s with that selection's labels and permutation, the smallest
+    relative |pre-activation| under a ReLU)"""
+    from oracle import gin_oracle as O
+    d, pool = case_data(case), pool or case_pool(case)
+    ob = oracle_batch([pool.graphs[j] for j in pool.selections[s]])
+    for g, lab in zip(ob, pool.labels[s]):
+        g.label = int(lab)
+    om = O.OracleGIN(d.state, case.L, case.m, case.eps, case.gpool, case.npool, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        ref = om.train_step_grads(ob, pool.perms[s], beta=BETA,
+                                  dropout_masks=None if d.masks is None else [d.masks[l].astype(np.float64)
+                                                                              for l in range(case.L)])
+    margin = np.inf
+    for l, lc in enumerate(ref["cache"]["layers"]):
+        acts = [(lc["bn_out"][0], "batch_norms.%d" % l)]
+        acts += [(ent[2], "mlps.%d.batch_norms.%d" % (l, k)) for k, ent in enumerate(lc["mlp"]) if ent[0] == "lin_bn_relu"]
+        for (xhat, _, gamma, _), bn in acts:
+            y = xhat * gamma + d.state[bn + ".bias"].astype(np.float64)
+            margin = min(margin, float(np.abs(y).min() / np.abs(y).max()))
+    return ref, margin
+
+
+ANCHOR_CASES = ("lin-rz-wide-H64-m2", "agg-csr-H64", "agg-dir-csr-H64", "lin-generic-masked-H128-m2", "lin-sums-m2-H32")
+
+
+@functools.lru_cache(maxsize=None)
+def anchor(id_):
+    """(s, the fp64 oracle's step on selection s) of an ANCHOR_CASES case: s = 1, the first batch of the sequence that
+    is not the template -- or the first later one that keeps RELU_MARGIN, where selection 1 does not"""
+    case = BY_ID[id_]
+    for s in (1, 2, 4):
+        ref, margin = selection_oracle(case, s)
+        if margin >= RELU_MARGIN:
+            return s, ref
+    raise AssertionError("%s: no selection keeps the ReLU margin" % id_)
