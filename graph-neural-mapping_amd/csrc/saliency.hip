@@ -400,6 +400,18 @@ static int sl_layers(SlArgs& a, float* const* S, float* const* R, hipStream_t s)
     return GNM_OK;
 }
 
+// The final launch: dX [N, F0] from layer 0's S (and R), the gradient at the first Linear's output over a.B graphs.
+static int sl_final(SlArgs& a, const float* S0, const float* R0, float* dX, int ldx, hipStream_t s) {
+    a.l = 0;
+    a.Sin = S0;
+    a.Rin = R0;
+    a.Sout = nullptr; a.Rout = nullptr;
+    a.out = dX; a.ldo = ldx; a.final_launch = 1;
+    hipLaunchKernelGGL(gnm_saliency_layer_kernel<false>, dim3(a.B * a.wmax), dim3(256), 0, s, a);
+    GNM_CHECK_LAUNCH();
+    return GNM_OK;
+}
+
 extern "C" int gnm_saliency(const uint32_t* adj_bits, const int64_t* b_tbits_off, const int32_t* node_off,
                             const int32_t* rowptr, const int64_t* b_rp_off, int B, int n_max, long long N, int F0, int H,
                             int L, int m, int C, int cls, int average, int self_loop, int graph_avg,
@@ -416,14 +428,53 @@ extern "C" int gnm_saliency(const uint32_t* adj_bits, const int64_t* b_tbits_off
     float* R[kSlMaxL];
     sl_pingpong(S, R, scratch, N, H, L, average && !self_loop);
     if ((rc = sl_layers<false>(a, S, R, s)) != GNM_OK) return rc;
-    a.l = 0;                                      // the final launch: dX from layer 0's S (and R)
-    a.Sin = S[0];
-    a.Rin = R[0];
-    a.Sout = nullptr; a.Rout = nullptr;
-    a.out = dX; a.ldo = ldx; a.final_launch = 1;
-    hipLaunchKernelGGL(gnm_saliency_layer_kernel<false>, dim3(B * a.wmax), dim3(256), 0, s, a);
-    GNM_CHECK_LAUNCH();
-    return GNM_OK;
+    return sl_final(a, S[0], R[0], dX, ldx, s);
+}
+
+extern "C" int gnm_intgrad_reduce(const float* Sv, const float* Rv, const int32_t* node_off, int B, int n_max,
+                                  const float* weights, int K, int H, float* Sbar, float* Rbar, hipStream_t s);
+extern "C" int gnm_intgrad_scale(float* attr, int lda, const float* X, int ldx, const float* base, int ldb,
+                                 const int32_t* node_off, int B, int n_max, int F0, hipStream_t s);
+
+// Integrated gradients of class cls (csrc/intgrad.hip, include/gnm_hip.h): gnm_saliency's layer launches over the K B
+// virtual graphs (v_*: their descriptors, K consecutive ones per source graph, over the forward that `table` describes),
+// layer 0's S (and R) reduced over the steps with the quadrature weights, then ONE final launch over the B source
+// graphs and the (X - baseline) pass.  The checks are gnm_saliency's, in its order, on the source batch and then on the
+// virtual one.
+extern "C" int gnm_integrated_gradients(const uint32_t* adj_bits, const int64_t* b_tbits_off, const int32_t* node_off,
+                                        const int32_t* rowptr, const int64_t* b_rp_off, int B, int n_max, long long N,
+                                        int F0, int H, int L, int m, int C, int cls, int average, int self_loop,
+                                        int graph_avg, const long long* table, const float* eps, float* scratch,
+                                        const int64_t* v_tbits_off, const int32_t* v_node_off, const int64_t* v_rp_off,
+                                        int K, const float* weights, const float* X, int ldxin, const float* base,
+                                        int ldb, int n_base, float* attr, int lda, void* stream) {
+    if (B <= 0) return GNM_OK;
+    SlArgs a, v;
+    const bool bad_shape = F0 < 1 || F0 > gnm_linear_max_k(H);
+    const bool bad_arg = lda < F0 || ldxin < F0 || K < 1 || (base && (ldb < F0 || n_base < n_max));
+    const bool null_arg = !attr || !X || !weights || !v_tbits_off || !v_node_off || !v_rp_off;
+    const long long row_floats = lda > H ? lda : H;
+    int rc = sl_setup(a, adj_bits, b_tbits_off, node_off, rowptr, b_rp_off, B, n_max, N, H, L, m, C, cls, average,
+                      self_loop, graph_avg, table, eps, scratch, bad_shape, bad_arg, null_arg, false, row_floats);
+    if (rc != GNM_OK) return rc;
+    const long long Nv = N * K;                   // virtual rows are indexed in int32, as node_off is
+    if (K > (1 << 20) || Nv >= (1LL << 31) || (long long)B * K >= (1LL << 31) / a.wmax) return GNM_ERR_UNSUPPORTED;
+    rc = sl_setup(v, adj_bits, v_tbits_off, v_node_off, rowptr, v_rp_off, B * K, n_max, Nv, H, L, m, C, cls, average,
+                  self_loop, graph_avg, table, eps, scratch, false, false, false,
+                  (reinterpret_cast<uintptr_t>(scratch) & 15) != 0, H);
+    if (rc != GNM_OK) return rc;
+    a.F0 = F0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool need_r = average && !self_loop;
+    float* S[kSlMaxL];
+    float* R[kSlMaxL];
+    sl_pingpong(S, R, scratch, Nv, H, L, need_r);
+    if ((rc = sl_layers<false>(v, S, R, s)) != GNM_OK) return rc;
+    float* Sbar = scratch + 4 * Nv * H;
+    float* Rbar = need_r ? Sbar + N * H : nullptr;
+    if ((rc = gnm_intgrad_reduce(S[0], R[0], node_off, B, n_max, weights, K, H, Sbar, Rbar, s)) != GNM_OK) return rc;
+    if ((rc = sl_final(a, Sbar, Rbar, attr, lda, s)) != GNM_OK) return rc;
+    return gnm_intgrad_scale(attr, lda, X, ldxin, base, ldb, node_off, B, n_max, F0, s);
 }
 
 // The gradient class activation map of class cls (graphcnn.py:284,288-289): gcam[v] = sum_l <dscore/dh_l[v], h_l[v]>.

@@ -86,6 +86,10 @@ SIGNATURES = {
     "gnm_occlusion_scratch_floats": (_ll, [_ll, _ll, _i, _i, _i]),
     "gnm_occlusion": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _ll, _ll, _p, _i, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i,
                            _f, _p, _p, _p, _p, _ll, _p]),
+    "gnm_integrated_gradients_scratch_floats": (_ll, [_ll, _i, _i]),
+    "gnm_intgrad_z0": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _i, _p]),
+    "gnm_integrated_gradients": (_i, [_p, _p, _p, _p, _p, _i, _i, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p,
+                                      _p, _p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _p]),
     "gnm_class_activation_table_words": (_ll, [_i]),
     "gnm_class_activation_max_classes": (_i, []),
     "gnm_class_activation": (_i, [_p, _i, _i, _ll, _i, _i, _i, _p, _i, _i, _p, _p, _ll, _p]),

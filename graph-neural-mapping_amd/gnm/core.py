@@ -424,11 +424,15 @@ class _LinSave:
 _LayerSave = collections.namedtuple("_LayerSave", "h_in pooled lins aux")
 
 
-def encoder_forward(spec, batch, X, P, training, update_running, P0=None):
+def encoder_forward(spec, batch, X, P, training, update_running, P0=None, z0=None):
     """The L GIN layers + readout.  P: dict of parameter/buffer tensors keyed by the
     reference's state_dict names.  P0: the arena's cached parameter-independent part of layer 0's
-    aggregation (GraphArena.features_and_agg0) or None.  Returns (hidden list, g_f [B, L*H], saved)."""
-    dev = X.device
+    aggregation (GraphArena.features_and_agg0) or None.  z0: the pre-BatchNorm output [N, H] of layer 0's first Linear,
+    given (eval mode only; integrated_gradients_hip): layer 0's aggregation and that Linear are not run and X is not
+    read (it may be None).  Returns (hidden list, g_f [B, L*H], saved)."""
+    if z0 is not None and training:
+        raise GnmError("encoder_forward: z0 is an eval-mode entry")
+    dev = X.device if z0 is None else z0.device
     N, B = batch.N, batch.B
     L, m = spec.L, spec.m
     H = P["batch_norms.0.weight"].shape[0]
@@ -448,10 +452,13 @@ def encoder_forward(spec, batch, X, P, training, update_running, P0=None):
               "gnm_bn_relu_readout")                                          # graphcnn.py:163-166, 228-229
 
     for l in range(L):
-        F_l = h.shape[1]
+        given = l == 0 and z0 is not None         # layer 0 starts behind its first Linear
+        F_l = h.shape[1] if not given else 0
         eps_ptr = P["eps"].data_ptr() + 4 * l if spec.learn_eps else None
         aux = None          # max pooling: what its backward needs
-        if l == 0 and P0 is not None:
+        if given:
+            pooled = None
+        elif l == 0 and P0 is not None:
             # A X [/deg] comes from the arena's cache; only the (1 + eps_0) X self term depends on a parameter
             pooled = torch.addcmul(P0, h, P["eps"][0:1] + 1.0) if spec.learn_eps else P0
         else:
@@ -486,10 +493,13 @@ def encoder_forward(spec, batch, X, P, training, update_running, P0=None):
                 W, bias = P[f"mlps.{l}.linears.{k}.weight"], P[f"mlps.{l}.linears.{k}.bias"]
             bn = f"batch_norms.{l}" if k == m - 1 else f"mlps.{l}.batch_norms.{k}"
             Hk, K = W.shape
-            z = torch.empty((N, Hk), **f32)
             grid = lib.gnm_linear_grid(N)
             stats = torch.empty((grid, 2, Hk), dtype=torch.float64, device=dev) if training else None
-            _linear(x_in, W, 0, bias, z, N, K, Hk, pro, stats)
+            if given and k == 0:
+                z = z0
+            else:
+                z = torch.empty((N, Hk), **f32)
+                _linear(x_in, W, 0, bias, z, N, K, Hk, pro, stats)
             sv = _LinSave()
             sv.x_in, sv.pro, sv.z, sv.K, sv.H = x_in, pro, z, K, Hk
             sv.scale, sv.shift, sv.mean, sv.rstd = (torch.empty(Hk, **f32) for _ in range(4))
@@ -961,6 +971,102 @@ def occlusion_hip(spec, batch, X, P, classes, out=None):
                                         int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS,
                                         table.data_ptr(), P["eps"].data_ptr() if spec.learn_eps else None,
                                         scratch.data_ptr(), dst.data_ptr(), out.stride(0), _stream()), "gnm_occlusion")
+            g0 = g1
+    return out
+
+
+# integrated_gradients_hip's device arrays per chunk of source graphs stay under this many bytes: the virtual batch's
+# forward keeps every Linear's z and every layer's aggregation, (m L + L - 1) K N H floats, next to 4 K N H of scratch.
+# K = 32, 8 graphs of 400 nodes, H = 64, m = 2, L = 5: 0.26 GB of z, 0.47 GB in all.
+INTGRAD_SCRATCH_BYTES = 2 << 30
+
+
+def _intgrad_floats(rows, H, L, m, K):
+    """floats integrated_gradients_hip holds for a chunk of `rows` source rows: z0 and the forward's saved arrays over
+    the K rows virtual rows, and gnm_integrated_gradients' scratch"""
+    return (m * L + L - 1) * K * rows * H + int(lib.gnm_integrated_gradients_scratch_floats(rows, H, K))
+
+
+def integrated_gradients_hip(spec, batch, X, P, classes, alphas, weights, baseline=None, out=None):
+    """Integrated gradients of a whole batch for every c in `classes` (include/gnm_hip.h gnm_integrated_gradients):
+    out[ci, row] = (X - x')[row] * sum_k weights[k] d score[:, c] / d X at x' + alphas[k] (X - x'), x' = `baseline`
+    ([n, F0], shared by the graphs, which then all have n nodes) or zeros.  Per batch P = pool(X W0^T) (and Q of the
+    baseline): the split-precision Linear, then the layer-0 aggregation at width H (agg_launch) -- pool and W0 commute.
+    Then per chunk of source graphs whose arrays fit INTGRAD_SCRATCH_BYTES (never a part of one graph's steps):
+    gnm_intgrad_z0, the rest of the eval forward over the K B virtual graphs (encoder_forward from z0; the virtual
+    batch lists every arena graph K times, so it shares the source graphs' adjacency), and per class
+    gnm_integrated_gradients.  The shapes saliency_decline(dx=True) takes.  Parameters, buffers and the numpy RNG are
+    not touched.  Returns a float32 [len(classes), N, F0] tensor (`out` when given)."""
+    dev = launch_device(X, P["eps"])
+    L, m = spec.L, spec.m
+    N, B = batch.N, batch.B
+    H = P["batch_norms.0.weight"].shape[0]
+    Cn = P["linears_prediction.0.weight"].shape[0]
+    F0 = X.shape[1]
+    a32 = np.ascontiguousarray(alphas, dtype=np.float64).astype(np.float32)
+    w32 = np.ascontiguousarray(weights, dtype=np.float64).astype(np.float32)
+    K = int(a32.shape[0])
+    if K < 1 or a32.ndim != 1 or w32.shape != a32.shape:
+        raise GnmError("integrated gradients need K >= 1 nodes and as many weights")
+    X = X.contiguous()
+    out = _out_array(out, (len(classes), N, F0), dev)
+    offs = np.asarray(batch.node_off_host, dtype=np.int64)
+    ns = np.diff(offs)
+    arena = batch.arena
+    with torch.no_grad(), _stream_scope(dev):
+        f32 = dict(dtype=torch.float32, device=dev)
+        lin0 = "mlps.0.linear" if m == 1 else "mlps.0.linears.0"
+        W0, b0 = P[lin0 + ".weight"], P[lin0 + ".bias"].contiguous()
+        al, wt = arena._upload(torch.as_tensor(a32)), arena._upload(torch.as_tensor(w32))
+        eps_ptr = P["eps"].data_ptr() if spec.learn_eps else None
+
+        def pooled_product(src, rows):
+            """pool(src) W0^T as pool(src W0^T): src is [rows, F0] (the batch's features, or ONE graph's baseline)"""
+            XW = torch.empty((rows, H), **f32)
+            _linear(src, W0, 0, None, XW, rows, F0, H, None, None)
+            if rows != N:
+                XW = XW.repeat(B, 1)
+            Pz = torch.empty((N, H), **f32)
+            _agg(batch, XW, Pz, H, eps_ptr, spec, backward=False)
+            return Pz
+
+        Pz = pooled_product(X, N)
+        Qz = None
+        if baseline is not None:
+            baseline = baseline.to(device=dev, dtype=torch.float32).contiguous()
+            if baseline.dim() != 2 or baseline.shape[1] != F0 or (ns != baseline.shape[0]).any():
+                raise GnmError("the baseline must be [n, %d] with n the node count of every graph" % F0)
+            Qz = pooled_product(baseline, int(baseline.shape[0]))
+        gh = batch.gids.cpu().numpy()
+        g0 = 0
+        while g0 < B:
+            g1 = g0 + 1                     # the longest run of graphs whose arrays fit the budget (at least one)
+            while g1 < B and 4 * _intgrad_floats(int(offs[g1 + 1] - offs[g0]), H, L, m, K) <= INTGRAD_SCRATCH_BYTES:
+                g1 += 1
+            r0, rows = int(offs[g0]), int(offs[g1] - offs[g0])
+            sub = batch if (g0, g1) == (0, B) else arena.batch_from_gids(gh[g0:g1])
+            vb = arena.batch_from_gids(np.repeat(gh[g0:g1], K))
+            z0 = torch.empty((K * rows, H), **f32)
+            check(lib.gnm_intgrad_z0(Pz[r0:].data_ptr(), Pz.stride(0), Qz[r0:].data_ptr() if Qz is not None else None,
+                                     Qz.stride(0) if Qz is not None else 0, b0.data_ptr(), sub.node_off.data_ptr(),
+                                     sub.B, sub.n_max, al.data_ptr(), K, H, z0.data_ptr(), z0.stride(0), _stream()),
+                  "gnm_intgrad_z0")
+            _, _, saved = encoder_forward(spec, vb, None, P, training=False, update_running=False, z0=z0)
+            table = torch.tensor(_saliency_table_words(spec, P, saved), dtype=torch.int64).pin_memory().to(
+                dev, non_blocking=True)
+            scratch = torch.empty(int(lib.gnm_integrated_gradients_scratch_floats(rows, H, K)), **f32)
+            for ci, c in enumerate(classes):
+                dst = out[ci, r0:r0 + rows]
+                with _timed("integrated_gradients_hip", B=sub.B, N=rows, F0=F0, H=H, K=K):
+                    check(lib.gnm_integrated_gradients(
+                        *sub.bits_ptrs(transposed=True), sub.node_off.data_ptr(), *sub.deg_ptrs(), sub.B, sub.n_max,
+                        rows, F0, H, L, m, Cn, int(c), int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg),
+                        table.data_ptr(), eps_ptr, scratch.data_ptr(), vb.t_bits_off.data_ptr(),
+                        vb.node_off.data_ptr(), vb.rp_off.data_ptr(), K, wt.data_ptr(), X[r0:].data_ptr(), X.stride(0),
+                        ptr(baseline), baseline.stride(0) if baseline is not None else 0,
+                        int(baseline.shape[0]) if baseline is not None else 0, dst.data_ptr(), out.stride(1),
+                        _stream()), "gnm_integrated_gradients")
+            del saved, table, scratch, z0
             g0 = g1
     return out
 

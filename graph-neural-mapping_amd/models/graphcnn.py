@@ -34,8 +34,9 @@ from mlp import MLP  # noqa: E402
 from discriminator import Discriminator  # noqa: E402
 from gnm.arena import GraphArena  # noqa: E402
 from gnm.core import (DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, edge_saliency_hip,  # noqa: E402
-                      eval_forward_fused, eval_fused_ok, launch_device, occlusion_decline, occlusion_hip,
-                      saliency_decline, saliency_hip, saliency_maps_hip)
+                      eval_forward_fused, eval_fused_ok, integrated_gradients_hip, launch_device, occlusion_decline,
+                      occlusion_hip, saliency_decline, saliency_hip, saliency_maps_hip)
+from gnm.intgrad import quadrature  # noqa: E402
 
 __all__ = ["GIN_InfoMaxReg", "GraphCNN", "MLP", "Discriminator"]
 
@@ -556,10 +557,103 @@ class GIN_InfoMaxReg(nn.Module):
         return self._clean_graphs_apart(chunk, batch, bad, dst, (len(classes), batch.N),
                                         lambda sub, Xs: occlusion_hip(self._spec, sub, Xs, P, classes))
 
-    def _clean_graphs_apart(self, chunk, batch, bad, dst, shape, run):
+    def integrated_gradients(self, graphs, cls, steps=32, baseline=None, method="midpoint", batch_size=8,
+                             return_scores=False):
+        """Integrated-gradients attribution of many graphs in batches: the path method for ReLU networks, whose
+        attributions add up to score(X) - score(baseline).  With x' the baseline, (alpha_k, w_k), k < K = steps, the
+        quadrature of `method` on [0, 1] (gnm/intgrad.py) and score_c the eval logit c_logit[:, c] of forward()
+        (BatchNorm on its running statistics, no dropout -- the score of saliency() and occlusion()):
+
+            attr[c, g] = (X_g - x') * sum_k w_k d score_c / d X (x' + alpha_k (X_g - x'))          [n_g, F0], fp32
+
+        baseline: None for zeros (natural for one-hot node features, where the gradient at the input itself says
+        least), or ONE [n, F0] float array or tensor shared by all graphs, which then all have n nodes.  method:
+        "midpoint" (alpha_k = (k + 1/2) / K, w = 1 / K), "trapezoid" (endpoints included, K >= 2) or "gausslegendre".
+
+        No copy of a graph and no rescaled feature array is built: every (graph, step) pair runs as a virtual graph
+        over the source graph's adjacency, layer 0 is formed from one product per source graph (it is affine in alpha),
+        and the steps are summed at hidden width before the one input-width launch per source graph
+        (csrc/intgrad.hip, include/gnm_hip.h gnm_integrated_gradients).
+
+        cls: an int, or a sequence of ints; one forward per batch serves all of them.  Returns a float32 device tensor
+        [len(graphs), n, F0] for an int `cls` and [len(cls), len(graphs), n, F0] for a sequence; for graphs of
+        different node counts a list of [n_g, F0] tensors (a list of such lists for a sequence `cls`), as saliency()
+        lays them out.  return_scores=True returns (attr, base, base0, delta): base[c, g] = score_c(X_g) and
+        base0[c, g] = score_c(x'), both from the model's ordinary eval forward on the batch, and
+        delta[c, g] = sum attr[c, g] - (base - base0), the completeness residual of the quadrature, in fp32
+        ([len(graphs)] each for an int `cls`).
+
+        The shapes saliency()'s kernel takes; any other batch raises ValueError naming the condition (max pooling,
+        n > 416 or no bit adjacency, hidden_dim not in {32, 64, 128}, average pooling with learned eps and an isolated
+        node, ...), as do steps < 1 (< 2 for "trapezoid"), an unknown method, a baseline of the wrong shape or with a
+        non-finite entry, and a shared baseline with graphs of different node counts.  A graph with a non-finite
+        feature gets an all-NaN map; its batch-mates are unaffected.  There is no CPU fallback.
+
+        The K virtual copies of a batch hold (m L + L + 3) K N hidden_dim floats on the device (0.47 GB at K = 32 for 8
+        graphs of 400 nodes, hidden_dim 64, 5 layers of 2 Linears), hence the small default batch; a larger batch is run
+        in chunks of whole graphs under gnm/core.py INTGRAD_SCRATCH_BYTES.  The result is bitwise the same run to run
+        (no atomics, fixed summation orders); it may differ in the last bits between batch sizes, because the forward
+        chooses its aggregation kernel per batch.  No parameter .grad, BatchNorm buffer or numpy RNG state is touched,
+        and the train / eval mode is restored on exit."""
+        alphas, weights = quadrature(method, steps)
+        F0 = self.mlps[0].linear.in_features if self.num_mlp_layers == 1 else self.mlps[0].linears[0].in_features
+        if baseline is not None and len(graphs):
+            baseline = torch.as_tensor(np.asarray(baseline) if not torch.is_tensor(baseline) else baseline)
+            if not baseline.dtype.is_floating_point:
+                raise ValueError("integrated_gradients: the baseline must be a float array")
+            baseline = baseline.detach().to(device=self.eps.device, dtype=torch.float32)
+            if any(len(g.g) != len(graphs[0].g) for g in graphs):
+                raise ValueError("integrated_gradients: a shared baseline needs graphs of one node count")
+            if tuple(baseline.shape) != (len(graphs[0].g), F0):
+                raise ValueError("integrated_gradients: the baseline must be [%d, %d], got %s"
+                                 % (len(graphs[0].g), F0, list(baseline.shape)))
+            if not bool(torch.isfinite(baseline).all()):
+                raise ValueError("integrated_gradients: the baseline has a non-finite entry")
+        scores = [] if return_scores else None
+        attr = self._interpret("integrated_gradients", graphs, cls, batch_size, (F0,), functools.partial(
+            self._intgrad_batch, alphas=alphas, weights=weights, baseline=baseline, scores=scores))
+        if not return_scores:
+            return attr
+        single = isinstance(cls, (int, np.integer))
+        base = torch.cat([s[0] for s in scores], 1)         # [len(classes), len(graphs)]
+        base0 = torch.cat([s[1] for s in scores], 1)
+        if torch.is_tensor(attr):
+            total = attr.sum((-2, -1))
+        elif single:
+            total = torch.stack([a.sum() for a in attr])
+        else:
+            total = torch.stack([torch.stack([a.sum() for a in row]) for row in attr])
+        if single:
+            base, base0 = base[0], base0[0]
+        return attr, base, base0, total - (base - base0)
+
+    def _intgrad_batch(self, chunk, batch, P, classes, dst, alphas, weights, baseline, scores):
+        """integrated_gradients() of one batch: [len(classes), N, F0] (dst when given); with `scores` a list, the
+        batch's (base, base0) scores [len(classes), B] are appended to it"""
+        X = batch.arena.features(batch).detach()
+        launch_device(X, P["eps"])                          # no CPU fallback: GnmError before any shape question
+        why = saliency_decline(self._spec, batch, X, P, dx=True)
+        if why is not None:
+            raise ValueError("integrated_gradients does not cover this batch: %s" % why)
+        if scores is not None:
+            ident = np.arange(batch.B, dtype=np.int64)
+            X0 = torch.zeros_like(X) if baseline is None else baseline.repeat(batch.B, 1)
+            with torch.no_grad():
+                c1 = self._run(batch, X, ident, want_disc=False)[0]
+                c0 = self._run(batch, X0, ident, want_disc=False)[0]
+            scores.append((c1.detach()[:, classes].t().contiguous(), c0.detach()[:, classes].t().contiguous()))
+        run = functools.partial(integrated_gradients_hip, alphas=alphas, weights=weights, baseline=baseline)
+        bad = _nonfinite_graphs(batch, X)
+        if bad is None:
+            return run(self._spec, batch, X, P, classes, out=dst)
+        return self._clean_graphs_apart(chunk, batch, bad, dst, (len(classes), batch.N, X.shape[1]),
+                                        lambda sub, Xs: run(self._spec, sub, Xs, P, classes), crop=False)
+
+    def _clean_graphs_apart(self, chunk, batch, bad, dst, shape, run, crop=True):
         """The gradient class activation and edge maps of a batch with non-finite graphs (`bad`): an all-NaN map for
         each of those (its ReLU masks are meaningless), and the others run(sub, X) on a batch of their own, so their
-        maps are those of a clean batch, scattered into place.  Returns dst, or a new array of `shape`, [C, N, ...]."""
+        maps are those of a clean batch, scattered into place.  crop: the last axis holds n_j entries for graph j (an
+        edge map's columns; False for a feature axis).  Returns dst, or a new array of `shape`, [C, N, ...]."""
         out = dst if dst is not None else torch.empty(shape, dtype=torch.float32, device=self.eps.device)
         out.fill_(float("nan"))
         good = [j for j in range(batch.B) if not bad[j]]
@@ -568,7 +662,7 @@ class GIN_InfoMaxReg(nn.Module):
             r = run(sub, sub.arena.features(sub).detach())
             offs, so = np.asarray(batch.node_off_host), np.asarray(sub.node_off_host)
             for k, j in enumerate(good):
-                nj = int(so[k + 1] - so[k])
+                nj = int(so[k + 1] - so[k]) if crop else None
                 # (the last axis cropped to the graph's n_j: an edge map's columns; a no-op for a [C, N] map)
                 out[:, offs[j]:offs[j + 1]][..., :nj] = r[:, so[k]:so[k + 1]][..., :nj]
         return out

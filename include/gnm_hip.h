@@ -407,6 +407,41 @@ int gnm_occlusion(const uint32_t* adj_bits, const int64_t* b_bits_off, const int
                   const int* classes_host, int n_classes, int average, int self_loop, int graph_avg, float bn_eps,
                   const long long* table, const float* eps, float* scratch, float* out, long long ldo, void* stream);
 
+/* ---- Eval-mode integrated gradients (csrc/intgrad.hip over csrc/saliency.hip's layer launches) ----------------------
+ * attr[node_off[g] + r, :] = (X - x')[g, r, :] * sum_k w_k d score[cls] / d X (x' + alpha_k (X_g - x'))[r, :] for every
+ * graph g of a batch, x' the baseline (zeros, or one [n_base, F0] block every graph shares), (alpha_k, w_k), k < K, a
+ * quadrature on [0, 1].  A VIRTUAL graph is (source graph g, step k): n_g rows over g's own bit rows, transposed bits
+ * and rowptr; virtual graph g K + k owns rows K node_off[g] + k n_g .. + n_g of every virtual array.  No graph copy and
+ * no [K N, F0] feature array is formed.
+ *
+ * gnm_intgrad_z0: the first Linear's pre-BatchNorm output of layer 0 for every virtual row,
+ * Z[(g, k), r] = alpha_k P[g, r] + (1 - alpha_k) Q[g, r] + bias, with P = pool(X) W0^T and Q = pool(x') W0^T [N, H] of
+ * the SOURCE graphs (pool: the model's layer-0 aggregation with its self term and degree division; Q NULL: zeros) --
+ * layer 0 is affine in alpha because the adjacency is shared.  Z: OUTPUT [K N, H].  P, Q, bias, Z 16-byte aligned with
+ * leading dimensions multiples of 4 (GNM_ERR_UNSUPPORTED otherwise, as for H not in {32, 64, 128} or n_max outside
+ * 1..416); GNM_ERR_BAD_ARG: K < 1, a leading dimension < H, a NULL array (alphas included).
+ *
+ * gnm_integrated_gradients, after the rest of the eval forward has run over the K B virtual graphs (`table`:
+ * gnm_saliency's table over THAT forward): gnm_saliency's L layer launches over the virtual batch (v_tbits_off,
+ * v_node_off, v_rp_off: its [K B] / [K B + 1] descriptors), then Dbar[g, r] = sum_k w_k dZ0[(g, k), r] at width H in
+ * fixed k order, then gnm_saliency's final launch ONCE per source graph (it is linear in dZ0 and the adjacency is common
+ * to the steps of a graph), then attr *= X - x'.  The other arguments are gnm_saliency's, of the SOURCE batch; weights:
+ * [K] DEVICE floats; X: [N, F0] the source features; base: NULL or [n_base, F0] with n_base >= n_max; attr: OUTPUT
+ * [N, F0].  scratch: gnm_integrated_gradients_scratch_floats(N, H, K) floats, 16-byte aligned.
+ * GNM_ERR_UNSUPPORTED / GNM_ERR_BAD_ARG (nothing launched) as gnm_saliency, in its order; BAD_ARG also for K < 1,
+ * lda / ldx < F0, ldb < F0 or n_base < n_max with a baseline, NULL weights / X / attr / v_*; UNSUPPORTED also for
+ * K N >= 2^31.  No atomics, every sum in a fixed order: bitwise reproducible. */
+long long gnm_integrated_gradients_scratch_floats(long long N, int H, int K);
+int gnm_intgrad_z0(const float* P, int ldp, const float* Q, int ldq, const float* bias, const int32_t* node_off, int B,
+                   int n_max, const float* alphas, int K, int H, float* Z, int ldz, void* stream);
+int gnm_integrated_gradients(const uint32_t* adj_bits, const int64_t* b_tbits_off, const int32_t* node_off,
+                             const int32_t* rowptr, const int64_t* b_rp_off, int B, int n_max, long long N, int F0, int H,
+                             int L, int m, int C, int cls, int average, int self_loop, int graph_avg,
+                             const long long* table, const float* eps, float* scratch, const int64_t* v_tbits_off,
+                             const int32_t* v_node_off, const int64_t* v_rp_off, int K, const float* weights,
+                             const float* X, int ldx, const float* base, int ldb, int n_base, float* attr, int lda,
+                             void* stream);
+
 /* ---- Infomax discriminator (discriminator.py:19-38, graphcnn.py:233-246) ------------
  * hptrs_host: HOST array of L device pointers to the per-layer [N,H] hidden states
  * (n_f is never concatenated).  A layer may instead be given as the pre-BatchNorm output Z_l of its last Linear
