@@ -27,11 +27,9 @@
 //            backward terms and BatchNorm statistics of gnm_agg_bwd_stats, 128-B row segments stored.
 // The row-block -> wave map is static, so every reduction (column statistics, d eps, readout) has a fixed order.
 #include "gnm_agg_args.h"
+#include "gnm_rowblock.h"
 #include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
 
 #ifndef GNM_AGGM_WAVES
@@ -59,11 +57,6 @@ extern "C" void gnm_debug_set_aggm_stamps(void* p) { g_aggm_stamps = reinterpret
 
 // words per HALF row of the bit adjacency (layout: see gnm_adj_bits_build below)
 __host__ __device__ static inline int aggm_half_words(int W) { return (((W + 1) >> 1) + 3) & ~3; }
-
-__device__ __forceinline__ unsigned bf16_pair_hi(unsigned lo_word, unsigned hi_word) {
-    // (top 16 bits of hi_word) : (top 16 bits of lo_word)
-    return __builtin_amdgcn_perm(hi_word, lo_word, 0x07060302u);
-}
 
 // AVG: neighbor_pooling_type "average" (the epilogue then also loads degrees / the raw input); decided by the launcher
 // so that the "sum" forms carry none of it.
@@ -114,13 +107,7 @@ __global__ void __launch_bounds__(kAggmThreads, 4) gnm_aggm_kernel(const AggArgs
     const int rbA = role, rbB = role + kAggmWaves;
     const bool two = rbB < W;
     const bool has_rows = p.y && rbA < W;
-    if (tid < 16) {          // nibble e -> bf16 (bit 0, bit 1, bit 2, bit 3) as two words
-        const unsigned one = 0x3F80u;
-        u32x2 v;
-        v.x = ((tid & 1) ? one : 0u) | ((tid & 2) ? one << 16 : 0u);
-        v.y = ((tid & 4) ? one : 0u) | ((tid & 8) ? one << 16 : 0u);
-        *reinterpret_cast<u32x2*>(lut + 8 * tid) = v;
-    }
+    rb_lut_init(lut, tid);
 
     // Statistics form: the per-row gradient of the discriminator's first score (one float per node) goes to LDS, one
     // coalesced load, instead of sixteen 4-byte global loads per row block and lane in the epilogue.  Requested here,
@@ -184,11 +171,11 @@ __global__ void __launch_bounds__(kAggmThreads, 4) gnm_aggm_kernel(const AggArgs
         // "load; s_waitcnt vmcnt(0)" AHEAD of the tile loads: every workgroup began by sitting out a memory round trip.
         const uint32_t* gbits = p.adj_bits + p.b_bits_off[b];
         const int second = HPW > 4 ? 1 : 0;
-        const u32x4* ra = reinterpret_cast<const u32x4*>(gbits + (size_t)(min(rbA, W - 1) * 32 + i) * (2 * HPW) + h * HPW);
-        const u32x4* rb = reinterpret_cast<const u32x4*>(gbits + (size_t)((two ? rbB : min(rbA, W - 1)) * 32 + i) * (2 * HPW) + h * HPW);
+        const gnm_u32x4* ra = reinterpret_cast<const gnm_u32x4*>(gbits + (size_t)(min(rbA, W - 1) * 32 + i) * (2 * HPW) + h * HPW);
+        const gnm_u32x4* rb = reinterpret_cast<const gnm_u32x4*>(gbits + (size_t)((two ? rbB : min(rbA, W - 1)) * 32 + i) * (2 * HPW) + h * HPW);
         // (12 bytes of the second piece: its last word would be steps 28-31, which no graph of <= 416 nodes has -- and a
         //  loaded register the compiler knows to be dead is reused at once, behind a vmcnt(0) for the write-after-write)
-        const u32x4 a0 = ra[0], b0 = rb[0];
+        const gnm_u32x4 a0 = ra[0], b0 = rb[0];
         const u32x3 a1 = *reinterpret_cast<const u32x3*>(ra + second), b1 = *reinterpret_cast<const u32x3*>(rb + second);
 #pragma unroll
         for (int j = 0; j < 4; ++j) { pkA[j] = a0[j]; pkB[j] = b0[j]; }
@@ -243,20 +230,16 @@ __global__ void __launch_bounds__(kAggmThreads, 4) gnm_aggm_kernel(const AggArgs
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float f = c == 0 ? v[u][r].x : (c == 1 ? v[u][r].y : (c == 2 ? v[u][r].z : v[u][r].w));
-                    const unsigned a1 = __float_as_uint(f) & 0xFFFF0000u;
-                    const float r1 = f - __uint_as_float(a1);
-                    const unsigned a2 = __float_as_uint(r1) & 0xFFFF0000u;
-                    const float r2 = r1 - __uint_as_float(a2);
-                    x0[r] = a1; x1[r] = a2; x2[r] = __float_as_uint(r2);
+                    gnm_split3(f, x0[r], x1[r], x2[r]);
                 }
-                u32x2 w0, w1, w2;
-                w0.x = bf16_pair_hi(x0[0], x0[1]); w0.y = bf16_pair_hi(x0[2], x0[3]);
-                w1.x = bf16_pair_hi(x1[0], x1[1]); w1.y = bf16_pair_hi(x1[2], x1[3]);
-                w2.x = bf16_pair_hi(x2[0], x2[1]); w2.y = bf16_pair_hi(x2[2], x2[3]);
+                gnm_u32x2 w0, w1, w2;
+                w0.x = gnm_bf16_pair(x0[0], x0[1]); w0.y = gnm_bf16_pair(x0[2], x0[3]);
+                w1.x = gnm_bf16_pair(x1[0], x1[1]); w1.y = gnm_bf16_pair(x1[2], x1[3]);
+                w2.x = gnm_bf16_pair(x2[0], x2[1]); w2.y = gnm_bf16_pair(x2[2], x2[3]);
                 char* dst = smem + base + c * 16;
-                *reinterpret_cast<u32x2*>(dst) = w0;
-                *reinterpret_cast<u32x2*>(dst + plane_bytes) = w1;
-                *reinterpret_cast<u32x2*>(dst + 2u * plane_bytes) = w2;
+                *reinterpret_cast<gnm_u32x2*>(dst) = w0;
+                *reinterpret_cast<gnm_u32x2*>(dst + plane_bytes) = w1;
+                *reinterpret_cast<gnm_u32x2*>(dst + 2u * plane_bytes) = w2;
             }
         }
     }
@@ -308,16 +291,16 @@ __global__ void __launch_bounds__(kAggmThreads, 4) gnm_aggm_kernel(const AggArgs
         f32x16 accA, accB;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { accA[r] = 0.f; accB[r] = 0.f; }
-        auto afrag = [&](unsigned pk, int m) -> bf16x8 {
+        auto afrag = [&](unsigned pk, int m) -> gnm_bf16x8 {
             const unsigned byte3 = m == 0 ? (pk << 3) : (pk >> (8 * m - 3));
             const unsigned lo = byte3 & 0x78u, hi = (byte3 >> 4) & 0x78u;
-            const u32x2 l2 = *reinterpret_cast<const u32x2*>(lut + lo);
-            const u32x2 h2 = *reinterpret_cast<const u32x2*>(lut + hi);
-            const u32x4 q = {l2.x, l2.y, h2.x, h2.y};
-            return __builtin_bit_cast(bf16x8, q);
+            const gnm_u32x2 l2 = *reinterpret_cast<const gnm_u32x2*>(lut + lo);
+            const gnm_u32x2 h2 = *reinterpret_cast<const gnm_u32x2*>(lut + hi);
+            const gnm_u32x4 q = {l2.x, l2.y, h2.x, h2.y};
+            return __builtin_bit_cast(gnm_bf16x8, q);
         };
-        auto bfrag = [&](const char* bp, int ks) -> bf16x8 {
-            return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(bp + ks * kAggmStepBytes));
+        auto bfrag = [&](const char* bp, int ks) -> gnm_bf16x8 {
+            return __builtin_bit_cast(gnm_bf16x8, *reinterpret_cast<const gnm_u32x4*>(bp + ks * kAggmStepBytes));
         };
         // The product, software-pipelined by hand: the operands of step ks + 1 are requested from LDS before the MFMAs
         // of step ks are issued (left to the compiler, every step was  ds_read x5 -> wait -> 3 MFMA -> ds_read x2 -> wait
@@ -326,17 +309,17 @@ __global__ void __launch_bounds__(kAggmThreads, 4) gnm_aggm_kernel(const AggArgs
         // branch; what was requested for them is read from inside the workgroup's own LDS and dropped.
         auto product = [&](auto two_tag) {
             constexpr bool TWO = decltype(two_tag)::value;
-            bf16x8 b0 = bfrag(bp0, 0), b1 = bfrag(bp1, 0), b2 = bfrag(bp2, 0);
-            bf16x8 aA = afrag(pkA[0], 0), aB = aA;
+            gnm_bf16x8 b0 = bfrag(bp0, 0), b1 = bfrag(bp1, 0), b2 = bfrag(bp2, 0);
+            gnm_bf16x8 aA = afrag(pkA[0], 0), aB = aA;
             if constexpr (TWO) aB = afrag(pkB[0], 0);
 #pragma unroll
             for (int ks = 0; ks < 26; ++ks) {
                 if (ks < ksteps) {                                // wave-uniform
                     constexpr int LASTK = 25;
                     const int kn = ks < LASTK ? ks + 1 : LASTK;
-                    const bf16x8 n0 = bfrag(bp0, kn), n1 = bfrag(bp1, kn), n2 = bfrag(bp2, kn);
-                    const bf16x8 nA = afrag(pkA[kn >> 2], kn & 3);
-                    bf16x8 nB = nA;
+                    const gnm_bf16x8 n0 = bfrag(bp0, kn), n1 = bfrag(bp1, kn), n2 = bfrag(bp2, kn);
+                    const gnm_bf16x8 nA = afrag(pkA[kn >> 2], kn & 3);
+                    gnm_bf16x8 nB = nA;
                     if constexpr (TWO) nB = afrag(pkB[kn >> 2], kn & 3);
                     __builtin_amdgcn_sched_barrier(0);            // the requests above stay above the MFMAs below
                     accA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aA, b0, accA, 0, 0, 0);
@@ -410,11 +393,11 @@ __global__ void __launch_bounds__(kAggmThreads, 4) gnm_aggm_kernel(const AggArgs
             if constexpr (STATS) dv4 = *reinterpret_cast<const f32x4*>(dvs + rb * 32 + 8 * k + 4 * h);   // (rows >= n: unused)
             const unsigned yq = lane_y + (unsigned)(rb * 32 + 8 * k) * row_y;
             float wq[4];
-            {
+            {   // (the inverse of gnm_split.h's split, not a copy of it: a stored element's planes add up to it exactly)
                 const char* e = smem + (unsigned)min(rb * 4 + k, (n16 >> 3) - 1) * kAggmK8Stride + i * 16 + h * 8;
-                const u32x2 p1 = *reinterpret_cast<const u32x2*>(e);
-                const u32x2 p2 = *reinterpret_cast<const u32x2*>(e + plane_bytes);
-                const u32x2 p3 = *reinterpret_cast<const u32x2*>(e + 2u * plane_bytes);
+                const gnm_u32x2 p1 = *reinterpret_cast<const gnm_u32x2*>(e);
+                const gnm_u32x2 p2 = *reinterpret_cast<const gnm_u32x2*>(e + plane_bytes);
+                const gnm_u32x2 p3 = *reinterpret_cast<const gnm_u32x2*>(e + 2u * plane_bytes);
                 wq[0] = (__uint_as_float(p1.x << 16) + __uint_as_float(p2.x << 16)) + __uint_as_float(p3.x << 16);
                 wq[1] = (__uint_as_float(p1.x & 0xFFFF0000u) + __uint_as_float(p2.x & 0xFFFF0000u)) + __uint_as_float(p3.x & 0xFFFF0000u);
                 wq[2] = (__uint_as_float(p1.y << 16) + __uint_as_float(p2.y << 16)) + __uint_as_float(p3.y << 16);

@@ -11,20 +11,14 @@
 // This kernel then forms, per workgroup of (graph, 32-row block), the [32, n] strip of
 //   E[u, v] = sum_l <S_l[u], h_{l-1}[v]>          (a GEMM with K = L H; h_{l-1} = relu(z * scale + shift) of layer
 //                                                  l-1's last Linear, re-formed as the forward does; Y for l = 0)
-// as split-bf16 MFMA products with fp32 accumulation (the six-term split of saliency.hip's sl_step), and writes
+// as split-bf16 MFMA products with fp32 accumulation (the six-term split of gnm_split.h), and writes
 //   sum:     out = E
 //   average: out[u, v] = E[u, v] - c[u],  c[u] = (1 / d_u) sum_w A[u, w] E[u, w]   (a masked row mean of the strip)
 // Every output element is written once, from LDS, with a fixed summation order: deterministic, no atomics.
-#include "gnm_common.h"
+#include "gnm_rowblock.h"
 
-typedef __bf16 es_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int es_u32x4 __attribute__((ext_vector_type(4)));
-
-static constexpr int kEsMaxN = 416;               // as saliency.hip: a bit row is at most 13 words
-static constexpr int kEsMaxH = 128;
-static constexpr int kEsTS = kEsMaxH + 4;         // row stride of the S tile in LDS (floats)
 static constexpr int kEsLinWords = 6;             // gnm_saliency's table: per (layer, Linear) W, ld W, z, ld z, scale, shift
-static constexpr int kEsMaxTiles = (kEsMaxN + 31) / 32 / 4 + 1;   // 32-column tiles per wave (13 tiles, 4 waves: 4)
+static constexpr int kEsMaxTiles = (kRbMaxN + 31) / 32 / 4 + 1;   // 32-column tiles per wave (13 tiles, 4 waves: 4)
 
 struct EsArgs {
     const uint32_t* adj_bits; const int64_t* b_bits_off;    // the FORWARD bit rows (row u: the v with A[u, v] = 1)
@@ -37,29 +31,10 @@ struct EsArgs {
     int lde;                                      // row stride of the E strip in LDS (floats)
 };
 
-__device__ __forceinline__ void es_split8(const float* f, es_bf16x8& p1, es_bf16x8& p2, es_bf16x8& p3) {
-    unsigned a1[8], a2[8], a3[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        a1[j] = __float_as_uint(f[j]) & 0xFFFF0000u;
-        const float r1 = f[j] - __uint_as_float(a1[j]);
-        a2[j] = __float_as_uint(r1) & 0xFFFF0000u;
-        a3[j] = __float_as_uint(r1 - __uint_as_float(a2[j]));
-    }
-    es_u32x4 q1, q2, q3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        q1[j] = __builtin_amdgcn_perm(a1[2 * j + 1], a1[2 * j], 0x07060302u);
-        q2[j] = __builtin_amdgcn_perm(a2[2 * j + 1], a2[2 * j], 0x07060302u);
-        q3[j] = __builtin_amdgcn_perm(a3[2 * j + 1], a3[2 * j], 0x07060302u);
-    }
-    p1 = __builtin_bit_cast(es_bf16x8, q1); p2 = __builtin_bit_cast(es_bf16x8, q2); p3 = __builtin_bit_cast(es_bf16x8, q3);
-}
-
 __global__ void __launch_bounds__(256) gnm_edge_saliency_kernel(const EsArgs p) {
     extern __shared__ __attribute__((aligned(16))) float es_smem[];
-    float* Ts = es_smem;                          // [32][kEsTS]: the block's rows of S_l
-    float* Es = es_smem + 32 * kEsTS;             // [32][lde]: the E strip
+    float* Ts = es_smem;                          // [32][kRbTS]: the block's rows of S_l
+    float* Es = es_smem + 32 * kRbTS;             // [32][lde]: the E strip
     float* cs = Es + 32 * p.lde;                  // [32]: the average pooling's row correction
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -90,7 +65,7 @@ __global__ void __launch_bounds__(256) gnm_edge_saliency_kernel(const EsArgs p) 
             for (int c = 4 * c8; c < H; c += 32) {
                 float4 v = *reinterpret_cast<const float4*>(srow + c);
                 if (!vrow) v = make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<float4*>(Ts + row * kEsTS + c) = v;
+                *reinterpret_cast<float4*>(Ts + row * kRbTS + c) = v;
             }
         }
         const float* src; int lds;
@@ -106,14 +81,8 @@ __global__ void __launch_bounds__(256) gnm_edge_saliency_kernel(const EsArgs p) 
 #pragma nounroll
         for (int s = 0; s < (H >> 4); ++s) {
             const int k0 = 16 * s + 8 * h;
-            float fa[8];
-            {
-                const float4 v0 = *reinterpret_cast<const float4*>(Ts + i * kEsTS + k0);
-                const float4 v1 = *reinterpret_cast<const float4*>(Ts + i * kEsTS + k0 + 4);
-                fa[0] = v0.x; fa[1] = v0.y; fa[2] = v0.z; fa[3] = v0.w; fa[4] = v1.x; fa[5] = v1.y; fa[6] = v1.z; fa[7] = v1.w;
-            }
-            es_bf16x8 a1, a2, a3;
-            es_split8(fa, a1, a2, a3);
+            gnm_bf16x8 a1, a2, a3;
+            gnm_tile_split(Ts, kRbTS, i, h, s, a1, a2, a3);
             float scv[8], shv[8];
             if (sc) {
                 const float4 s0 = *reinterpret_cast<const float4*>(sc + k0), s1 = *reinterpret_cast<const float4*>(sc + k0 + 4);
@@ -132,14 +101,9 @@ __global__ void __launch_bounds__(256) gnm_edge_saliency_kernel(const EsArgs p) 
 #pragma unroll
                     for (int j = 0; j < 8; ++j) fb[j] = gnm_relu(fb[j] * scv[j] + shv[j]);   // graphcnn.py:163-166
                 }
-                es_bf16x8 b1, b2, b3;
-                es_split8(fb, b1, b2, b3);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc[t], 0, 0, 0);   // small terms first
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[t], 0, 0, 0);
+                gnm_bf16x8 b1, b2, b3;
+                gnm_split8(fb, b1, b2, b3);
+                gnm_mma6(acc[t], a1, a2, a3, b1, b2, b3);
             }
         }
     }
@@ -152,7 +116,7 @@ __global__ void __launch_bounds__(256) gnm_edge_saliency_kernel(const EsArgs p) 
     }
     __syncthreads();
     if (p.average) {                              // c[u] = (1 / d_u) sum_w A[u, w] E[u, w], 8 lanes per row
-        const int HPW = (((W + 1) >> 1) + 3) & ~3;
+        const int HPW = rb_half_words(W);
         const uint32_t* brow = p.adj_bits + p.b_bits_off[b] + (size_t)(rb * 32 + row) * (2 * HPW);
         const float* er = Es + row * p.lde;
         float sum = 0.f;
@@ -185,7 +149,7 @@ __global__ void __launch_bounds__(256) gnm_edge_saliency_kernel(const EsArgs p) 
 // LDS bytes of gnm_edge_saliency_kernel for graphs of at most n_max nodes
 static size_t es_lds_bytes(int n_max, int* lde) {
     *lde = 32 * ((n_max + 31) / 32) + 4;
-    return (size_t)(32 * kEsTS + 32 * *lde + 32) * sizeof(float);
+    return (size_t)(32 * kRbTS + 32 * *lde + 32) * sizeof(float);
 }
 
 // The contraction of gnm_edge_saliency (saliency.hip), after its layer launches; arguments as there, checked there.
@@ -193,7 +157,7 @@ extern "C" __attribute__((visibility("hidden"))) int gnm_edge_saliency_contract(
     const uint32_t* adj_bits, const int64_t* b_bits_off, const int32_t* node_off, const int32_t* rowptr,
     const int64_t* b_rp_off, int B, int n_max, long long N, int H, int L, int m, int average, int self_loop,
     const long long* table, const float* S, const float* Y, int ldy, float* out, long long ldo, hipStream_t s) {
-    if (n_max < 1 || n_max > kEsMaxN || !(H == 32 || H == 64 || H == 128)) return GNM_ERR_UNSUPPORTED;
+    if (n_max < 1 || n_max > kRbMaxN || !(H == 32 || H == 64 || H == 128)) return GNM_ERR_UNSUPPORTED;
     EsArgs a;
     a.adj_bits = adj_bits; a.b_bits_off = b_bits_off; a.node_off = node_off; a.rowptr = rowptr; a.b_rp_off = b_rp_off;
     a.wmax = (n_max + 31) / 32; a.L = L; a.m = m; a.H = H; a.average = average; a.self_loop = self_loop;

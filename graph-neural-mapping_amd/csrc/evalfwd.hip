@@ -17,12 +17,8 @@
 // Arithmetic is the training kernels' (fp32-faithful three-plane splits, fp32 accumulation); results agree with them to
 // fp32 rounding, not bitwise.  The MFMA work of one graph on one CU bounds it at ~57 us (aggregation 33 + Linears 24);
 // B graphs run on B CUs in the same launch.
-#include "gnm_common.h"
+#include "gnm_rowblock.h"
 #include <string.h>
-
-typedef __bf16 ev_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int ev_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int ev_u32x2 __attribute__((ext_vector_type(2)));
 
 #define GNM_EVAL_MAX_LAYERS 16
 #define GNM_EVAL_MAX_MLP 3
@@ -54,26 +50,6 @@ struct EvalArgs {
     float* c_logit; int ldc;                             // [B, C]
 };
 
-__device__ __forceinline__ unsigned ev_pair_hi(unsigned lo_word, unsigned hi_word) {
-    return __builtin_amdgcn_perm(hi_word, lo_word, 0x07060302u);
-}
-__device__ __forceinline__ void ev_split3(const float f, unsigned& a1, unsigned& a2, unsigned& a3) {
-    a1 = __float_as_uint(f) & 0xFFFF0000u;
-    const float r1 = f - __uint_as_float(a1);
-    a2 = __float_as_uint(r1) & 0xFFFF0000u;
-    a3 = __float_as_uint(r1 - __uint_as_float(a2));
-}
-__device__ __forceinline__ void ev_split8(const float* f, ev_u32x4& p1, ev_u32x4& p2, ev_u32x4& p3) {
-    unsigned a1[8], a2[8], a3[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ev_split3(f[j], a1[j], a2[j], a3[j]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        p1[j] = ev_pair_hi(a1[2 * j], a1[2 * j + 1]);
-        p2[j] = ev_pair_hi(a2[2 * j], a2[2 * j + 1]);
-        p3[j] = ev_pair_hi(a3[2 * j], a3[2 * j + 1]);
-    }
-}
 __host__ __device__ static inline int ev_half_words(int W) { return (((W + 1) >> 1) + 3) & ~3; }
 
 __global__ void __launch_bounds__(kEvThreads) gnm_eval_encoder_kernel(const EvalArgs p) {
@@ -82,7 +58,7 @@ __global__ void __launch_bounds__(kEvThreads) gnm_eval_encoder_kernel(const Eval
     constexpr int E = 4 * HT * 64;                     // 16-byte operand entries per weight plane ([m][c][lane])
     const unsigned plane_bytes = (unsigned)(p.n16_max >> 3) * kEvK8;
     char* planes = smem;                                                   // [3][n16 / 8][512]
-    ev_u32x4* Wpl = reinterpret_cast<ev_u32x4*>(smem + 3u * plane_bytes);  // [3][E] weight planes of the current Linear
+    gnm_u32x4* Wpl = reinterpret_cast<gnm_u32x4*>(smem + 3u * plane_bytes);  // [3][E] weight planes of the current Linear
     char* lut = reinterpret_cast<char*>(Wpl + 3 * E);                      // 128 B nibble table
     float* bnv = reinterpret_cast<float*>(lut + 128);                      // [3][H]: bias, scale, shift of the current Linear
     float* rsum = bnv + 3 * H;                                             // [16 waves][H] readout partials
@@ -119,19 +95,13 @@ __global__ void __launch_bounds__(kEvThreads) gnm_eval_encoder_kernel(const Eval
     const uint32_t* gbits = p.adj_bits + p.b_bits_off[b];
     const int32_t* rp = p.rowptr + p.b_rp_off[b];
 
-    if (tid < 16) {            // nibble e -> bf16 (bit 0, bit 1, bit 2, bit 3) as two words
-        const unsigned one = 0x3F80u;
-        ev_u32x2 v;
-        v.x = ((tid & 1) ? one : 0u) | ((tid & 2) ? one << 16 : 0u);
-        v.y = ((tid & 4) ? one : 0u) | ((tid & 8) ? one << 16 : 0u);
-        *reinterpret_cast<ev_u32x2*>(lut + 8 * tid) = v;
-    }
+    rb_lut_init(lut, tid);
     // a wave's rows of the bit adjacency: row block `wave` is kept in registers for the whole kernel (the same for
     // every layer and column block); a wave that also owns block wave + 12 loads that one when it gets there
     auto load_pk = [&](int rb, unsigned (&pkv)[8]) {
-        const ev_u32x4* ra = reinterpret_cast<const ev_u32x4*>(gbits + (size_t)(min(rb, W - 1) * 32 + i) * (2 * HPW) + h * HPW);
-        const ev_u32x4 z4 = {0u, 0u, 0u, 0u};
-        const ev_u32x4 q0 = ra[0], q1 = HPW > 4 ? ra[1] : z4;
+        const gnm_u32x4* ra = reinterpret_cast<const gnm_u32x4*>(gbits + (size_t)(min(rb, W - 1) * 32 + i) * (2 * HPW) + h * HPW);
+        const gnm_u32x4 z4 = {0u, 0u, 0u, 0u};
+        const gnm_u32x4 q0 = ra[0], q1 = HPW > 4 ? ra[1] : z4;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { pkv[j] = q0[j]; pkv[4 + j] = q1[j]; }
     };
@@ -164,15 +134,15 @@ __global__ void __launch_bounds__(kEvThreads) gnm_eval_encoder_kernel(const Eval
                 for (int c = 0; c < 4; ++c) {
                     unsigned x0[4], x1[4], x2[4];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) ev_split3(v[k][c], x0[k], x1[k], x2[k]);
-                    ev_u32x2 w0, w1, w2;
-                    w0.x = ev_pair_hi(x0[0], x0[1]); w0.y = ev_pair_hi(x0[2], x0[3]);
-                    w1.x = ev_pair_hi(x1[0], x1[1]); w1.y = ev_pair_hi(x1[2], x1[3]);
-                    w2.x = ev_pair_hi(x2[0], x2[1]); w2.y = ev_pair_hi(x2[2], x2[3]);
+                    for (int k = 0; k < 4; ++k) gnm_split3(v[k][c], x0[k], x1[k], x2[k]);
+                    gnm_u32x2 w0, w1, w2;
+                    w0.x = gnm_bf16_pair(x0[0], x0[1]); w0.y = gnm_bf16_pair(x0[2], x0[3]);
+                    w1.x = gnm_bf16_pair(x1[0], x1[1]); w1.y = gnm_bf16_pair(x1[2], x1[3]);
+                    w2.x = gnm_bf16_pair(x2[0], x2[1]); w2.y = gnm_bf16_pair(x2[2], x2[3]);
                     char* dst = planes + off + c * 16;
-                    *reinterpret_cast<ev_u32x2*>(dst) = w0;
-                    *reinterpret_cast<ev_u32x2*>(dst + plane_bytes) = w1;
-                    *reinterpret_cast<ev_u32x2*>(dst + 2u * plane_bytes) = w2;
+                    *reinterpret_cast<gnm_u32x2*>(dst) = w0;
+                    *reinterpret_cast<gnm_u32x2*>(dst + plane_bytes) = w1;
+                    *reinterpret_cast<gnm_u32x2*>(dst + 2u * plane_bytes) = w2;
                 }
             }
             __syncthreads();
@@ -190,25 +160,25 @@ __global__ void __launch_bounds__(kEvThreads) gnm_eval_encoder_kernel(const Eval
                 f32x16 acc;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-                auto afrag = [&](unsigned pkw, int mm) -> ev_bf16x8 {
+                auto afrag = [&](unsigned pkw, int mm) -> gnm_bf16x8 {
                     const unsigned byte3 = mm == 0 ? (pkw << 3) : (pkw >> (8 * mm - 3));
                     const unsigned lo = byte3 & 0x78u, hi = (byte3 >> 4) & 0x78u;
-                    const ev_u32x2 l2 = *reinterpret_cast<const ev_u32x2*>(lut + lo);
-                    const ev_u32x2 h2 = *reinterpret_cast<const ev_u32x2*>(lut + hi);
-                    const ev_u32x4 q = {l2.x, l2.y, h2.x, h2.y};
-                    return __builtin_bit_cast(ev_bf16x8, q);
+                    const gnm_u32x2 l2 = *reinterpret_cast<const gnm_u32x2*>(lut + lo);
+                    const gnm_u32x2 h2 = *reinterpret_cast<const gnm_u32x2*>(lut + hi);
+                    const gnm_u32x4 q = {l2.x, l2.y, h2.x, h2.y};
+                    return __builtin_bit_cast(gnm_bf16x8, q);
                 };
-                auto bfrag = [&](const char* bp, int ks) -> ev_bf16x8 {
-                    return __builtin_bit_cast(ev_bf16x8, *reinterpret_cast<const ev_u32x4*>(bp + ks * kEvStep));
+                auto bfrag = [&](const char* bp, int ks) -> gnm_bf16x8 {
+                    return __builtin_bit_cast(gnm_bf16x8, *reinterpret_cast<const gnm_u32x4*>(bp + ks * kEvStep));
                 };
-                ev_bf16x8 b0 = bfrag(bp0, 0), b1 = bfrag(bp1, 0), b2 = bfrag(bp2, 0);
-                ev_bf16x8 aA = afrag(pk[0], 0);
+                gnm_bf16x8 b0 = bfrag(bp0, 0), b1 = bfrag(bp1, 0), b2 = bfrag(bp2, 0);
+                gnm_bf16x8 aA = afrag(pk[0], 0);
 #pragma unroll
                 for (int ks = 0; ks < 25; ++ks) {
                     if (ks < ksteps) {                                // wave-uniform
                         constexpr int LASTK = 24;
                         const int kn = ks < LASTK ? ks + 1 : LASTK;
-                        const ev_bf16x8 nA = afrag(pk[kn >> 2], kn & 3);
+                        const gnm_bf16x8 nA = afrag(pk[kn >> 2], kn & 3);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aA, b0, acc, 0, 0, 0);
                         b0 = bfrag(bp0, kn);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aA, b1, acc, 0, 0, 0);
@@ -266,8 +236,8 @@ __global__ void __launch_bounds__(kEvThreads) gnm_eval_encoder_kernel(const Eval
                         const int kk = 8 * mm + 32 * kg + j;
                         f[j] = kk < K ? Wg[(size_t)(32 * c + nn) * ldw + kk] : 0.f;
                     }
-                    ev_u32x4 p1, p2, p3;
-                    ev_split8(f, p1, p2, p3);
+                    gnm_u32x4 p1, p2, p3;
+                    gnm_split8(f, p1, p2, p3);
                     Wpl[e] = p1; Wpl[E + e] = p2; Wpl[2 * E + e] = p3;
                 }
                 if (tid < H) {         // bias and the folded eval-mode BatchNorm behind this Linear (running statistics)
@@ -283,7 +253,7 @@ __global__ void __launch_bounds__(kEvThreads) gnm_eval_encoder_kernel(const Eval
                 const int r0 = t * 32;
                 const int arow = min(r0 + i, n - 1);
                 // A fragments straight from the (L2-resident) input: row i, k = 8 mm + 32 h + 0..7
-                ev_u32x4 A1[4], A2[4], A3[4];
+                gnm_u32x4 A1[4], A2[4], A3[4];
 #pragma unroll
                 for (int mm = 0; mm < 4; ++mm) {
                     float f[8];
@@ -297,7 +267,7 @@ __global__ void __launch_bounds__(kEvThreads) gnm_eval_encoder_kernel(const Eval
 #pragma unroll
                         for (int j = 0; j < 8; ++j) f[j] = k0 + j < K ? src[j] : 0.f;
                     }
-                    ev_split8(f, A1[mm], A2[mm], A3[mm]);
+                    gnm_split8(f, A1[mm], A2[mm], A3[mm]);
                 }
                 f32x16 acc[HT];
 #pragma unroll
@@ -307,19 +277,14 @@ __global__ void __launch_bounds__(kEvThreads) gnm_eval_encoder_kernel(const Eval
 #pragma unroll
                 for (int mm = 0; mm < 4; ++mm) {
                     if (8 * mm < K || 32 + 8 * mm < K) {       // wave-uniform: k groups past K are all zero
-                        const ev_bf16x8 a1 = __builtin_bit_cast(ev_bf16x8, A1[mm]), a2 = __builtin_bit_cast(ev_bf16x8, A2[mm]),
-                                        a3 = __builtin_bit_cast(ev_bf16x8, A3[mm]);
+                        const gnm_bf16x8 a1 = __builtin_bit_cast(gnm_bf16x8, A1[mm]), a2 = __builtin_bit_cast(gnm_bf16x8, A2[mm]),
+                                        a3 = __builtin_bit_cast(gnm_bf16x8, A3[mm]);
 #pragma unroll
                         for (int c = 0; c < HT; ++c) {
                             const int e = (mm * HT + c) * 64 + lane;
-                            const ev_bf16x8 w1 = __builtin_bit_cast(ev_bf16x8, Wpl[e]), w2 = __builtin_bit_cast(ev_bf16x8, Wpl[E + e]),
-                                            w3 = __builtin_bit_cast(ev_bf16x8, Wpl[2 * E + e]);
-                            acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, w3, acc[c], 0, 0, 0);      // small terms first
-                            acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, w1, acc[c], 0, 0, 0);
-                            acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, w2, acc[c], 0, 0, 0);
-                            acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, w2, acc[c], 0, 0, 0);
-                            acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, w1, acc[c], 0, 0, 0);
-                            acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, w1, acc[c], 0, 0, 0);
+                            const gnm_bf16x8 w1 = __builtin_bit_cast(gnm_bf16x8, Wpl[e]), w2 = __builtin_bit_cast(gnm_bf16x8, Wpl[E + e]),
+                                            w3 = __builtin_bit_cast(gnm_bf16x8, Wpl[2 * E + e]);
+                            gnm_mma6(acc[c], a1, a2, a3, w1, w2, w3);
                         }
                     }
                 }

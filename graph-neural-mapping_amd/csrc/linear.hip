@@ -17,7 +17,7 @@
 //     of squares (fp64) for the BatchNorm that follows (mlp.py:48, graphcnn.py:163):
 //     in the 32x32 C/D layout a lane owns one output COLUMN, so the statistics are
 //     register adds.
-#include "gnm_common.h"
+#include "gnm_split.h"
 
 // tuning knobs, read once per process
 static bool lin_force_generic() { static const bool v = getenv("GNM_LIN_GENERIC") != nullptr; return v; }
@@ -496,8 +496,6 @@ static int launch_lin_fast(const LinArgs& a, int grid, hipStream_t s) {
 // The wait in front of the staging writes becomes vmcnt(15..8): the previous tile's stores drain under this tile's
 // MFMAs instead of in front of them.
 // ---------------------------------------------------------------------------------
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t gnm_tile_rsrc(const float* base, long long rows, int ld, int width) {
     // raw buffer (stride 0): byte offsets >= num_records read 0 / are not written.  On gfx950 the check covers the
     // scalar offset too (tools/ubench/soffset_check.hip: a load that leaves the range only through soffset returns 0),
@@ -552,7 +550,7 @@ __global__ void __launch_bounds__(256) gnm_lin_stream_kernel(const LinArgs p) {
     const int out_voff = ((lane / O4) * p.ldz + 4 * (lane % O4)) * 4;
     const int out_step = WSTEP * p.ldz * 4;
 
-    u32x4 raw[NLD];
+    gnm_u32x4 raw[NLD];
     auto load_tile = [&](int tile) {
         const long long row0 = (long long)tile * 32;
         const __amdgpu_buffer_rsrc_t rs = gnm_tile_rsrc(p.X + row0 * p.ldx, min((long long)p.N - row0, 32LL), p.ldx, KC);
@@ -669,7 +667,7 @@ __global__ void __launch_bounds__(256) gnm_lin_stream_kernel(const LinArgs p) {
         for (int st = 0; st < NST; ++st) {
             const int idx = lane + 64 * st;
             const int row = idx / O4, oc = idx - row * O4;
-            const u32x4 v = *reinterpret_cast<const u32x4*>(Xs + row * XS + 4 * oc);
+            const gnm_u32x4 v = *reinterpret_cast<const gnm_u32x4*>(Xs + row * XS + 4 * oc);
             // row step in the VECTOR offset, scalar offset 0: with an SGPR soffset hipcc (ROCm 7.2) schedules a VALU
             // write of the data registers straight behind a 16-byte buffer store (its hazard table exempts that form)
             // and on gfx950 the store then picks up the new value in some lanes -- seen as address integers in Z.
@@ -735,31 +733,6 @@ static int launch_lin_stream(const LinArgs& a, int grid, hipStream_t s) {
 // with a copy each do not fit the LDS); its waves form three groups of four that write three rows of statistics
 // partials, so the launch produces exactly the gnm_linear_grid(N) rows the BatchNorm finalize expects.
 // ---------------------------------------------------------------------------------
-typedef __bf16 lin_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void lin_split3(const float f, unsigned& a1, unsigned& a2, unsigned& a3) {
-    a1 = __float_as_uint(f) & 0xFFFF0000u;
-    const float r1 = f - __uint_as_float(a1);
-    a2 = __float_as_uint(r1) & 0xFFFF0000u;
-    a3 = __float_as_uint(r1 - __uint_as_float(a2));        // <= 8 significant bits left: its top half is all of it
-}
-// (top 16 bits of hi_word) : (top 16 bits of lo_word)
-__device__ __forceinline__ unsigned lin_bf16_pair(unsigned lo_word, unsigned hi_word) {
-    return __builtin_amdgcn_perm(hi_word, lo_word, 0x07060302u);
-}
-// eight consecutive-k floats -> the three bf16x8 operands
-__device__ __forceinline__ void lin_split8(const float* f, u32x4& p1, u32x4& p2, u32x4& p3) {
-    unsigned a1[8], a2[8], a3[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) lin_split3(f[j], a1[j], a2[j], a3[j]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        p1[j] = lin_bf16_pair(a1[2 * j], a1[2 * j + 1]);
-        p2[j] = lin_bf16_pair(a2[2 * j], a2[2 * j + 1]);
-        p3[j] = lin_bf16_pair(a3[2 * j], a3[2 * j + 1]);
-    }
-}
-
 #ifndef GNM_SPLIT_WAVES           // tuning builds: 16 = four waves per SIMD (needs GNM_LIN_GRID=1024 to fill 256 CUs)
 #define GNM_SPLIT_WAVES 12
 #endif
@@ -783,7 +756,7 @@ __global__ void __launch_bounds__(kSplitWaves * 64) gnm_lin_split_kernel(const L
     constexpr int E = 4 * HT * 64;                // operand entries (16 B) per weight plane: [m][c][lane]
     GNM_SSTAMP(0)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    u32x4* Wp = reinterpret_cast<u32x4*>(smem);                               // [3][E]
+    gnm_u32x4* Wp = reinterpret_cast<gnm_u32x4*>(smem);                               // [3][E]
     float* Xs_all = reinterpret_cast<float*>(smem + (size_t)3 * E * 16);      // [NW][32][XS]; first the fp32 weight image
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -813,7 +786,7 @@ __global__ void __launch_bounds__(kSplitWaves * 64) gnm_lin_split_kernel(const L
     const int out_voff = ((lane / O4) * p.ldz + 4 * (lane % O4)) * 4;
     const int out_step = WSTEP * p.ldz * 4;
 
-    u32x4 raw[NLD];
+    gnm_u32x4 raw[NLD];
     auto load_tile = [&](int tile) {
         const long long row0 = (long long)tile * 32;
         const __amdgpu_buffer_rsrc_t rs = gnm_tile_rsrc(p.X + row0 * p.ldx, (GNM_L64_ABLATE & 2) ? 0LL : min((long long)p.N - row0, 32LL), p.ldx, KC);
@@ -840,8 +813,8 @@ __global__ void __launch_bounds__(kSplitWaves * 64) gnm_lin_split_kernel(const L
             const float* src = p.W + (size_t)(32 * c + n) * p.ldw + 8 * m + 32 * kg;
             const float4 w0 = load_w4(src), w1 = load_w4(src + 4);
             const float f[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-            u32x4 p1, p2, p3;
-            lin_split8(f, p1, p2, p3);
+            gnm_u32x4 p1, p2, p3;
+            gnm_split8(f, p1, p2, p3);
             Wp[e] = p1; Wp[E + e] = p2; Wp[2 * E + e] = p3;
         }
     } else {
@@ -855,8 +828,8 @@ __global__ void __launch_bounds__(kSplitWaves * 64) gnm_lin_split_kernel(const L
             float f[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = Wt[(8 * m + 32 * kg + j) * HP + 32 * c + n];
-            u32x4 p1, p2, p3;
-            lin_split8(f, p1, p2, p3);
+            gnm_u32x4 p1, p2, p3;
+            gnm_split8(f, p1, p2, p3);
             Wp[e] = p1; Wp[E + e] = p2; Wp[2 * E + e] = p3;
         }
     }
@@ -896,37 +869,37 @@ __global__ void __launch_bounds__(kSplitWaves * 64) gnm_lin_split_kernel(const L
         // front of its MFMAs (GNM_L64_SPLIT_AHEAD: all four first, as until round 4 -- 36 more registers, and the
         // splits cannot run in the MFMAs' shadow)
 #ifdef GNM_L64_SPLIT_AHEAD
-        u32x4 A1[4], A2[4], A3[4];
+        gnm_u32x4 A1[4], A2[4], A3[4];
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const float4 v0 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m);
             const float4 v1 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m + 4);
             const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-            lin_split8(f, A1[m], A2[m], A3[m]);
+            gnm_split8(f, A1[m], A2[m], A3[m]);
         }
         GNM_SSTAMP(4 + 6 * min(tk, 9))
 #endif
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
 #ifdef GNM_L64_SPLIT_AHEAD
-            const lin_bf16x8 a1 = __builtin_bit_cast(lin_bf16x8, A1[m]), a2 = __builtin_bit_cast(lin_bf16x8, A2[m]),
-                             a3 = __builtin_bit_cast(lin_bf16x8, A3[m]);
+            const gnm_bf16x8 a1 = __builtin_bit_cast(gnm_bf16x8, A1[m]), a2 = __builtin_bit_cast(gnm_bf16x8, A2[m]),
+                             a3 = __builtin_bit_cast(gnm_bf16x8, A3[m]);
 #else
-            u32x4 A1m, A2m, A3m;
+            gnm_u32x4 A1m, A2m, A3m;
             {
                 const float4 v0 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m);
                 const float4 v1 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m + 4);
                 const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                lin_split8(f, A1m, A2m, A3m);
+                gnm_split8(f, A1m, A2m, A3m);
             }
-            const lin_bf16x8 a1 = __builtin_bit_cast(lin_bf16x8, A1m), a2 = __builtin_bit_cast(lin_bf16x8, A2m),
-                             a3 = __builtin_bit_cast(lin_bf16x8, A3m);
+            const gnm_bf16x8 a1 = __builtin_bit_cast(gnm_bf16x8, A1m), a2 = __builtin_bit_cast(gnm_bf16x8, A2m),
+                             a3 = __builtin_bit_cast(gnm_bf16x8, A3m);
 #endif
 #pragma unroll
             for (int c = 0; c < HT; ++c) {
                 const int e = (m * HT + c) * 64 + lane;
-                const lin_bf16x8 b1 = __builtin_bit_cast(lin_bf16x8, Wp[e]), b2 = __builtin_bit_cast(lin_bf16x8, Wp[E + e]),
-                                 b3 = __builtin_bit_cast(lin_bf16x8, Wp[2 * E + e]);
+                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wp[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wp[E + e]),
+                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wp[2 * E + e]);
                 acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc[c], 0, 0, 0);      // small terms first
                 acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc[c], 0, 0, 0);
                 acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc[c], 0, 0, 0);
@@ -977,7 +950,7 @@ __global__ void __launch_bounds__(kSplitWaves * 64) gnm_lin_split_kernel(const L
         const float* const xi = Xs + (lane / O4) * XS + 4 * (lane % O4);
 #pragma unroll
         for (int st = 0; st < NST; ++st) {
-            const u32x4 v = *reinterpret_cast<const u32x4*>(xi + st * WSTEP * XS);
+            const gnm_u32x4 v = *reinterpret_cast<const gnm_u32x4*>(xi + st * WSTEP * XS);
             __builtin_amdgcn_raw_buffer_store_b128(v, rz, out_voff + st * out_step, 0, 0);     // (row step in the vector offset: see above)
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1060,7 +1033,7 @@ __global__ void __launch_bounds__(kSplit128Waves * 64) gnm_lin_split128_kernel(c
     constexpr int K = 128, HT = 4, HP = 128, NW = kSplit128Waves, NT = NW * 64;
     constexpr int E = 2 * 4 * HT * 64;              // 16-byte operand entries per weight plane: [kk][m][c][lane]
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    u32x4* Wp = reinterpret_cast<u32x4*>(smem);                              // [3][E]
+    gnm_u32x4* Wp = reinterpret_cast<gnm_u32x4*>(smem);                              // [3][E]
     float* psv = reinterpret_cast<float*>(smem + (size_t)3 * E * 16);        // [3][K]: prologue scale / shift, bias
     // column statistics of this wave, fp64, in LDS ([2][HP] per wave: 16 registers a lane could not spare -- with them
     // in registers the tile loop spilled 21)
@@ -1091,8 +1064,8 @@ __global__ void __launch_bounds__(kSplit128Waves * 64) gnm_lin_split128_kernel(c
             for (int j = 0; j < 8; ++j)
                 f[j] = p.w_kmajor ? p.W[(size_t)(k0 + j) * p.ldw + hh] : p.W[(size_t)hh * p.ldw + k0 + j];
         }
-        u32x4 p1, p2, p3;
-        lin_split8(f, p1, p2, p3);
+        gnm_u32x4 p1, p2, p3;
+        gnm_split8(f, p1, p2, p3);
         Wp[e] = p1; Wp[E + e] = p2; Wp[2 * E + e] = p3;
     }
     for (int e = tid; e < K; e += NT) {
@@ -1121,9 +1094,9 @@ __global__ void __launch_bounds__(kSplit128Waves * 64) gnm_lin_split128_kernel(c
     // this kernel ran at; D = 4 (the plain form; the masked form has registers for 2) keeps up to 96 KB in flight.
     constexpr int D = MASKED ? 2 : 4;
     int t = gw;
-    u32x4 ring0[D], ring1[D];
+    gnm_u32x4 ring0[D], ring1[D];
 #pragma unroll
-    for (int q = 0; q < D; ++q) { ring0[q] = u32x4{0u, 0u, 0u, 0u}; ring1[q] = ring0[q]; }
+    for (int q = 0; q < D; ++q) { ring0[q] = gnm_u32x4{0u, 0u, 0u, 0u}; ring1[q] = ring0[q]; }
     if (t < ntiles) {
         const __amdgpu_buffer_rsrc_t rs0 = tile_rsrc_of(t);
 #pragma unroll
@@ -1146,8 +1119,8 @@ __global__ void __launch_bounds__(kSplit128Waves * 64) gnm_lin_split128_kernel(c
             for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
         // slice 0 (requested under the previous tile's epilogue) into the image; LDS operations of one wave execute in
         // order, so the image needs no second buffer and no barrier
-        *reinterpret_cast<u32x4*>(xs_w) = ring0[0];
-        *reinterpret_cast<u32x4*>(xs_w + 16 * XS) = ring1[0];
+        *reinterpret_cast<gnm_u32x4*>(xs_w) = ring0[0];
+        *reinterpret_cast<gnm_u32x4*>(xs_w + 16 * XS) = ring1[0];
         // eight k steps of 16, unrolled (the ring slots are compile-time) with a scheduling fence per step: left alone,
         // the scheduler hoists every load and split of the 192-MFMA body (295 spilled registers in round 3)
 #pragma unroll
@@ -1177,15 +1150,15 @@ __global__ void __launch_bounds__(kSplit128Waves * 64) gnm_lin_split128_kernel(c
                     for (int j = 0; j < 8; ++j) f[j] = gnm_relu(f[j]);
                 }
             }
-            u32x4 A1, A2, A3;
-            lin_split8(f, A1, A2, A3);
-            const lin_bf16x8 a1 = __builtin_bit_cast(lin_bf16x8, A1), a2 = __builtin_bit_cast(lin_bf16x8, A2),
-                             a3 = __builtin_bit_cast(lin_bf16x8, A3);
+            gnm_u32x4 A1, A2, A3;
+            gnm_split8(f, A1, A2, A3);
+            const gnm_bf16x8 a1 = __builtin_bit_cast(gnm_bf16x8, A1), a2 = __builtin_bit_cast(gnm_bf16x8, A2),
+                             a3 = __builtin_bit_cast(gnm_bf16x8, A3);
 #pragma unroll
             for (int c = 0; c < HT; ++c) {
                 const int e = ((step * HT + c) << 6) + lane;
-                const lin_bf16x8 b1 = __builtin_bit_cast(lin_bf16x8, Wp[e]), b2 = __builtin_bit_cast(lin_bf16x8, Wp[E + e]),
-                                 b3 = __builtin_bit_cast(lin_bf16x8, Wp[2 * E + e]);
+                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wp[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wp[E + e]),
+                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wp[2 * E + e]);
                 acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc[c], 0, 0, 0);      // small terms first
                 acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc[c], 0, 0, 0);
                 acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc[c], 0, 0, 0);
@@ -1194,8 +1167,8 @@ __global__ void __launch_bounds__(kSplit128Waves * 64) gnm_lin_split128_kernel(c
                 acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[c], 0, 0, 0);
             }
             if (step < 7) {       // the next slice into the image (behind this step's reads, in order)
-                *reinterpret_cast<u32x4*>(xs_w) = ring0[(step + 1) % D];
-                *reinterpret_cast<u32x4*>(xs_w + 16 * XS) = ring1[(step + 1) % D];
+                *reinterpret_cast<gnm_u32x4*>(xs_w) = ring0[(step + 1) % D];
+                *reinterpret_cast<gnm_u32x4*>(xs_w + 16 * XS) = ring1[(step + 1) % D];
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1771,17 +1744,17 @@ __global__ void __launch_bounds__(512) gnm_wgrad_split128_kernel(const WgArgs p)
                     x[b][j] = p.pro_relu ? gnm_relu(v) : v;
                 }
         }
-        lin_bf16x8 dp[2][3], xp[2][3];
+        gnm_bf16x8 dp[2][3], xp[2][3];
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             dbs[a] += ((d[a][0] + d[a][1]) + (d[a][2] + d[a][3])) + ((d[a][4] + d[a][5]) + (d[a][6] + d[a][7]));
-            u32x4 p1, p2, p3;
-            lin_split8(d[a], p1, p2, p3);
-            dp[a][0] = __builtin_bit_cast(lin_bf16x8, p1); dp[a][1] = __builtin_bit_cast(lin_bf16x8, p2);
-            dp[a][2] = __builtin_bit_cast(lin_bf16x8, p3);
-            lin_split8(x[a], p1, p2, p3);
-            xp[a][0] = __builtin_bit_cast(lin_bf16x8, p1); xp[a][1] = __builtin_bit_cast(lin_bf16x8, p2);
-            xp[a][2] = __builtin_bit_cast(lin_bf16x8, p3);
+            gnm_u32x4 p1, p2, p3;
+            gnm_split8(d[a], p1, p2, p3);
+            dp[a][0] = __builtin_bit_cast(gnm_bf16x8, p1); dp[a][1] = __builtin_bit_cast(gnm_bf16x8, p2);
+            dp[a][2] = __builtin_bit_cast(gnm_bf16x8, p3);
+            gnm_split8(x[a], p1, p2, p3);
+            xp[a][0] = __builtin_bit_cast(gnm_bf16x8, p1); xp[a][1] = __builtin_bit_cast(gnm_bf16x8, p2);
+            xp[a][2] = __builtin_bit_cast(gnm_bf16x8, p3);
         }
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -1979,7 +1952,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
     // exact bf16 planes each (see gnm_lin_split_kernel); the weight image is then the three operand planes (24 KB)
     constexpr int EW = 4 * KT * 64;
     float* Wt = reinterpret_cast<float*>(smem);                   // [HP][KP]: W itself (contraction index first)
-    u32x4* Wp = reinterpret_cast<u32x4*>(smem);                   // SPLITD: [3][EW] operand entries instead
+    gnm_u32x4* Wp = reinterpret_cast<gnm_u32x4*>(smem);                   // SPLITD: [3][EW] operand entries instead
     float* Xs_all = SPLITD ? reinterpret_cast<float*>(smem + (size_t)3 * EW * 16) : Wt + (size_t)HP * KP;   // [4][32][XS]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1994,8 +1967,8 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 f[j] = (!NARROW || 32 * c + n < p.K) ? p.W[(size_t)(8 * m + 32 * kg + j) * p.ldw + 32 * c + n] : 0.f;
-            u32x4 p1, p2, p3;
-            lin_split8(f, p1, p2, p3);
+            gnm_u32x4 p1, p2, p3;
+            gnm_split8(f, p1, p2, p3);
             Wp[e] = p1; Wp[EW + e] = p2; Wp[2 * EW + e] = p3;
         }
     } else {
@@ -2112,16 +2085,16 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
                     const float4 v0 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m);
                     const float4 v1 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m + 4);
                     const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                    u32x4 A1, A2, A3;
-                    lin_split8(f, A1, A2, A3);
-                    const lin_bf16x8 x1 = __builtin_bit_cast(lin_bf16x8, A1), x2 = __builtin_bit_cast(lin_bf16x8, A2),
-                                     x3 = __builtin_bit_cast(lin_bf16x8, A3);
+                    gnm_u32x4 A1, A2, A3;
+                    gnm_split8(f, A1, A2, A3);
+                    const gnm_bf16x8 x1 = __builtin_bit_cast(gnm_bf16x8, A1), x2 = __builtin_bit_cast(gnm_bf16x8, A2),
+                                     x3 = __builtin_bit_cast(gnm_bf16x8, A3);
 #pragma unroll
                     for (int c = 0; c < KT; ++c) {
                         const int e = (m * KT + c) * 64 + lane;
-                        const lin_bf16x8 b1 = __builtin_bit_cast(lin_bf16x8, Wp[e]),
-                                         b2 = __builtin_bit_cast(lin_bf16x8, Wp[EW + e]),
-                                         b3 = __builtin_bit_cast(lin_bf16x8, Wp[2 * EW + e]);
+                        const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wp[e]),
+                                         b2 = __builtin_bit_cast(gnm_bf16x8, Wp[EW + e]),
+                                         b3 = __builtin_bit_cast(gnm_bf16x8, Wp[2 * EW + e]);
                         dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b3, dacc[c], 0, 0, 0);
                         dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, b1, dacc[c], 0, 0, 0);
                         dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b2, dacc[c], 0, 0, 0);
@@ -2369,7 +2342,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArg
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int EW = 4 * KT * 64;
     float* Wt = reinterpret_cast<float*>(smem);                   // [HP][KP]
-    u32x4* Wp = reinterpret_cast<u32x4*>(smem);                   // SPLITD: [3][EW] bf16 operand entries of W instead
+    gnm_u32x4* Wp = reinterpret_cast<gnm_u32x4*>(smem);                   // SPLITD: [3][EW] bf16 operand entries of W instead
     float* Xs_all = SPLITD ? reinterpret_cast<float*>(smem + (size_t)3 * EW * 16) : Wt + (size_t)HP * KP;   // [4][32][XS]
     float* coef = Xs_all + 4 * 32 * XS;                           // [5][HP]: mean, rstd, cA, m1, m2 of the BatchNorm
     const int tid = threadIdx.x;
@@ -2383,8 +2356,8 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArg
             float f[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = p.W[(size_t)(8 * m + 32 * kg + j) * p.ldw + 32 * c + n];
-            u32x4 p1, p2, p3;
-            lin_split8(f, p1, p2, p3);
+            gnm_u32x4 p1, p2, p3;
+            gnm_split8(f, p1, p2, p3);
             Wp[e] = p1; Wp[EW + e] = p2; Wp[2 * EW + e] = p3;
         }
     } else {
@@ -2428,7 +2401,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArg
     // (no dX wanted: an empty descriptor over any readable address -- the stores stay unconditional)
     const float* dxbase = p.dA ? p.dA : p.G;
 
-    u32x4 g4[NLD], z4[NLD];
+    gnm_u32x4 g4[NLD], z4[NLD];
     auto load_gz = [&](int tile) {
         const long long row0 = (long long)tile * 32;
         const long long rows = min((long long)p.N - row0, 32LL);
@@ -2487,15 +2460,15 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArg
                 const float4 v0 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m);
                 const float4 v1 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m + 4);
                 const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                u32x4 A1, A2, A3;
-                lin_split8(f, A1, A2, A3);
-                const lin_bf16x8 x1 = __builtin_bit_cast(lin_bf16x8, A1), x2 = __builtin_bit_cast(lin_bf16x8, A2),
-                                 x3 = __builtin_bit_cast(lin_bf16x8, A3);
+                gnm_u32x4 A1, A2, A3;
+                gnm_split8(f, A1, A2, A3);
+                const gnm_bf16x8 x1 = __builtin_bit_cast(gnm_bf16x8, A1), x2 = __builtin_bit_cast(gnm_bf16x8, A2),
+                                 x3 = __builtin_bit_cast(gnm_bf16x8, A3);
 #pragma unroll
                 for (int c = 0; c < KT; ++c) {
                     const int e = (m * KT + c) * 64 + lane;
-                    const lin_bf16x8 b1 = __builtin_bit_cast(lin_bf16x8, Wp[e]), b2 = __builtin_bit_cast(lin_bf16x8, Wp[EW + e]),
-                                     b3 = __builtin_bit_cast(lin_bf16x8, Wp[2 * EW + e]);
+                    const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wp[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wp[EW + e]),
+                                     b3 = __builtin_bit_cast(gnm_bf16x8, Wp[2 * EW + e]);
                     dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b3, dacc[c], 0, 0, 0);
                     dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, b1, dacc[c], 0, 0, 0);
                     dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b2, dacc[c], 0, 0, 0);
@@ -2565,7 +2538,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArg
             for (int st = 0; st < (32 * O4) / 64; ++st) {
                 const int idx = lane + 64 * st;
                 const int row = idx / O4, oc = idx - row * O4;
-                const u32x4 v = *reinterpret_cast<const u32x4*>(Xs + row * XS + 4 * oc);
+                const gnm_u32x4 v = *reinterpret_cast<const gnm_u32x4*>(Xs + row * XS + 4 * oc);
                 __builtin_amdgcn_raw_buffer_store_b128(v, rd, out_voff + st * out_step, 0, 0);
             }
         }
@@ -2671,8 +2644,8 @@ static constexpr int kRzWaves = 8;
 __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const LbArgs p) {
     constexpr int KP = 64, HP = 64, XS = 68, EW = 512, NW = kRzWaves, NT = NW * 64, TILE = 16 * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    u32x4* Wf = reinterpret_cast<u32x4*>(smem);                   // [3][EW]: (m, c, lane = 32 kg + n) = W[32c+n][8m+32kg+j]
-    u32x4* Wb = Wf + 3 * EW;                                      // [3][EW]: (m, c, lane = 32 kg + n) = W[8m+32kg+j][32c+n]
+    gnm_u32x4* Wf = reinterpret_cast<gnm_u32x4*>(smem);                   // [3][EW]: (m, c, lane = 32 kg + n) = W[32c+n][8m+32kg+j]
+    gnm_u32x4* Wb = Wf + 3 * EW;                                      // [3][EW]: (m, c, lane = 32 kg + n) = W[8m+32kg+j][32c+n]
     float* Xs_all = reinterpret_cast<float*>(smem + (size_t)6 * EW * 16);     // [NW][32][XS]
     float* coef = Xs_all + NW * 32 * XS;                          // [6][64]: mean, rstd, cA, m1, m2, bias
     float* psv = coef + 6 * 64;                                   // [2][64]: prologue scale, shift
@@ -2686,14 +2659,14 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
     for (int e = tid; e < EW; e += NT) {
         const int n = e & 31, kg = (e >> 5) & 1, c = (e >> 6) & 1, m = e >> 7;
         float f[8];
-        u32x4 p1, p2, p3;
+        gnm_u32x4 p1, p2, p3;
 #pragma unroll
         for (int j = 0; j < 8; ++j) f[j] = p.W[(size_t)(32 * c + n) * p.ldw + 8 * m + 32 * kg + j];
-        lin_split8(f, p1, p2, p3);
+        gnm_split8(f, p1, p2, p3);
         Wf[e] = p1; Wf[EW + e] = p2; Wf[2 * EW + e] = p3;
 #pragma unroll
         for (int j = 0; j < 8; ++j) f[j] = p.W[(size_t)(8 * m + 32 * kg + j) * p.ldw + 32 * c + n];
-        lin_split8(f, p1, p2, p3);
+        gnm_split8(f, p1, p2, p3);
         Wb[e] = p1; Wb[EW + e] = p2; Wb[2 * EW + e] = p3;
     }
     for (int idx = tid; idx < 64; idx += NT) {
@@ -2732,7 +2705,7 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
     const int out_voff = ((lane >> 4) * p.lda + 4 * (lane & 15)) * 4, out_step = 4 * p.lda * 4;
 
     float g[2][16];
-    u32x4 xa[4][2];
+    gnm_u32x4 xa[4][2];
     auto load_next_x = [&](int tile) {
         const long long row0 = (long long)tile * 32;
         const long long rows = min((long long)p.N - row0, 32LL);
@@ -2781,15 +2754,15 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
                     for (int j = 0; j < 8; ++j) f[j] = gnm_relu(f[j]);
                 }
             }
-            u32x4 A1, A2, A3;
-            lin_split8(f, A1, A2, A3);
-            const lin_bf16x8 a1 = __builtin_bit_cast(lin_bf16x8, A1), a2 = __builtin_bit_cast(lin_bf16x8, A2),
-                             a3 = __builtin_bit_cast(lin_bf16x8, A3);
+            gnm_u32x4 A1, A2, A3;
+            gnm_split8(f, A1, A2, A3);
+            const gnm_bf16x8 a1 = __builtin_bit_cast(gnm_bf16x8, A1), a2 = __builtin_bit_cast(gnm_bf16x8, A2),
+                             a3 = __builtin_bit_cast(gnm_bf16x8, A3);
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const int e = (m * 2 + c) * 64 + lane;
-                const lin_bf16x8 b1 = __builtin_bit_cast(lin_bf16x8, Wf[e]), b2 = __builtin_bit_cast(lin_bf16x8, Wf[EW + e]),
-                                 b3 = __builtin_bit_cast(lin_bf16x8, Wf[2 * EW + e]);
+                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wf[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wf[EW + e]),
+                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wf[2 * EW + e]);
                 dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, dz[c], 0, 0, 0);
                 dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, dz[c], 0, 0, 0);
                 dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, dz[c], 0, 0, 0);
@@ -2845,15 +2818,15 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
             const float4 v0 = *reinterpret_cast<const float4*>(Xs + i * XS + 32 * h + 8 * m);
             const float4 v1 = *reinterpret_cast<const float4*>(Xs + i * XS + 32 * h + 8 * m + 4);
             const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-            u32x4 A1, A2, A3;
-            lin_split8(f, A1, A2, A3);
-            const lin_bf16x8 x1 = __builtin_bit_cast(lin_bf16x8, A1), x2 = __builtin_bit_cast(lin_bf16x8, A2),
-                             x3 = __builtin_bit_cast(lin_bf16x8, A3);
+            gnm_u32x4 A1, A2, A3;
+            gnm_split8(f, A1, A2, A3);
+            const gnm_bf16x8 x1 = __builtin_bit_cast(gnm_bf16x8, A1), x2 = __builtin_bit_cast(gnm_bf16x8, A2),
+                             x3 = __builtin_bit_cast(gnm_bf16x8, A3);
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const int e = (m * 2 + c) * 64 + lane;
-                const lin_bf16x8 b1 = __builtin_bit_cast(lin_bf16x8, Wb[e]), b2 = __builtin_bit_cast(lin_bf16x8, Wb[EW + e]),
-                                 b3 = __builtin_bit_cast(lin_bf16x8, Wb[2 * EW + e]);
+                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wb[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wb[EW + e]),
+                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wb[2 * EW + e]);
                 dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b3, dacc[c], 0, 0, 0);
                 dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, b1, dacc[c], 0, 0, 0);
                 dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b2, dacc[c], 0, 0, 0);
@@ -2879,7 +2852,7 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
             for (int st = 0; st < 8; ++st) {
                 const int idx = lane + 64 * st;
                 const int row = idx >> 4, oc = idx & 15;
-                const u32x4 v = *reinterpret_cast<const u32x4*>(Xs + row * XS + 4 * oc);
+                const gnm_u32x4 v = *reinterpret_cast<const gnm_u32x4*>(Xs + row * XS + 4 * oc);
                 __builtin_amdgcn_raw_buffer_store_b128(v, rd, out_voff + st * out_step, 0, 0);
             }
         }
@@ -2892,16 +2865,16 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
         // ---- dW += dZ^T f(X): both operands from registers, batch rows in the accumulators' order ---------------------
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-            lin_bf16x8 dp[2][3], xp[2][3];
+            gnm_bf16x8 dp[2][3], xp[2][3];
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 float f[8];
-                u32x4 p1, p2, p3;
+                gnm_u32x4 p1, p2, p3;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) f[j] = dz[a][8 * m + j];
-                lin_split8(f, p1, p2, p3);
-                dp[a][0] = __builtin_bit_cast(lin_bf16x8, p1); dp[a][1] = __builtin_bit_cast(lin_bf16x8, p2);
-                dp[a][2] = __builtin_bit_cast(lin_bf16x8, p3);
+                gnm_split8(f, p1, p2, p3);
+                dp[a][0] = __builtin_bit_cast(gnm_bf16x8, p1); dp[a][1] = __builtin_bit_cast(gnm_bf16x8, p2);
+                dp[a][2] = __builtin_bit_cast(gnm_bf16x8, p3);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     float x = xv[8 * m + j][a];
@@ -2911,9 +2884,9 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
                     }
                     f[j] = x;
                 }
-                lin_split8(f, p1, p2, p3);
-                xp[a][0] = __builtin_bit_cast(lin_bf16x8, p1); xp[a][1] = __builtin_bit_cast(lin_bf16x8, p2);
-                xp[a][2] = __builtin_bit_cast(lin_bf16x8, p3);
+                gnm_split8(f, p1, p2, p3);
+                xp[a][0] = __builtin_bit_cast(gnm_bf16x8, p1); xp[a][1] = __builtin_bit_cast(gnm_bf16x8, p2);
+                xp[a][2] = __builtin_bit_cast(gnm_bf16x8, p3);
             }
 #pragma unroll
             for (int a = 0; a < 2; ++a)
@@ -3004,8 +2977,8 @@ static int launch_lb_rz(const LbArgs& a, int grid, hipStream_t s) {
 __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const LbArgs p) {
     constexpr int HP = 64, XS = 68, NW = kRzWaves, NT = NW * 64, TILE = 16 * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    u32x4* Wf = reinterpret_cast<u32x4*>(smem);                   // [3][2 c][64]: (c, lane = 32 kg + n) = W[32c+n][8kg+j], k < K
-    u32x4* Wb = Wf + 3 * 128;                                     // [3][4 m][64]: (m, lane = 32 kg + n) = W[8m+32kg+j][n], n < K
+    gnm_u32x4* Wf = reinterpret_cast<gnm_u32x4*>(smem);                   // [3][2 c][64]: (c, lane = 32 kg + n) = W[32c+n][8kg+j], k < K
+    gnm_u32x4* Wb = Wf + 3 * 128;                                     // [3][4 m][64]: (m, lane = 32 kg + n) = W[8m+32kg+j][n], n < K
     float* Xs_all = reinterpret_cast<float*>(smem + (size_t)(3 * 128 + 3 * 256) * 16);    // [NW][32][XS]
     float* coef = Xs_all + NW * 32 * XS;                          // [6][64]: mean, rstd, cA, m1, m2, bias
     const int tid = threadIdx.x;
@@ -3017,19 +2990,19 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const
     for (int e = tid; e < 128; e += NT) {
         const int n = e & 31, kg = (e >> 5) & 1, c = e >> 6;
         float f[8];
-        u32x4 p1, p2, p3;
+        gnm_u32x4 p1, p2, p3;
 #pragma unroll
         for (int j = 0; j < 8; ++j) f[j] = 8 * kg + j < K ? p.W[(size_t)(32 * c + n) * p.ldw + 8 * kg + j] : 0.f;
-        lin_split8(f, p1, p2, p3);
+        gnm_split8(f, p1, p2, p3);
         Wf[e] = p1; Wf[128 + e] = p2; Wf[256 + e] = p3;
     }
     for (int e = tid; e < 256; e += NT) {
         const int n = e & 31, kg = (e >> 5) & 1, m = e >> 6;
         float f[8];
-        u32x4 p1, p2, p3;
+        gnm_u32x4 p1, p2, p3;
 #pragma unroll
         for (int j = 0; j < 8; ++j) f[j] = n < K ? p.W[(size_t)(8 * m + 32 * kg + j) * p.ldw + n] : 0.f;
-        lin_split8(f, p1, p2, p3);
+        gnm_split8(f, p1, p2, p3);
         Wb[e] = p1; Wb[256 + e] = p2; Wb[512 + e] = p3;
     }
     for (int idx = tid; idx < 64; idx += NT) {
@@ -3084,15 +3057,15 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const
 #pragma unroll
             for (int r = 0; r < 16; ++r) dz[c][r] = 0.f;
         {
-            u32x4 A1, A2, A3;
-            lin_split8(fx, A1, A2, A3);
-            const lin_bf16x8 a1 = __builtin_bit_cast(lin_bf16x8, A1), a2 = __builtin_bit_cast(lin_bf16x8, A2),
-                             a3 = __builtin_bit_cast(lin_bf16x8, A3);
+            gnm_u32x4 A1, A2, A3;
+            gnm_split8(fx, A1, A2, A3);
+            const gnm_bf16x8 a1 = __builtin_bit_cast(gnm_bf16x8, A1), a2 = __builtin_bit_cast(gnm_bf16x8, A2),
+                             a3 = __builtin_bit_cast(gnm_bf16x8, A3);
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const int e = c * 64 + lane;
-                const lin_bf16x8 b1 = __builtin_bit_cast(lin_bf16x8, Wf[e]), b2 = __builtin_bit_cast(lin_bf16x8, Wf[128 + e]),
-                                 b3 = __builtin_bit_cast(lin_bf16x8, Wf[256 + e]);
+                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wf[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wf[128 + e]),
+                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wf[256 + e]);
                 dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, dz[c], 0, 0, 0);
                 dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, dz[c], 0, 0, 0);
                 dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, dz[c], 0, 0, 0);
@@ -3133,13 +3106,13 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const
                 const float4 v0 = *reinterpret_cast<const float4*>(Xs + i * XS + 32 * h + 8 * m);
                 const float4 v1 = *reinterpret_cast<const float4*>(Xs + i * XS + 32 * h + 8 * m + 4);
                 const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                u32x4 A1, A2, A3;
-                lin_split8(f, A1, A2, A3);
-                const lin_bf16x8 x1 = __builtin_bit_cast(lin_bf16x8, A1), x2 = __builtin_bit_cast(lin_bf16x8, A2),
-                                 x3 = __builtin_bit_cast(lin_bf16x8, A3);
+                gnm_u32x4 A1, A2, A3;
+                gnm_split8(f, A1, A2, A3);
+                const gnm_bf16x8 x1 = __builtin_bit_cast(gnm_bf16x8, A1), x2 = __builtin_bit_cast(gnm_bf16x8, A2),
+                                 x3 = __builtin_bit_cast(gnm_bf16x8, A3);
                 const int e = m * 64 + lane;
-                const lin_bf16x8 b1 = __builtin_bit_cast(lin_bf16x8, Wb[e]), b2 = __builtin_bit_cast(lin_bf16x8, Wb[256 + e]),
-                                 b3 = __builtin_bit_cast(lin_bf16x8, Wb[512 + e]);
+                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wb[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wb[256 + e]),
+                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wb[512 + e]);
                 dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b3, dacc, 0, 0, 0);
                 dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, b1, dacc, 0, 0, 0);
                 dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b2, dacc, 0, 0, 0);
@@ -3159,19 +3132,19 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             float f[8];
-            u32x4 p1, p2, p3;
+            gnm_u32x4 p1, p2, p3;
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = xv[8 * m + j];
-            lin_split8(f, p1, p2, p3);
-            const lin_bf16x8 x1 = __builtin_bit_cast(lin_bf16x8, p1), x2 = __builtin_bit_cast(lin_bf16x8, p2),
-                             x3 = __builtin_bit_cast(lin_bf16x8, p3);
+            gnm_split8(f, p1, p2, p3);
+            const gnm_bf16x8 x1 = __builtin_bit_cast(gnm_bf16x8, p1), x2 = __builtin_bit_cast(gnm_bf16x8, p2),
+                             x3 = __builtin_bit_cast(gnm_bf16x8, p3);
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) f[j] = dz[a][8 * m + j];
-                lin_split8(f, p1, p2, p3);
-                const lin_bf16x8 d1 = __builtin_bit_cast(lin_bf16x8, p1), d2 = __builtin_bit_cast(lin_bf16x8, p2),
-                                 d3 = __builtin_bit_cast(lin_bf16x8, p3);
+                gnm_split8(f, p1, p2, p3);
+                const gnm_bf16x8 d1 = __builtin_bit_cast(gnm_bf16x8, p1), d2 = __builtin_bit_cast(gnm_bf16x8, p2),
+                                 d3 = __builtin_bit_cast(gnm_bf16x8, p3);
                 wacc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d1, x3, wacc[a], 0, 0, 0);
                 wacc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d3, x1, wacc[a], 0, 0, 0);
                 wacc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d2, x2, wacc[a], 0, 0, 0);

@@ -20,17 +20,9 @@
 // One launch per layer over (virtual graph, 32-row block), then a launch that adds the readout shares in fixed order,
 // scales by the fp32 1/(n - 1) under graph "average" and applies the classifier head.  No float atomics; every sum has
 // a fixed order, so results are bitwise reproducible and do not depend on how the caller chunks the graphs.
-#include "gnm_common.h"
+#include "gnm_rowblock.h"
 #include <string.h>
 
-typedef __bf16 oc_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int oc_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int oc_u32x2 __attribute__((ext_vector_type(2)));
-
-static constexpr int kOcMaxN = 416;               // 13 row blocks, 26 steps (csrc/evallayer.hip)
-static constexpr int kOcMaxH = 128;
-static constexpr int kOcLinWords = 7;             // the parameter table of evalfwd.hip (gnm_eval_table_words)
-static constexpr int kOcTS = kOcMaxH + 4;         // row stride of the LDS tiles (floats)
 static constexpr int kOcMaxClasses = 8;           // classes per finish launch
 
 struct OcArgs {
@@ -50,35 +42,16 @@ struct OcArgs {
     float* rpart;                                 // [V][wmax][H]: this layer's readout shares
 };
 
-__device__ __forceinline__ void oc_split8(const float* f, oc_bf16x8& p1, oc_bf16x8& p2, oc_bf16x8& p3) {
-    unsigned a1[8], a2[8], a3[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        a1[j] = __float_as_uint(f[j]) & 0xFFFF0000u;
-        const float r1 = f[j] - __uint_as_float(a1[j]);
-        a2[j] = __float_as_uint(r1) & 0xFFFF0000u;
-        a3[j] = __float_as_uint(r1 - __uint_as_float(a2[j]));
-    }
-    oc_u32x4 q1, q2, q3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        q1[j] = __builtin_amdgcn_perm(a1[2 * j + 1], a1[2 * j], 0x07060302u);
-        q2[j] = __builtin_amdgcn_perm(a2[2 * j + 1], a2[2 * j], 0x07060302u);
-        q3[j] = __builtin_amdgcn_perm(a3[2 * j + 1], a3[2 * j], 0x07060302u);
-    }
-    p1 = __builtin_bit_cast(oc_bf16x8, q1); p2 = __builtin_bit_cast(oc_bf16x8, q2); p3 = __builtin_bit_cast(oc_bf16x8, q3);
-}
-
 // FIRST: layer 0 (the first pre-activation from XW and S, see the file header; no product with the adjacency and no
 // first Linear); otherwise a layer >= 1 on the virtual graph's own activations (input width H).
 template <bool FIRST>
 __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p) {
-    __shared__ __attribute__((aligned(16))) float T0[32 * kOcTS];
-    __shared__ __attribute__((aligned(16))) float T1[32 * kOcTS];
+    __shared__ __attribute__((aligned(16))) float T0[32 * kRbTS];
+    __shared__ __attribute__((aligned(16))) float T1[32 * kRbTS];
     __shared__ __attribute__((aligned(16))) float part[4][32][33];
     __shared__ __attribute__((aligned(16))) char lut[128];
     __shared__ unsigned bitsw[8][256];            // word j of thread t's half row of the block's adjacency bits
-    __shared__ float aff[3][3][kOcMaxH];          // per Linear of the MLP: bias, scale, shift (the BatchNorm behind it, folded)
+    __shared__ float aff[3][3][kRbMaxH];          // per Linear of the MLP: bias, scale, shift (the BatchNorm behind it, folded)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -92,48 +65,13 @@ __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p
     if (rb >= W) return;
     const size_t row0 = (size_t)p.vrow_off[b] + (size_t)v * n;    // the virtual graph's rows of Hin / Hout
     const int H = p.H;
-    const int HPW = (((W + 1) >> 1) + 3) & ~3;
+    const int HPW = rb_half_words(W);
     const uint32_t* gbits = p.adj_bits + p.b_bits_off[b];
-    if (!FIRST && tid < 16) {  // nibble e -> bf16 (bit 0, bit 1, bit 2, bit 3) as two words
-        const unsigned one = 0x3F80u;
-        oc_u32x2 t;
-        t.x = ((tid & 1) ? one : 0u) | ((tid & 2) ? one << 16 : 0u);
-        t.y = ((tid & 4) ? one : 0u) | ((tid & 8) ? one << 16 : 0u);
-        *reinterpret_cast<oc_u32x2*>(lut + 8 * tid) = t;
-    }
-    // ---- what the MLP needs that does not depend on the tile, requested now (csrc/evallayer.hip)
-    const int NCT = H >> 5, KSB = 4 / NCT;
-    const int ctB = wave % NCT, khB = wave / NCT;
-    const int ncolB = 32 * ctB + i;                               // output column of this lane = row of W
-    const float* Wk[3];
-    int ldwk[3];
-    float fbw[3][2][8];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        Wk[k] = nullptr; ldwk[k] = 0;
-        if (k < p.m) {
-            const long long* te = p.table + (size_t)(p.l * p.m + k) * kOcLinWords;
-            Wk[k] = reinterpret_cast<const float*>(te[0]);
-            ldwk[k] = (int)te[6];
-            if (tid < H) {
-                const float gam = reinterpret_cast<const float*>(te[2])[tid], bet = reinterpret_cast<const float*>(te[3])[tid];
-                const float rm = reinterpret_cast<const float*>(te[4])[tid], rv = reinterpret_cast<const float*>(te[5])[tid];
-                const float rstd = (float)(1.0 / sqrt((double)rv + (double)p.bn_eps));
-                const float sc = gam * rstd;
-                aff[k][0][tid] = reinterpret_cast<const float*>(te[1])[tid];
-                aff[k][1][tid] = sc;
-                aff[k][2][tid] = bet - rm * sc;
-            }
-            if (!(FIRST && k == 0)) {                             // (layer 0's first Linear ran on the source graphs)
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int k0 = 16 * (khB + KSB * u) + 8 * h;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) fbw[k][u][j] = k0 + j < H ? Wk[k][(size_t)ncolB * ldwk[k] + k0 + j] : 0.f;
-                }
-            }
-        }
-    }
+    if (!FIRST) rb_lut_init(lut, tid);
+    // what the MLP needs that does not depend on the tile, requested now (layer 0's first Linear ran on the source graphs)
+    RbMlp M;
+    rb_mlp_prefetch<FIRST ? 1 : 0>(M, aff, p.table, p.l, p.m, p.bn_eps, H, H, tid, wave, i, h);
+    const int NCT = M.NCT;
     // the combine pass's operands (8 threads per tile row): the row, whether it is a row of the deleted graph, bit
     // (row, v) of the adjacency and the row's reduced degree
     const int row = tid >> 3, c8 = tid & 7;
@@ -147,6 +85,12 @@ __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p
         deg = (float)(rp[vr + 1] - rp[vr] - (int)arv + p.self_loop);
     }
     const float eps_l = p.eps ? p.eps[p.l] : 0.f;
+    // what the layer's last Linear leaves of column c of this thread's row
+    auto last_rule = [&](int c, float y) {
+        if (!keep) y = 0.f;                                       // the deleted row (and rows past n): zeros, not in the readout
+        if (vrow && p.l + 1 < p.L) p.Hout[(row0 + vr) * H + c] = y;
+        return y;
+    };
     if (FIRST) {
         // ---- layer 0: the first Linear's output of the deleted graph from the source graph's XW and S ----------------
         __syncthreads();                                          // the vectors
@@ -166,28 +110,18 @@ __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p
             }
             if (!p.self_loop) t += p.average ? selfw * xw : eps_l * xw;
             float y = gnm_relu((t + aff[0][0][c]) * aff[0][1][c] + aff[0][2][c]);
-            if (last) {
-                if (!keep) y = 0.f;                               // the deleted row (and rows past n): zeros, not in the readout
-                if (vrow && p.l + 1 < p.L) p.Hout[(row0 + vr) * H + c] = y;
-            }
-            T1[row * kOcTS + c] = y;
+            if (last) y = last_rule(c, y);
+            T1[row * kRbTS + c] = y;
         }
     } else {
         // ---- A. aggregation over the virtual graph's activations (row v of them is zero) ---------------------------
         const int NCA = NCT;
         const float* Hg = p.Hin + row0 * H;
-        for (int c = c8; c < H; c += 8) T1[row * kOcTS + c] = Hg[(size_t)vr * H + c];       // the self term, parked
+        for (int c = c8; c < H; c += 8) T1[row * kRbTS + c] = Hg[(size_t)vr * H + c];       // the self term, parked
         {
             const int ksteps = (n + 15) >> 4;
             const int ct = wave % NCA, kh = wave / NCA, KS = 4 / NCA;
-            {   // this lane's half row of the block's adjacency bits -> LDS, one word per (word index, thread)
-                const oc_u32x4* rp4 = reinterpret_cast<const oc_u32x4*>(gbits + (size_t)(rb * 32 + i) * (2 * HPW) + h * HPW);
-                const oc_u32x4 z4 = {0u, 0u, 0u, 0u};
-                const oc_u32x4 a0 = rp4[0];
-                const oc_u32x4 a1 = HPW > 4 ? rp4[1] : z4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { bitsw[j][tid] = a0[j]; bitsw[4 + j][tid] = a1[j]; }
-            }
+            rb_stage_bits(bitsw, gbits, rb, i, h, HPW, tid);
             const unsigned xbytes = (unsigned)(((size_t)(n - 1) * H + H) * 4);
             const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Hg), 0, (int)xbytes, 0x00020000);
             const int c = 32 * ct + i;
@@ -201,35 +135,9 @@ __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p
 #pragma unroll
                 for (int j = 0; j < 8; ++j) d[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xvo, (16 * s + j) * xrow, 0));
             };
-            auto multiply = [&](const float (&d)[8], int s) {
-                oc_bf16x8 a1, a2, a3;
-                oc_split8(d, a1, a2, a3);
-                // the 8 bits of (row 32 rb + i, columns 16 s + 8 h ..): byte s & 3 of word s >> 2 of this lane's half row
-                const unsigned pkw = bitsw[s >> 2][tid];
-                const unsigned byte3 = ((pkw >> (8 * (s & 3))) & 0xFFu) << 3;
-                const unsigned lo = byte3 & 0x78u, hi = (byte3 >> 4) & 0x78u;
-                const oc_u32x2 l2 = *reinterpret_cast<const oc_u32x2*>(lut + lo);
-                const oc_u32x2 h2 = *reinterpret_cast<const oc_u32x2*>(lut + hi);
-                const oc_u32x4 qq = {l2.x, l2.y, h2.x, h2.y};
-                const oc_bf16x8 bq = __builtin_bit_cast(oc_bf16x8, qq);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, bq, acc, 0, 0, 0);      // small planes first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bq, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bq, acc, 0, 0, 0);
-            };
-            // this wave's steps s = kh + KS u, four to an iteration, three requests ahead of the one being multiplied
-            float hb0[8], hb1[8], hb2[8], hb3[8];
-            request(hb0, kh); request(hb1, kh + KS); request(hb2, kh + 2 * KS);
-#pragma nounroll
-            for (int s = kh; s < ksteps; s += 4 * KS) {           // wave-uniform
-                request(hb3, s + 3 * KS);
-                multiply(hb0, s);
-                if (s + KS < ksteps) { request(hb0, s + 4 * KS); multiply(hb1, s + KS); }
-                if (s + 2 * KS < ksteps) { request(hb1, s + 5 * KS); multiply(hb2, s + 2 * KS); }
-                if (s + 3 * KS < ksteps) { request(hb2, s + 6 * KS); multiply(hb3, s + 3 * KS); }
-            }
+            rb_bits_product(acc, request, kh, KS, ksteps, lut, bitsw, tid);
             // accumulator (r, lane): input column 32 ct + (r & 3) + 8 (r >> 2) + 4 h, output row i
-#pragma unroll
-            for (int r = 0; r < 16; ++r) part[wave][i][(r & 3) + 8 * (r >> 2) + 4 * h] = acc[r];
+            rb_acc_to_part_rows(part, wave, i, h, acc);
         }
         __syncthreads();
         {
@@ -238,81 +146,23 @@ __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p
             for (int c = c8; c < H; c += 8) {
                 float t = 0.f;
                 for (int k = 0; k < KS; ++k) t += part[(c >> 5) + NCA * k][row][c & 31];
-                const float hin = T1[row * kOcTS + c];
+                const float hin = T1[row * kRbTS + c];
                 if (p.self_loop) t += hin;
                 if (p.average) {
                     if (deg == 0.f) t = 0.f;                      // no neighbour left: 0 / 0 -> NaN as in the reference
                     t /= deg;
                 }
                 if (!p.self_loop) t += selfw * hin;
-                T0[row * kOcTS + c] = vrow ? t : 0.f;
+                T0[row * kRbTS + c] = vrow ? t : 0.f;
             }
         }
     }
     // ---- B. the MLP (layer 0: from its second Linear) ----------------------------------------------------------
     float* Tin = FIRST ? T1 : T0;
     float* Tout = FIRST ? T0 : T1;
-#pragma unroll
-    for (int k = FIRST ? 1 : 0; k < 3; ++k) {
-        if (k >= p.m) break;                                      // workgroup-uniform
-        const int ct = ctB, kh = khB, ncol = ncolB;
-        const int nst = H >> 4;
-        __syncthreads();                                          // the input tile (and, the first time, the vectors) complete
-        {
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            auto stepB = [&](const float (&fb)[8], int s) {
-                const int k0 = 16 * s + 8 * h;
-                float fa[8];
-                const float4 v0 = *reinterpret_cast<const float4*>(Tin + i * kOcTS + k0);
-                const float4 v1 = *reinterpret_cast<const float4*>(Tin + i * kOcTS + k0 + 4);
-                fa[0] = v0.x; fa[1] = v0.y; fa[2] = v0.z; fa[3] = v0.w; fa[4] = v1.x; fa[5] = v1.y; fa[6] = v1.z; fa[7] = v1.w;
-                oc_bf16x8 a1, a2, a3, b1, b2, b3;
-                oc_split8(fa, a1, a2, a3);
-                oc_split8(fb, b1, b2, b3);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc, 0, 0, 0);      // small terms first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
-            };
-            if (kh < nst) stepB(fbw[k][0], kh);
-            if (kh + KSB < nst) stepB(fbw[k][1], kh + KSB);
-#pragma nounroll
-            for (int s = kh + 2 * KSB; s < nst; s += KSB) {
-                const int k0 = 16 * s + 8 * h;
-                float fb[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) fb[j] = k0 + j < H ? Wk[k][(size_t)ncol * ldwk[k] + k0 + j] : 0.f;
-                stepB(fb, s);
-            }
-            // accumulator (r, lane): tile row (r & 3) + 8 (r >> 2) + 4 h, output column 32 ct + i
-#pragma unroll
-            for (int r = 0; r < 16; ++r) part[wave][(r & 3) + 8 * (r >> 2) + 4 * h][i] = acc[r];
-        }
-        __syncthreads();
-        const bool last = k == p.m - 1;
-        for (int c = c8; c < H; c += 8) {
-            float z = aff[k][0][c];
-            for (int u = 0; u < KSB; ++u) z += part[(c >> 5) + NCT * u][row][c & 31];
-            float y = gnm_relu(z * aff[k][1][c] + aff[k][2][c]);        // mlp.py:48 (inner) / graphcnn.py:163-166, 187-190 (outer)
-            if (last) {
-                if (!keep) y = 0.f;                               // the deleted row (and rows past n): zeros, not in the readout
-                if (vrow && p.l + 1 < p.L) p.Hout[(row0 + vr) * H + c] = y;
-            }
-            Tout[row * kOcTS + c] = y;
-        }
-        float* t = Tin; Tin = Tout; Tout = t;
-    }
-    __syncthreads();
-    // the block's share of the deleted graph's readout (graphcnn.py:228-229): column sums of its rows, fixed order
-    if (tid < H) {
-        float ssum = 0.f;
-        for (int r = 0; r < 32; ++r) ssum += Tin[r * kOcTS + tid];
-        p.rpart[((size_t)q * p.wmax + rb) * H + tid] = ssum;
-    }
+    rb_mlp_forward<FIRST ? 1 : 0>(M, aff, part, Tin, Tout, p.m, H, H, wave, i, h, row, c8, last_rule);
+    // the block's share of the deleted graph's readout
+    rb_readout_share(Tin, H, tid, p.rpart + ((size_t)q * p.wmax + rb) * H);
 }
 
 struct OcFinArgs {
@@ -332,24 +182,14 @@ __global__ void __launch_bounds__(256) gnm_occlusion_finish_kernel(const OcFinAr
     const int W = (n + 31) >> 5, H = p.H, LH = p.L * p.H;
     for (int e = tid; e < LH; e += 256) {
         const int l = e / H, c = e - l * H;
-        float s = 0.f;
-        for (int rb = 0; rb < W; ++rb) s += p.rpart[(((size_t)l * p.V + q) * p.wmax + rb) * H + c];
+        float s = rb_readout_sum(p.rpart, p.V, q, p.wmax, W, H, l, c);
         if (p.graph_avg) s *= 1.0f / (float)(n - 1);    // the reference stores 1./len(graph.g) as fp32 (graphcnn.py:123,130)
         gfl[e] = s;
     }
     __syncthreads();
-    // classifier head (graphcnn.py:224-231, eval: no dropout): a wave per class, lanes over the L*H products
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63, wave = tid >> 6;   // a wave per class
     for (int ci = wave; ci < p.ncls; ci += 4) {
-        const int cls = p.cls[ci];
-        float acc = 0.f;
-        for (int e = lane; e < LH; e += 64) {
-            const int l = e / H, c = e - l * H;
-            const long long* th = p.table + (size_t)p.L * p.m * kOcLinWords + 2 * l;
-            acc += gfl[e] * reinterpret_cast<const float*>(th[0])[(size_t)cls * H + c];
-        }
-        if (lane < p.L) acc += reinterpret_cast<const float*>((p.table + (size_t)p.L * p.m * kOcLinWords + 2 * lane)[1])[cls];
-        acc = wave_sum(acc);
+        const float acc = rb_readout_head(gfl, p.table, p.L, p.m, H, p.cls[ci], lane);
         if (lane == 0) p.out[(size_t)ci * p.ldo + q] = acc;
     }
 }
@@ -371,7 +211,7 @@ extern "C" int gnm_occlusion(const uint32_t* adj_bits, const int64_t* b_bits_off
                              void* stream) {
     if (B == 0 || V == 0) return GNM_OK;
     if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || C < 1 || C > 256 || n_max < 2 ||
-        n_max > kOcMaxN)
+        n_max > kRbMaxN)
         return GNM_ERR_UNSUPPORTED;
     if (B < 0 || V < 0 || rows < V || ldo < V || !classes_host || n_classes < 1) return GNM_ERR_BAD_ARG;
     for (int k = 0; k < n_classes; ++k)

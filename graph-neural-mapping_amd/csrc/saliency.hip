@@ -22,18 +22,11 @@
 // leaves in memory anyway.
 // gnm_saliency_maps runs the same layer launches (kMaps = true) to form the gradient class activation map
 // sum_l <dscore/dh_l[v], h_l[v]> in stage B instead of dX: L launches, no final one.
-#include "gnm_common.h"
+#include "gnm_rowblock.h"
 #include <string.h>
 
-typedef __bf16 sl_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int sl_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int sl_u32x2 __attribute__((ext_vector_type(2)));
-
-static constexpr int kSlMaxN = 416;               // as evallayer.hip: a block's bit rows fit 8 words per lane
-static constexpr int kSlMaxH = 128;
 static constexpr int kSlMaxL = 16;              // layers (the S / R placement arrays of the launchers)
 static constexpr int kSlLinWords = 6;             // per (layer, Linear): W, ld W, z, ld z, scale, shift
-static constexpr int kSlTS = kSlMaxH + 4;         // row stride of the LDS tiles (floats)
 
 extern "C" int gnm_linear_max_k(int H);
 
@@ -53,51 +46,13 @@ struct SlArgs {
     float* gcam;                                  // gnm_saliency_maps: OUTPUT [N], the gradient class activation map
 };
 
-__device__ __forceinline__ void sl_split8(const float* f, sl_bf16x8& p1, sl_bf16x8& p2, sl_bf16x8& p3) {
-    unsigned a1[8], a2[8], a3[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        a1[j] = __float_as_uint(f[j]) & 0xFFFF0000u;
-        const float r1 = f[j] - __uint_as_float(a1[j]);
-        a2[j] = __float_as_uint(r1) & 0xFFFF0000u;
-        a3[j] = __float_as_uint(r1 - __uint_as_float(a2[j]));
-    }
-    sl_u32x4 q1, q2, q3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        q1[j] = __builtin_amdgcn_perm(a1[2 * j + 1], a1[2 * j], 0x07060302u);
-        q2[j] = __builtin_amdgcn_perm(a2[2 * j + 1], a2[2 * j], 0x07060302u);
-        q3[j] = __builtin_amdgcn_perm(a3[2 * j + 1], a3[2 * j], 0x07060302u);
-    }
-    p1 = __builtin_bit_cast(sl_bf16x8, q1); p2 = __builtin_bit_cast(sl_bf16x8, q2); p3 = __builtin_bit_cast(sl_bf16x8, q3);
-}
-
-// acc += T[32 x 16 s ..] x W[16 s .., col], the split-precision product of evallayer.hip (A from the LDS tile, row i of
-// the lane; B = 8 consecutive rows k of W's column `col`, already in fb)
-__device__ __forceinline__ void sl_step(f32x16& acc, const float* T, int i, int h, int s, const float (&fb)[8]) {
-    const int k0 = 16 * s + 8 * h;
-    float fa[8];
-    const float4 v0 = *reinterpret_cast<const float4*>(T + i * kSlTS + k0);
-    const float4 v1 = *reinterpret_cast<const float4*>(T + i * kSlTS + k0 + 4);
-    fa[0] = v0.x; fa[1] = v0.y; fa[2] = v0.z; fa[3] = v0.w; fa[4] = v1.x; fa[5] = v1.y; fa[6] = v1.z; fa[7] = v1.w;
-    sl_bf16x8 a1, a2, a3, b1, b2, b3;
-    sl_split8(fa, a1, a2, a3);
-    sl_split8(fb, b1, b2, b3);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc, 0, 0, 0);      // small terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
-}
-
 // kMaps (gnm_saliency_maps): stage B also forms the row's gradient class activation <dscore/dh_l[v], h_l[v]>
 // (graphcnn.py:284,289) and stores (top layer) or adds it to p.gcam[v]; layer 0 stops there.  kMaps = false is
 // gnm_saliency's kernel, whose code the other form leaves as it was.
 template <bool kMaps>
 __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p) {
-    __shared__ __attribute__((aligned(16))) float T0[32 * kSlTS];
-    __shared__ __attribute__((aligned(16))) float T1[32 * kSlTS];
+    __shared__ __attribute__((aligned(16))) float T0[32 * kRbTS];
+    __shared__ __attribute__((aligned(16))) float T1[32 * kRbTS];
     __shared__ __attribute__((aligned(16))) float part[4][32][33];
     __shared__ __attribute__((aligned(16))) char lut[128];
     __shared__ unsigned bitsw[8][256];
@@ -112,13 +67,7 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
     if (rb >= W) return;                          // (also an empty graph)
     const int H = p.H, l = p.l;
     const int ksteps = (n + 15) >> 4;
-    if (tid < 16) {            // nibble e -> bf16 (bit 0, bit 1, bit 2, bit 3) as two words
-        const unsigned one = 0x3F80u;
-        sl_u32x2 v;
-        v.x = ((tid & 1) ? one : 0u) | ((tid & 2) ? one << 16 : 0u);
-        v.y = ((tid & 4) ? one : 0u) | ((tid & 8) ? one << 16 : 0u);
-        *reinterpret_cast<sl_u32x2*>(lut + 8 * tid) = v;
-    }
+    rb_lut_init(lut, tid);
     // the combine passes: 8 threads per tile row
     const int row = tid >> 3, c8 = tid & 7;
     const int vr = min(rb * 32 + row, n - 1);
@@ -131,16 +80,7 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
     const bool agg = p.Sin != nullptr;
     if (agg) {
         const int ct = wave % NCT, kh = wave / NCT;
-        const int HPW = (((W + 1) >> 1) + 3) & ~3;
-        {
-            const uint32_t* gbits = p.adj_bits + p.b_tbits_off[b];
-            const sl_u32x4* rp = reinterpret_cast<const sl_u32x4*>(gbits + (size_t)(rb * 32 + i) * (2 * HPW) + h * HPW);
-            const sl_u32x4 z4 = {0u, 0u, 0u, 0u};
-            const sl_u32x4 a0 = rp[0];
-            const sl_u32x4 a1 = HPW > 4 ? rp[1] : z4;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { bitsw[j][tid] = a0[j]; bitsw[4 + j][tid] = a1[j]; }
-        }
+        rb_stage_bits(bitsw, p.adj_bits + p.b_tbits_off[b], rb, i, h, rb_half_words(W), tid);
         // rows past n read zero: the row offset travels in the VECTOR offset, which the descriptor's range check covers
         const unsigned sbytes = (unsigned)(((size_t)(n - 1) * p.lds + H) * 4);
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -156,33 +96,9 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
             for (int j = 0; j < 8; ++j)
                 d[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, svo + (unsigned)(16 * s + j) * srow, 0, 0));
         };
-        auto multiply = [&](const float (&d)[8], int s) {
-            sl_bf16x8 a1, a2, a3;
-            sl_split8(d, a1, a2, a3);
-            const unsigned pkw = bitsw[s >> 2][tid];
-            const unsigned byte3 = ((pkw >> (8 * (s & 3))) & 0xFFu) << 3;
-            const unsigned lo = byte3 & 0x78u, hi = (byte3 >> 4) & 0x78u;
-            const sl_u32x2 l2 = *reinterpret_cast<const sl_u32x2*>(lut + lo);
-            const sl_u32x2 h2 = *reinterpret_cast<const sl_u32x2*>(lut + hi);
-            const sl_u32x4 q = {l2.x, l2.y, h2.x, h2.y};
-            const sl_bf16x8 bq = __builtin_bit_cast(sl_bf16x8, q);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, bq, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bq, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bq, acc, 0, 0, 0);
-        };
-        float hb0[8], hb1[8], hb2[8], hb3[8];
-        request(hb0, kh); request(hb1, kh + KSB); request(hb2, kh + 2 * KSB);
-#pragma nounroll
-        for (int s = kh; s < ksteps; s += 4 * KSB) {              // wave-uniform
-            request(hb3, s + 3 * KSB);
-            multiply(hb0, s);
-            if (s + KSB < ksteps) { request(hb0, s + 4 * KSB); multiply(hb1, s + KSB); }
-            if (s + 2 * KSB < ksteps) { request(hb1, s + 5 * KSB); multiply(hb2, s + 2 * KSB); }
-            if (s + 3 * KSB < ksteps) { request(hb2, s + 6 * KSB); multiply(hb3, s + 3 * KSB); }
-        }
+        rb_bits_product(acc, request, kh, KSB, ksteps, lut, bitsw, tid);
         // accumulator (r, lane): column 32 ct + (r & 3) + 8 (r >> 2) + 4 h of S, output row i
-#pragma unroll
-        for (int r = 0; r < 16; ++r) part[wave][i][(r & 3) + 8 * (r >> 2) + 4 * h] = acc[r];
+        rb_acc_to_part_rows(part, wave, i, h, acc);
     }
     __syncthreads();
     // ---- B. gradient at h_l (or, final launch, at pooled_0 before W0) -> T0 --------------------------------------
@@ -215,7 +131,7 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
                 if constexpr (kMaps) dot += g * gnm_relu(y);       // g = dscore / dh_l, before the mask
                 g = (y > 0.f) ? g * sc : 0.f;                      // outer BatchNorm + ReLU (graphcnn.py:163-166)
             }
-            T0[row * kSlTS + c] = vrow ? g : 0.f;
+            T0[row * kRbTS + c] = vrow ? g : 0.f;
         }
         if constexpr (kMaps) {                                    // the row's 8 lanes: a fixed butterfly
             dot += __shfl_xor(dot, 4, 8);
@@ -247,10 +163,9 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
                 float fb[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) fb[j] = Wk[(size_t)(k0 + j) * ldw + ncol];
-                sl_step(acc, Tin, i, h, s, fb);
+                gnm_tile_step(acc, Tin, kRbTS, i, h, s, fb);
             }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) part[wave][(r & 3) + 8 * (r >> 2) + 4 * h][i] = acc[r];
+            rb_acc_to_part_cols(part, wave, i, h, acc);
             __syncthreads();
             const float* zp = nullptr; const float* scp = nullptr; const float* shp = nullptr;
             int ldz = 0;
@@ -266,7 +181,7 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
                     const float z = zp[(size_t)grow * ldz + c], sc = scp[c];
                     v = (z * sc + shp[c] > 0.f) ? v * sc : 0.f;
                 }
-                Tout[row * kSlTS + c] = vrow ? v : 0.f;
+                Tout[row * kRbTS + c] = vrow ? v : 0.f;
             }
             float* t = Tin; Tin = Tout; Tout = t;
         }
@@ -274,7 +189,7 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
         __syncthreads();
         if (vrow) {
             for (int c = c8; c < H; c += 8) {
-                const float g = Tin[row * kSlTS + c];
+                const float g = Tin[row * kRbTS + c];
                 p.Sout[(size_t)grow * p.lds + c] = p.average ? g / deg : g;
                 if (p.Rout) p.Rout[(size_t)grow * p.lds + c] = g;
             }
@@ -301,7 +216,7 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
                 float fb[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) fb[j] = ncol < F0 ? W0[(size_t)(k0 + j) * ldw0 + ncol] : 0.f;
-                sl_step(acc, Tin, i, h, s, fb);
+                gnm_tile_step(acc, Tin, kRbTS, i, h, s, fb);
             }
             if (ncol < F0) {
 #pragma unroll
@@ -327,11 +242,10 @@ __global__ void __launch_bounds__(256) gnm_saliency_layer_kernel(const SlArgs p)
                 float fb[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) fb[j] = ncol < F0 ? W0[(size_t)(k0 + j) * ldw0 + ncol] : 0.f;
-                sl_step(acc, Tin, i, h, s, fb);
+                gnm_tile_step(acc, Tin, kRbTS, i, h, s, fb);
             }
         }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) part[wave][(r & 3) + 8 * (r >> 2) + 4 * h][i] = acc[r];
+        rb_acc_to_part_cols(part, wave, i, h, acc);
         __syncthreads();
         if (vrow) {
             for (int c = c8; c < F0; c += 8) {
@@ -359,7 +273,7 @@ static int sl_setup(SlArgs& a, const uint32_t* adj_bits, const int64_t* b_tbits_
                     int C, int cls, int average, int self_loop, int graph_avg, const long long* table, const float* eps,
                     const float* scratch, bool bad_shape, bool bad_arg, bool null_arg, bool misaligned,
                     long long row_floats) {
-    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > kSlMaxL || n_max < 1 || n_max > kSlMaxN ||
+    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > kSlMaxL || n_max < 1 || n_max > kRbMaxN ||
         C < 1 || bad_shape)
         return GNM_ERR_UNSUPPORTED;
     if (cls < 0 || cls >= C || N < 1 || bad_arg) return GNM_ERR_BAD_ARG;

@@ -9,10 +9,7 @@
 // gnm_wgrad_split128_kernel) -- are split in registers into three exact bf16 planes and multiplied as six bf16 terms
 // (see gnm_lin_split_kernel: fp32-accurate, 16x the rate of the fp32 instruction).  The eight partial tiles are added in a
 // fixed order through LDS: one launch, bitwise reproducible.  320 or 100 workgroups -- about one per CU.
-#include "gnm_common.h"
-
-typedef __bf16 sg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int sg_u32x4 __attribute__((ext_vector_type(4)));
+#include "gnm_split.h"
 
 struct SgArgs {
     const float* A; const float* B; float* C;
@@ -22,25 +19,6 @@ struct SgArgs {
     int b_cols;      // 0: B given as [n][k] (ldb >= K: C = A Bn^T); 1: B given as [k][n] (ldb >= N)
     int a_vec, b_vec;   // row-major operand 16-byte addressable (else 4-byte loads)
 };
-
-__device__ __forceinline__ void sg_split8(const float* f, sg_bf16x8& p1, sg_bf16x8& p2, sg_bf16x8& p3) {
-    unsigned a1[8], a2[8], a3[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        a1[j] = __float_as_uint(f[j]) & 0xFFFF0000u;
-        const float r1 = f[j] - __uint_as_float(a1[j]);
-        a2[j] = __float_as_uint(r1) & 0xFFFF0000u;
-        a3[j] = __float_as_uint(r1 - __uint_as_float(a2[j]));
-    }
-    sg_u32x4 q1, q2, q3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        q1[j] = __builtin_amdgcn_perm(a1[2 * j + 1], a1[2 * j], 0x07060302u);
-        q2[j] = __builtin_amdgcn_perm(a2[2 * j + 1], a2[2 * j], 0x07060302u);
-        q3[j] = __builtin_amdgcn_perm(a3[2 * j + 1], a3[2 * j], 0x07060302u);
-    }
-    p1 = __builtin_bit_cast(sg_bf16x8, q1); p2 = __builtin_bit_cast(sg_bf16x8, q2); p3 = __builtin_bit_cast(sg_bf16x8, q3);
-}
 
 // One operand fragment of step s for this lane: eight values along the contraction index (k = 16 s + 8 h + 0..7) of
 // row / column `line` (= 32 tile + i).  Rows, columns and steps past the operand read zero (offsets the descriptor
@@ -60,8 +38,8 @@ __device__ __forceinline__ void sg_fetch(const __amdgpu_buffer_rsrc_t rs, int ld
             f[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff, (16 * s + j) * ld * 4, 0));
     } else if constexpr (MODE == 0) {
         const unsigned off = (line < nlines && k0 < K) ? (unsigned)((line * ld + k0) * 4) : 0xFFFFFFE0u;
-        const sg_u32x4 v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-        const sg_u32x4 v1 = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 16, 0);
+        const gnm_u32x4 v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+        const gnm_u32x4 v1 = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 16, 0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) { f[j] = __uint_as_float(v0[j]); f[4 + j] = __uint_as_float(v1[j]); }
     } else {
@@ -109,15 +87,10 @@ __global__ void __launch_bounds__(kSgWaves * 64) gnm_small_gemm_kernel(const SgA
 #pragma unroll
         for (int u = 0; u < D; ++u) {
             if (base + kSgWaves * u < nsteps) {                   // wave-uniform
-                sg_bf16x8 a1, a2, a3, b1, b2, b3;
-                sg_split8(fa[u], a1, a2, a3);
-                sg_split8(fb[u], b1, b2, b3);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc, 0, 0, 0);      // small terms first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
+                gnm_bf16x8 a1, a2, a3, b1, b2, b3;
+                gnm_split8(fa[u], a1, a2, a3);
+                gnm_split8(fb[u], b1, b2, b3);
+                gnm_mma6(acc, a1, a2, a3, b1, b2, b3);
             }
         }
     }

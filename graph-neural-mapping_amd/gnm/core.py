@@ -714,28 +714,48 @@ def eval_forward_fused(spec, batch, perm, P, X, want_disc, mode=True):
     return c_logit, d_logit, g_f
 
 
-def saliency_decline(spec, batch, X, P, dx):
-    """None if csrc/saliency.hip takes this batch, else the condition it declines.  dx: the input width must fit
-    gnm_saliency's dX launch (GIN_InfoMaxReg.saliency(); the gradient class activation and edge maps never form dX)."""
-    H = P["batch_norms.0.weight"].shape[0]
+def _rowblock_graph_decline(spec, batch, H):
+    """The graphs and width the 32-row-block kernels (csrc/gnm_rowblock.h) take: None, or the condition declined"""
     if spec.n_max:
         return "max neighbour pooling"
     if not getattr(batch, "has_bits", False) or batch.n_max > 416:
         return "a graph of more than 416 nodes or without a bit adjacency"
     if H not in (32, 64, 128):
         return "hidden_dim %d not in {32, 64, 128}" % H
-    if spec.n_avg and spec.learn_eps and getattr(batch, "iso", False):
-        # the 0/0 row of an isolated node: the autograd path's NaN semantics, not re-derived here
-        return "average neighbour pooling with learned eps and an isolated node"
+    return None
+
+
+def _rowblock_model_decline(spec, batch, X):
+    """The model and batch the 32-row-block kernels take: None, or the condition declined"""
     if not 1 <= spec.m <= 3 or spec.L > 16:
         return "num_mlp_layers outside 1..3 or more than 16 layers"
     if spec.sync_bn is not None:
         return "synchronised BatchNorm"
     if not X.is_cuda or batch.B < 1:
         return "an empty batch or one off the GPU"
-    if dx and not 1 <= X.shape[1] <= int(lib.gnm_linear_max_k(H)):
+    return None
+
+
+def _width_decline(X, H):
+    """None if the split-precision Linear takes X's width as its contraction, else the condition declined"""
+    if not 1 <= X.shape[1] <= int(lib.gnm_linear_max_k(H)):
         return "input width %d outside 1..%d" % (X.shape[1], int(lib.gnm_linear_max_k(H)))
     return None
+
+
+def saliency_decline(spec, batch, X, P, dx):
+    """None if csrc/saliency.hip takes this batch, else the condition it declines.  dx: the input width must fit
+    gnm_saliency's dX launch (GIN_InfoMaxReg.saliency(); the gradient class activation and edge maps never form dX)."""
+    H = P["batch_norms.0.weight"].shape[0]
+    why = _rowblock_graph_decline(spec, batch, H)
+    if why is None and spec.n_avg and spec.learn_eps and getattr(batch, "iso", False):
+        # the 0/0 row of an isolated node: the autograd path's NaN semantics, not re-derived here
+        why = "average neighbour pooling with learned eps and an isolated node"
+    if why is None:
+        why = _rowblock_model_decline(spec, batch, X)
+    if why is None and dx:
+        why = _width_decline(X, H)
+    return why
 
 
 def _saliency_table_words(spec, P, saved):
@@ -769,16 +789,23 @@ def _out_array(out, shape, dev):
     return out
 
 
+def _launch_dims(spec, batch, X, P):
+    """What every eval-mode attribution driver reads off its arguments: the launch device, the dimensions, the
+    row-contiguous features and the device pointer of eps (None unless learned)"""
+    return types.SimpleNamespace(dev=launch_device(X, P["eps"]), L=spec.L, m=spec.m, N=batch.N, B=batch.B,
+                                 F0=X.shape[1], H=P["batch_norms.0.weight"].shape[0],
+                                 Cn=P["linears_prediction.0.weight"].shape[0], X=X.contiguous(),
+                                 eps=P["eps"].data_ptr() if spec.learn_eps else None)
+
+
 @contextlib.contextmanager
 def _saliency_launch(spec, batch, X, P, scratch_floats):
     """What saliency_hip, saliency_maps_hip and edge_saliency_hip share, as the scope of their launches (no autograd,
     the tensors' device and its stream): the dimensions, ONE eval forward through the training kernels (encoder_forward,
     BatchNorm on its running statistics; it leaves every Linear's pre-BatchNorm output z, which give the ReLU masks),
     gnm_saliency's parameter table over it on the device, and scratch_floats(N, H) floats of scratch."""
-    dev = launch_device(X, P["eps"])
-    k = types.SimpleNamespace(dev=dev, N=batch.N, B=batch.B, F0=X.shape[1], H=P["batch_norms.0.weight"].shape[0],
-                              Cn=P["linears_prediction.0.weight"].shape[0], X=X.contiguous(),
-                              eps=P["eps"].data_ptr() if spec.learn_eps else None)
+    k = _launch_dims(spec, batch, X, P)
+    dev = k.dev
     with torch.no_grad(), _stream_scope(dev):
         _, _, saved = encoder_forward(spec, batch, k.X, P, training=False, update_running=False)
         k.table = torch.tensor(_saliency_table_words(spec, P, saved), dtype=torch.int64).pin_memory().to(
@@ -816,15 +843,11 @@ def class_activation_hip(spec, batch, X, P, classes, out=None):
     (encoder_forward, BatchNorm on its running statistics), then gnm_class_activation, which re-forms each h_l from the
     layer's z, scale and shift.  Any neighbour pooling or adjacency form.  Parameters, buffers and the numpy RNG are not
     touched.  Returns a float32 [len(classes), N] tensor (`out` when given)."""
-    dev = launch_device(X, P["eps"])
-    L, m = spec.L, spec.m
-    N, B = batch.N, batch.B
-    H = P["batch_norms.0.weight"].shape[0]
-    Cn = P["linears_prediction.0.weight"].shape[0]
-    X = X.contiguous()
+    d = _launch_dims(spec, batch, X, P)
+    dev, L, m, N, B, H, Cn = d.dev, d.L, d.m, d.N, d.B, d.H, d.Cn
     out = _out_array(out, (len(classes), N), dev)
     with torch.no_grad(), _stream_scope(dev):
-        _, _, saved = encoder_forward(spec, batch, X, P, training=False, update_running=False)
+        _, _, saved = encoder_forward(spec, batch, d.X, P, training=False, update_running=False)
         words = []
         for l in range(L):
             sv = saved[l].lins[m - 1]
@@ -893,23 +916,10 @@ def occlusion_decline(spec, batch, X, P):
     """None if csrc/occlusion.hip takes this batch, else the condition it declines.  Unlike saliency_decline an isolated
     node under average pooling with learned eps is taken: a deleted graph's NaN stays in its own score."""
     H = P["batch_norms.0.weight"].shape[0]
-    if spec.n_max:
-        return "max neighbour pooling"
-    if not getattr(batch, "has_bits", False) or batch.n_max > 416:
-        return "a graph of more than 416 nodes or without a bit adjacency"
-    if H not in (32, 64, 128):
-        return "hidden_dim %d not in {32, 64, 128}" % H
-    if not 1 <= spec.m <= 3 or spec.L > 16:
-        return "num_mlp_layers outside 1..3 or more than 16 layers"
-    if spec.sync_bn is not None:
-        return "synchronised BatchNorm"
-    if not X.is_cuda or batch.B < 1:
-        return "an empty batch or one off the GPU"
-    if batch.n_min < 2:
-        return "a graph of fewer than 2 nodes"
-    if not 1 <= X.shape[1] <= int(lib.gnm_linear_max_k(H)):
-        return "input width %d outside 1..%d" % (X.shape[1], int(lib.gnm_linear_max_k(H)))
-    return None
+    why = _rowblock_graph_decline(spec, batch, H) or _rowblock_model_decline(spec, batch, X)
+    if why is None and batch.n_min < 2:
+        why = "a graph of fewer than 2 nodes"
+    return why or _width_decline(X, H)
 
 
 # occlusion_hip's scratch (two [sum n^2, H] activation arrays and the readout shares) stays under this many bytes: the
@@ -925,13 +935,8 @@ def occlusion_hip(spec, batch, X, P, classes, out=None):
     graphs whose scratch fits OCCLUSION_SCRATCH_BYTES, L layer launches and the finish launch.  The shapes
     occlusion_decline takes.  Parameters, buffers and the numpy RNG are not touched; the device parameter table is
     eval_forward_fused's.  Returns a float32 [len(classes), N] tensor (`out` when given)."""
-    dev = launch_device(X, P["eps"])
-    L, m = spec.L, spec.m
-    N, B = batch.N, batch.B
-    H = P["batch_norms.0.weight"].shape[0]
-    Cn = P["linears_prediction.0.weight"].shape[0]
-    F0 = X.shape[1]
-    X = X.contiguous()
+    d = _launch_dims(spec, batch, X, P)
+    dev, L, m, N, B, H, Cn, F0, X = d.dev, d.L, d.m, d.N, d.B, d.H, d.Cn, d.F0, d.X
     out = _out_array(out, (len(classes), N), dev)
     cls = (C.c_int * len(classes))(*[int(c) for c in classes])
     offs = np.asarray(batch.node_off_host, dtype=np.int64)
@@ -969,8 +974,8 @@ def occlusion_hip(spec, batch, X, P, classes, out=None):
                                         vrow_off.data_ptr(), g1 - g0, int(nc.max()), V, rows, XW[r0:].data_ptr(),
                                         XW.stride(0), S[r0:].data_ptr(), S.stride(0), H, L, m, Cn, cls, len(classes),
                                         int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS,
-                                        table.data_ptr(), P["eps"].data_ptr() if spec.learn_eps else None,
-                                        scratch.data_ptr(), dst.data_ptr(), out.stride(0), _stream()), "gnm_occlusion")
+                                        table.data_ptr(), d.eps, scratch.data_ptr(), dst.data_ptr(), out.stride(0),
+                                        _stream()), "gnm_occlusion")
             g0 = g1
     return out
 
@@ -997,18 +1002,13 @@ def integrated_gradients_hip(spec, batch, X, P, classes, alphas, weights, baseli
     batch lists every arena graph K times, so it shares the source graphs' adjacency), and per class
     gnm_integrated_gradients.  The shapes saliency_decline(dx=True) takes.  Parameters, buffers and the numpy RNG are
     not touched.  Returns a float32 [len(classes), N, F0] tensor (`out` when given)."""
-    dev = launch_device(X, P["eps"])
-    L, m = spec.L, spec.m
-    N, B = batch.N, batch.B
-    H = P["batch_norms.0.weight"].shape[0]
-    Cn = P["linears_prediction.0.weight"].shape[0]
-    F0 = X.shape[1]
+    d = _launch_dims(spec, batch, X, P)
+    dev, L, m, N, B, H, Cn, F0, X = d.dev, d.L, d.m, d.N, d.B, d.H, d.Cn, d.F0, d.X
     a32 = np.ascontiguousarray(alphas, dtype=np.float64).astype(np.float32)
     w32 = np.ascontiguousarray(weights, dtype=np.float64).astype(np.float32)
     K = int(a32.shape[0])
     if K < 1 or a32.ndim != 1 or w32.shape != a32.shape:
         raise GnmError("integrated gradients need K >= 1 nodes and as many weights")
-    X = X.contiguous()
     out = _out_array(out, (len(classes), N, F0), dev)
     offs = np.asarray(batch.node_off_host, dtype=np.int64)
     ns = np.diff(offs)
@@ -1018,7 +1018,7 @@ def integrated_gradients_hip(spec, batch, X, P, classes, alphas, weights, baseli
         lin0 = "mlps.0.linear" if m == 1 else "mlps.0.linears.0"
         W0, b0 = P[lin0 + ".weight"], P[lin0 + ".bias"].contiguous()
         al, wt = arena._upload(torch.as_tensor(a32)), arena._upload(torch.as_tensor(w32))
-        eps_ptr = P["eps"].data_ptr() if spec.learn_eps else None
+        eps_ptr = d.eps
 
         def pooled_product(src, rows):
             """pool(src) W0^T as pool(src W0^T): src is [rows, F0] (the batch's features, or ONE graph's baseline)"""
