@@ -40,6 +40,32 @@ __device__ __forceinline__ void rb_stage_bits(unsigned (*bitsw)[256], const uint
     for (int j = 0; j < 4; ++j) { bitsw[j][tid] = a0[j]; bitsw[4 + j][tid] = a1[j]; }
 }
 
+// Bit of column v in a row (or a keep mask) of the half-row layout: `row` points at its 2 HPW words
+__device__ __forceinline__ unsigned rb_row_bit(const uint32_t* row, int HPW, int v) {
+    return (row[((v >> 3) & 1) * HPW + (v >> 6)] >> ((((v >> 4) & 3) << 3) + (v & 7))) & 1u;
+}
+
+// rb_stage_bits with every staged word ANDed with a keep mask of the same half-row layout (lesion.hip: `mask` is the
+// virtual graph's 2 HPW words, a bit per kept COLUMN).  Returns the popcount of this lane's masked half row: with the
+// other half's (lane ^ 32) the row's degree in the reduced graph.
+__device__ __forceinline__ int rb_stage_bits_masked(unsigned (*bitsw)[256], const uint32_t* gbits, const uint32_t* mask,
+                                                    int rb, int i, int h, int HPW, int tid) {
+    const gnm_u32x4* rp = reinterpret_cast<const gnm_u32x4*>(gbits + (size_t)(rb * 32 + i) * (2 * HPW) + h * HPW);
+    const uint32_t* mp = mask + h * HPW;
+    const gnm_u32x4 z4 = {0u, 0u, 0u, 0u};
+    const gnm_u32x4 a0 = rp[0];
+    const gnm_u32x4 a1 = HPW > 4 ? rp[1] : z4;
+    int pc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned w0 = a0[j] & mp[j];
+        const unsigned w1 = HPW > 4 ? a1[j] & mp[4 + j] : 0u;
+        bitsw[j][tid] = w0; bitsw[4 + j][tid] = w1;
+        pc += __popc(w0) + __popc(w1);
+    }
+    return pc;
+}
+
 // The 8 bits of (row 32 rb + i, columns 16 s + 8 h ..) as a bf16x8 operand: byte s & 3 of word s >> 2 of the lane's half row
 __device__ __forceinline__ gnm_bf16x8 rb_bits_operand(const char* lut, const unsigned (*bitsw)[256], int s, int tid) {
     const unsigned pkw = bitsw[s >> 2][tid];

@@ -980,6 +980,82 @@ def occlusion_hip(spec, batch, X, P, classes, out=None):
     return out
 
 
+def lesion_decline(spec, batch, X, P):
+    """None if csrc/lesion.hip takes this batch, else the condition it declines: occlusion_decline's conditions (a
+    virtual graph whose NaN stays in its own score is taken; a set leaves at least one node, so a graph needs two)."""
+    return occlusion_decline(spec, batch, X, P)
+
+
+# lesion_hip's scratch (two [sum of n over the virtual graphs, H] activation arrays and the readout shares) stays under
+# this many bytes: the virtual graphs of a batch are run in chunks.  8 graphs x 20 sets at n = 400, H = 128: 0.07 GB.
+LESION_SCRATCH_BYTES = 2 << 30
+
+
+def lesion_hip(spec, batch, X, P, classes, removed, vgraph, out=None):
+    """The eval-mode class scores of set-deleted copies of the graphs of a batch (csrc/lesion.hip, include/gnm_hip.h
+    gnm_lesion): out[ci, q] = c_logit[classes[ci]] of graph vgraph[q] of the batch without the nodes r with
+    removed[q, r] != 0.  removed: a host uint8 / bool array [V, >= n_max] (entries past a graph's n are ignored);
+    vgraph: V host ints in [0, B).  Per batch XW = X W0^T (the split-precision Linear, any input width); then, per chunk
+    of whole virtual graphs whose scratch fits LESION_SCRATCH_BYTES, the mask-packing launch, ONE read-back of the
+    kept counts, L layer launches and the finish launch.  The shapes lesion_decline takes.  Parameters, buffers and the
+    numpy RNG are not touched; the device parameter table is eval_forward_fused's.  Returns a float32
+    [len(classes), V] tensor (`out` when given)."""
+    d = _launch_dims(spec, batch, X, P)
+    dev, L, m, N, B, H, Cn, F0, X = d.dev, d.L, d.m, d.N, d.B, d.H, d.Cn, d.F0, d.X
+    removed = np.ascontiguousarray(np.asarray(removed) != 0, dtype=np.uint8)
+    vgraph = np.ascontiguousarray(vgraph, dtype=np.int32)
+    Vt = int(vgraph.shape[0])
+    nm = int(batch.n_max)
+    if removed.ndim != 2 or removed.shape[0] != Vt or removed.shape[1] < nm:
+        raise GnmError("removed must be [%d, >= %d], got %s" % (Vt, nm, list(removed.shape)))
+    if Vt and (vgraph.min() < 0 or vgraph.max() >= B):
+        raise GnmError("vgraph entries must be graphs of the batch, 0 .. %d" % (B - 1))
+    out = _out_array(out, (len(classes), Vt), dev)
+    cls = (C.c_int * len(classes))(*[int(c) for c in classes])
+    offs = np.asarray(batch.node_off_host, dtype=np.int64)
+    vn = np.diff(offs)[vgraph].astype(np.int32)             # node count of each virtual graph
+    with torch.no_grad(), _stream_scope(dev):
+        table = _eval_table(spec, P, dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        W0 = P["mlps.0.linear.weight" if m == 1 else "mlps.0.linears.0.weight"]
+        XW = torch.empty((N, H), **f32)
+        _linear(X, W0, 0, None, XW, N, F0, H, None, None)
+        up = batch.arena._upload
+        q0 = 0
+        while q0 < Vt:
+            q1, rows, need = q0, 0, 0
+            while q1 < Vt:                  # the longest run of virtual graphs whose scratch fits the budget (at least one)
+                r = rows + int(vn[q1])
+                k = int(lib.gnm_lesion_scratch_floats(r, q1 + 1 - q0, int(vn[q0:q1 + 1].max()), H, L))
+                if q1 > q0 and 4 * k > LESION_SCRATCH_BYTES:
+                    break
+                q1, rows, need = q1 + 1, r, k
+            V, nc = q1 - q0, vn[q0:q1]
+            n_max = int(nc.max())
+            mstride = 2 * (((((n_max + 31) // 32 + 1) >> 1) + 3) & ~3)
+            vg = up(torch.as_tensor(vgraph[q0:q1]))
+            vrow_off = up(torch.as_tensor(np.concatenate([[0], np.cumsum(nc, dtype=np.int64)[:-1]]).astype(np.int64)))
+            rem = up(torch.as_tensor(removed[q0:q1]))
+            masks = torch.empty((V, mstride), dtype=torch.int32, device=dev)
+            kept = torch.empty(V, dtype=torch.int32, device=dev)
+            check(lib.gnm_lesion_pack(rem.data_ptr(), rem.stride(0), vg.data_ptr(), batch.node_off.data_ptr(), B,
+                                      n_max, V, mstride, masks.data_ptr(), kept.data_ptr(), _stream()),
+                  "gnm_lesion_pack")
+            kept_host = kept.cpu().numpy()                  # the one read-back of the chunk
+            scratch = torch.empty(need, **f32)
+            dst = out[:, q0:q1]
+            with _timed("lesion_hip", B=B, N=V, H=H, L=L):
+                check(lib.gnm_lesion(batch.arena.bits.buf.data_ptr(), batch.bits_off.data_ptr(),
+                                     batch.node_off.data_ptr(), vg.data_ptr(), vrow_off.data_ptr(), masks.data_ptr(),
+                                     mstride, kept.data_ptr(), kept_host.ctypes.data, nc.ctypes.data, B, n_max, V,
+                                     rows, XW.data_ptr(), XW.stride(0), H, L, m, Cn, cls, len(classes),
+                                     int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS,
+                                     table.data_ptr(), d.eps, scratch.data_ptr(), dst.data_ptr(), out.stride(0),
+                                     _stream()), "gnm_lesion")
+            q0 = q1
+    return out
+
+
 # integrated_gradients_hip's device arrays per chunk of source graphs stay under this many bytes: the virtual batch's
 # forward keeps every Linear's z and every layer's aggregation, (m L + L - 1) K N H floats, next to 4 K N H of scratch.
 # K = 32, 8 graphs of 400 nodes, H = 64, m = 2, L = 5: 0.26 GB of z, 0.47 GB in all.

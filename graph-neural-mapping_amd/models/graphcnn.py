@@ -34,9 +34,10 @@ from mlp import MLP  # noqa: E402
 from discriminator import Discriminator  # noqa: E402
 from gnm.arena import GraphArena  # noqa: E402
 from gnm.core import (DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, edge_saliency_hip,  # noqa: E402
-                      eval_forward_fused, eval_fused_ok, integrated_gradients_hip, launch_device, occlusion_decline,
-                      occlusion_hip, saliency_decline, saliency_hip, saliency_maps_hip)
+                      eval_forward_fused, eval_fused_ok, integrated_gradients_hip, launch_device, lesion_decline,
+                      lesion_hip, occlusion_decline, occlusion_hip, saliency_decline, saliency_hip, saliency_maps_hip)
 from gnm.intgrad import quadrature  # noqa: E402
+from gnm.lesion import curve_area, default_fractions, masks_from_ranking  # noqa: E402
 
 __all__ = ["GIN_InfoMaxReg", "GraphCNN", "MLP", "Discriminator"]
 
@@ -316,13 +317,9 @@ class GIN_InfoMaxReg(nn.Module):
         self.saliency_routes = routes
         return out
 
-    def _interpret(self, name, graphs, cls, batch_size, tail, run_batch, square=False):
-        """The batching saliency(), class_activation() and edge_saliency() share (`name`, which prefixes the errors):
-        the argument checks, eval mode with the previous mode restored on exit, chunks of batch_size graphs, and the
-        result layout.  run_batch(chunk, batch, P, classes, dst) returns one batch's [len(classes), N, *tail] result
-        (or a list of per-class [N, *tail] tensors), written into dst when that is given: the batch's view of the dense
-        [len(classes), len(graphs), n, *tail] result.  Graphs of different node counts get per-graph lists instead;
-        square: an [n, n] map per graph (tail (n,), each graph's map cropped to its n_g columns)."""
+    def _interpret_args(self, name, graphs, cls, batch_size):
+        """The argument checks every batched attribution method shares (`name` prefixes the errors): (whether cls is
+        one int, the classes as a list)"""
         single = isinstance(cls, (int, np.integer))
         classes = [int(cls)] if single else [int(c) for c in cls]
         n_cls = self.linears_prediction[0].out_features
@@ -335,6 +332,16 @@ class GIN_InfoMaxReg(nn.Module):
                 raise ValueError("%s: class %d out of range for a %d-class model" % (name, c, n_cls))
         if batch_size < 1:
             raise ValueError("%s: batch_size must be positive" % name)
+        return single, classes
+
+    def _interpret(self, name, graphs, cls, batch_size, tail, run_batch, square=False):
+        """The batching saliency(), class_activation() and edge_saliency() share (`name`, which prefixes the errors):
+        the argument checks, eval mode with the previous mode restored on exit, chunks of batch_size graphs, and the
+        result layout.  run_batch(chunk, batch, P, classes, dst) returns one batch's [len(classes), N, *tail] result
+        (or a list of per-class [N, *tail] tensors), written into dst when that is given: the batch's view of the dense
+        [len(classes), len(graphs), n, *tail] result.  Graphs of different node counts get per-graph lists instead;
+        square: an [n, n] map per graph (tail (n,), each graph's map cropped to its n_g columns)."""
+        single, classes = self._interpret_args(name, graphs, cls, batch_size)
         was_training = self.training
         self.eval()
         try:
@@ -556,6 +563,173 @@ class GIN_InfoMaxReg(nn.Module):
             return occlusion_hip(self._spec, batch, X, P, classes, out=dst)
         return self._clean_graphs_apart(chunk, batch, bad, dst, (len(classes), batch.N),
                                         lambda sub, Xs: occlusion_hip(self._spec, sub, Xs, P, classes))
+
+    def lesion(self, graphs, cls, rois, batch_size=8, return_scores=False):
+        """Virtual lesions of ROI SETS of many graphs in batches: how far the class score moves when a whole set of
+        nodes -- a resting-state network, a hemisphere, the top of an attribution map -- is taken out of the graph.
+        occlusion()'s contract with the node replaced by a set D, 0 <= |D| <= n - 1 (the nodes of D, their feature rows
+        and their edges in both directions removed; the other rows unchanged; the readout over n - |D| nodes, graph
+        "average" with the fp32 1/(n - |D|), neighbour "average" by the reduced graph's own degree, self loops kept):
+
+            lesioned[c, g, s] = score_c(G_g \\ D_s),   base[c, g] = score_c(G_g),   delta = base - lesioned  (fp32)
+
+        rois (True / 1 = removed): ONE bool or 0/1 array or tensor [S, n] applied to every graph, which then all have n
+        nodes, or a list of len(graphs) arrays [S_g, n_g].  No copy of a graph is built: csrc/lesion.hip runs every
+        (graph, set) pair as a virtual graph over the source graph's bit adjacency under a keep mask (include/gnm_hip.h
+        gnm_lesion); base is the model's ordinary eval forward.  The empty set is taken (lesioned = the kernel's score
+        of the whole graph, base to fp32 rounding).
+
+        cls: an int, or a sequence of ints; one pass per batch serves all of them.  Returns a float32 device tensor
+        [len(graphs), S] for an int `cls` and [len(cls), len(graphs), S] for a sequence; when the S_g differ a list
+        of [S_g] tensors (a list of such lists for a sequence `cls`).  return_scores=True returns
+        (delta, base, lesioned), base [len(graphs)] / [len(cls), len(graphs)].
+
+        If G \\ D leaves a kept node without neighbours under neighbour "average" with learned eps, the reference's
+        0/0 row makes that score NaN: lesioned[:, g, s] is NaN and no other entry is.  A graph with a non-finite
+        feature gets all-NaN results and its batch-mates run as a clean batch (a stated deviation: the explicit copy
+        would be clean if the bad row were in D).  The shapes occlusion() takes; any other batch raises ValueError
+        naming the condition, as do a set that removes every node of its graph, a mask of the wrong width or with an
+        entry other than 0 / 1, and a shared mask over graphs of different node counts.
+
+        The result is bitwise the same run to run, for any batch_size and whatever other sets share the call (no
+        atomics, fixed summation orders, one virtual graph per workgroup column).  A virtual graph needs 2 n
+        hidden_dim floats of scratch; the virtual graphs of a batch run in chunks under gnm/core.py
+        LESION_SCRATCH_BYTES.  No parameter .grad, BatchNorm buffer or numpy RNG state is touched, and the
+        train / eval mode is restored on exit."""
+        single, classes = self._interpret_args("lesion", graphs, cls, batch_size)
+        sets = self._lesion_sets(graphs, rois)
+        was_training = self.training
+        self.eval()
+        try:
+            names, tensors, buffers = self._param_lists()
+            P = dict(zip(names, tensors))
+            P.update(buffers)
+            bases, parts = [], []
+            for i0 in range(0, len(graphs), batch_size):
+                chunk = graphs[i0:i0 + batch_size]
+                base, les = self._lesion_batch(chunk, self._batch_of(chunk), P, classes, sets[i0:i0 + len(chunk)])
+                bases.append(base)
+                parts.append(les)
+        finally:
+            self.train(was_training)
+        base = torch.cat(bases, 1)                          # [len(classes), len(graphs)]
+        flat = torch.cat(parts, 1)                          # [len(classes), sum of S_g]
+        counts = [int(s.shape[0]) for s in sets]
+        if all(k == counts[0] for k in counts):
+            les = flat.view(len(classes), len(graphs), counts[0])
+            delta = base.unsqueeze(-1) - les
+            if single:
+                delta, base, les = delta[0], base[0], les[0]
+        else:
+            les = [list(torch.split(row, counts)) for row in flat]
+            delta = [[base[ci, j] - o for j, o in enumerate(row)] for ci, row in enumerate(les)]
+            if single:
+                delta, base, les = delta[0], base[0], les[0]
+        return (delta, base, les) if return_scores else delta
+
+    @staticmethod
+    def _lesion_sets(graphs, rois):
+        """lesion()'s `rois` as one bool [S_g, n_g] array per graph, checked"""
+        def as_mask(a, what):
+            a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+            if a.ndim != 2:
+                raise ValueError("lesion: %s must be a 2-D [sets, nodes] array, got shape %s" % (what, list(a.shape)))
+            if a.dtype != np.bool_:
+                if a.dtype.kind not in "iuf" or not np.isin(a, (0, 1)).all():
+                    raise ValueError("lesion: %s must be bool or hold only 0 and 1" % what)
+                a = a != 0
+            return a
+        ns = [len(g.g) for g in graphs]
+        shared = torch.is_tensor(rois) or isinstance(rois, np.ndarray) or (
+            isinstance(rois, (list, tuple)) and len(rois) > 0 and np.ndim(rois[0]) == 1 and not torch.is_tensor(rois[0]))
+        if shared:
+            a = as_mask(rois, "rois")
+            if any(k != ns[0] for k in ns):
+                raise ValueError("lesion: a shared [S, n] mask needs graphs of one node count")
+            sets = [a] * len(graphs)
+        else:
+            if not isinstance(rois, (list, tuple)) or len(rois) != len(graphs):
+                raise ValueError("lesion: rois must be one [S, n] array or a list of one [S_g, n_g] array per graph")
+            sets = [as_mask(a, "rois[%d]" % j) for j, a in enumerate(rois)]
+        for j, (a, n) in enumerate(zip(sets, ns)):
+            if n < 2:
+                raise ValueError("lesion: a graph of fewer than 2 nodes has no lesioned copy")
+            if a.shape[1] != n:
+                raise ValueError("lesion: the mask of graph %d is %d wide for a %d-node graph" % (j, a.shape[1], n))
+            if a.shape[0] and a.all(1).any():
+                raise ValueError("lesion: a set removes every node of graph %d" % j)
+        return sets
+
+    def _lesion_batch(self, chunk, batch, P, classes, sets):
+        """lesion() of one batch: (base [len(classes), B], lesioned [len(classes), sum of S_g], graph by graph)"""
+        X = batch.arena.features(batch).detach()
+        launch_device(X, P["eps"])                          # no CPU fallback: GnmError before any shape question
+        why = lesion_decline(self._spec, batch, X, P)
+        if why is not None:
+            raise ValueError("lesion does not cover this batch: %s" % why)
+        with torch.no_grad():
+            c_logit, _, _ = self._run(batch, X, np.arange(batch.B, dtype=np.int64), want_disc=False)
+        base = c_logit.detach()[:, classes].t().contiguous()
+
+        def run(b, Xb, which):
+            """the virtual graphs of graphs `which` of the chunk, which are the graphs of batch b, in order"""
+            nm = int(b.n_max)
+            removed = np.zeros((sum(sets[j].shape[0] for j in which), nm), dtype=np.uint8)
+            vgraph = np.concatenate([np.full(sets[j].shape[0], k, dtype=np.int32) for k, j in enumerate(which)])
+            q = 0
+            for j in which:
+                s = sets[j]
+                removed[q:q + s.shape[0], :s.shape[1]] = s
+                q += s.shape[0]
+            return lesion_hip(self._spec, b, Xb, P, classes, removed, vgraph)
+
+        bad = _nonfinite_graphs(batch, X)
+        if bad is None:
+            return base, run(batch, X, list(range(batch.B)))
+        # a graph with a non-finite feature: all-NaN results; the others run as a batch of their own
+        cnt = [sets[j].shape[0] for j in range(batch.B)]
+        out = torch.full((len(classes), sum(cnt)), float("nan"), dtype=torch.float32, device=self.eps.device)
+        good = [j for j in range(batch.B) if not bad[j]]
+        if good:
+            sub = self._batch_of([chunk[j] for j in good])
+            r = run(sub, sub.arena.features(sub).detach(), good)
+            starts = np.concatenate([[0], np.cumsum(cnt)])
+            q = 0
+            for j in good:
+                out[:, starts[j]:starts[j] + cnt[j]] = r[:, q:q + cnt[j]]
+                q += cnt[j]
+        return base, out
+
+    def deletion_curve(self, graphs, cls, ranking, fractions=None, order="descending", batch_size=8):
+        """The deletion curve of a per-ROI attribution map, the standard fidelity figure for comparing attribution
+        methods: the class score as the top-ranked 5 %, 10 %, ... of ROIs are lesioned, and the curve's area.
+
+        ranking: a [len(graphs), n] array or tensor, or a list of per-graph [n_g] vectors -- any per-ROI map, such as
+        occlusion()'s delta or a row-reduced saliency().  Per graph the nodes are sorted by it (a stable sort, ties to
+        the lower index; order "descending" removes the highest-ranked first, "ascending" the lowest first -- read
+        backwards, the insertion curve) and point k lesions the first min(n - 1, floor(fractions[k] n)) of them
+        (gnm/lesion.py masks_from_ranking).  fractions: numbers in [0, 1], default 0, 0.05, ..., 0.95.
+
+        Returns (scores, area): scores [len(graphs), K] for an int `cls` and [len(cls), len(graphs), K] for a
+        sequence, float32 on the device -- lesion()'s `lesioned` on those sets, bitwise -- and area [len(graphs)] /
+        [len(cls), len(graphs)], fp64 numpy: the trapezoid rule over the realised fractions count / n divided by their
+        span (gnm/lesion.py curve_area), the mean score along the curve.  A faithful map gives a descending curve that
+        falls fast: a small area.  A non-finite ranking value, a fraction outside [0, 1], an empty fraction list and a
+        ranking of the wrong length raise ValueError; otherwise as lesion()."""
+        self._interpret_args("deletion_curve", graphs, cls, batch_size)
+        fr = default_fractions() if fractions is None else np.asarray(fractions, dtype=np.float64).reshape(-1)
+        if fr.shape[0] == 0:
+            raise ValueError("deletion_curve: empty list of fractions")
+        if torch.is_tensor(ranking):
+            ranking = ranking.detach().cpu().numpy()
+        elif not isinstance(ranking, np.ndarray):
+            ranking = [r.detach().cpu().numpy() if torch.is_tensor(r) else np.asarray(r) for r in ranking]
+        if len(ranking) != len(graphs):
+            raise ValueError("deletion_curve: %d rankings for %d graphs" % (len(ranking), len(graphs)))
+        masks, counts = masks_from_ranking(ranking, fr, order)
+        _, _, scores = self.lesion(graphs, cls, masks, batch_size=batch_size, return_scores=True)
+        realised = np.stack([c / float(len(g.g)) for c, g in zip(counts, graphs)])       # [G, K]
+        return scores, curve_area(scores.cpu().numpy(), realised)
 
     def integrated_gradients(self, graphs, cls, steps=32, baseline=None, method="midpoint", batch_size=8,
                              return_scores=False):

@@ -407,6 +407,42 @@ int gnm_occlusion(const uint32_t* adj_bits, const int64_t* b_bits_off, const int
                   const int* classes_host, int n_classes, int average, int self_loop, int graph_avg, float bn_eps,
                   const long long* table, const float* eps, float* scratch, float* out, long long ldo, void* stream);
 
+/* ---- Eval-mode virtual lesions of ROI sets (csrc/lesion.hip) ---------------------------------------------------------
+ * out[ci * ldo + q] = the eval-mode class score c_logit[classes_host[ci]] of virtual graph q = (source graph vgraph[q],
+ * removed set D_q): gnm_occlusion's contract with the node v replaced by a set, 0 <= |D| <= n - 1 -- the nodes of D,
+ * their feature rows and their edges in both directions removed, the readout over kept = n - |D| nodes (graph
+ * "average": the fp32 1 / kept), neighbour "average" by the reduced graph's own degree (0 / 0 -> NaN for a kept row whose
+ * neighbours are all in D under learned eps, as the reference computes it on the explicit copy), self loops kept.
+ *
+ * gnm_lesion_pack: removed [V, ld] uint8 on the DEVICE (non-zero = removed; columns >= n of a row are ignored) ->
+ * masks [V][mstride] (virtual graph q's KEEP mask in the first 2 hw words of its row, hw the half-row words of ITS
+ * graph's bit adjacency, in that layout: column v is bit ((v >> 4) & 3) * 8 + (v & 7) of word ((v >> 3) & 1) * hw +
+ * (v >> 6); bits at columns >= n and the other words are zero) and kept [V] int32 = n - |D|.  mstride: 8 for n_max <= 256,
+ * else 16 (or 16 always).  node_off: the [B + 1] node offsets of the source graphs.  BAD_ARG: ld < n_max, mstride too
+ * small or > 16, a NULL array; UNSUPPORTED: n_max outside 1..416.
+ *
+ * gnm_lesion: vrow_off [V] int64 = the first row of virtual graph q in the activation arrays = sum of n over the virtual
+ * graphs before it; rows = that sum over all of them.  kept: gnm_lesion_pack's DEVICE counts; kept_host: the same counts
+ * read back to the HOST and vn_host [V]: the HOST node counts n of the virtual graphs' source graphs -- a virtual graph
+ * with kept outside 1..n is rejected before anything is launched.  XW: [N, H] = X W0^T of the SOURCE graphs (the first
+ * Linear of layer 0 WITHOUT its bias, gnm_linear_fwd): layer 0 multiplies the masked adjacency by its rows, so any input
+ * width F0 is taken.  table / eps: as gnm_eval_layers (the same DEVICE parameter table).  scratch:
+ * gnm_lesion_scratch_floats(rows, V, n_max, H, L) = 2 rows H + L V ceil(n_max / 32) H floats (0 for a negative argument).
+ * L launches over (virtual graph, 32-row block) and one finish launch per 8 classes.
+ * Return codes as gnm_occlusion, nothing launched on any of them: GNM_ERR_UNSUPPORTED for H not in {32, 64, 128}, m
+ * outside 1..3, L outside 1..16, C > 256, n_max < 2 or > 416; GNM_ERR_BAD_ARG for a class outside [0, C), n_classes < 1,
+ * ldo < V, rows < V, ldxw < H, a NULL array, mstride too small or > 16, a kept count outside 1..n.  Every sum has a fixed
+ * order and no atomics are used: bitwise reproducible, and a virtual graph's result does not depend on the others. */
+long long gnm_lesion_scratch_floats(long long rows, long long V, int n_max, int H, int L);
+int gnm_lesion_pack(const uint8_t* removed, long long ld, const int32_t* vgraph, const int32_t* node_off, int B, int n_max,
+                    long long V, int mstride, uint32_t* masks, int32_t* kept, void* stream);
+int gnm_lesion(const uint32_t* adj_bits, const int64_t* b_bits_off, const int32_t* node_off, const int32_t* vgraph,
+               const int64_t* vrow_off, const uint32_t* masks, int mstride, const int32_t* kept, const int32_t* kept_host,
+               const int32_t* vn_host, int B, int n_max, long long V, long long rows, const float* XW, int ldxw, int H,
+               int L, int m, int C, const int* classes_host, int n_classes, int average, int self_loop, int graph_avg,
+               float bn_eps, const long long* table, const float* eps, float* scratch, float* out, long long ldo,
+               void* stream);
+
 /* ---- Eval-mode integrated gradients (csrc/intgrad.hip over csrc/saliency.hip's layer launches) ----------------------
  * attr[node_off[g] + r, :] = (X - x')[g, r, :] * sum_k w_k d score[cls] / d X (x' + alpha_k (X_g - x'))[r, :] for every
  * graph g of a batch, x' the baseline (zeros, or one [n_base, F0] block every graph shares), (alpha_k, w_k), k < K, a
