@@ -52,7 +52,6 @@ __global__ void __launch_bounds__(256) gnm_eval_layer_kernel(const ElArgs p) {
     const int W = (n + 31) >> 5;
     if (rb >= W) return;                          // (also an empty graph: no rows, no readout share)
     const int H = p.H, Fin = p.Fin;
-    const int ksteps = (n + 15) >> 4;
     rb_lut_init(lut, tid);
     RbMlp M;
     rb_mlp_prefetch<0>(M, aff, p.table, p.l, p.m, p.bn_eps, H, Fin, tid, wave, i, h);
@@ -73,27 +72,8 @@ __global__ void __launch_bounds__(256) gnm_eval_layer_kernel(const ElArgs p) {
         const int vr = min(rb * 32 + row, n - 1);
         deg = (float)(rp[vr + 1] - rp[vr] + p.self_loop);
     }
-    {
-        const int ct = wave % NCA, kh = wave / NCA, KS = 4 / NCA;
-        rb_stage_bits(bitsw, p.adj_bits + p.b_bits_off[b], rb, i, h, rb_half_words(W), tid);
-        const unsigned xbytes = (unsigned)(((size_t)(n - 1) * p.ldin + Fin) * 4);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.Hin) + (size_t)row0 * p.ldin, 0, (int)xbytes, 0x00020000);
-        const int c = 32 * ct + i;
-        const unsigned xvo = c < Fin ? (unsigned)((8 * h * p.ldin + c) * 4) : 0x80000000u;     // (a column past Fin reads zero: past any buffer, and no wrap with the row offset)
-        const int xrow = p.ldin * 4;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        __syncthreads();                                          // the table
-        auto request = [&](float (&d)[8], int s) {                // rows past n: offsets past the descriptor, zeros
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xvo, (16 * s + j) * xrow, 0));
-        };
-        rb_bits_product(acc, request, kh, KS, ksteps, lut, bitsw, tid);
-        // accumulator (r, lane): input column 32 ct + (r & 3) + 8 (r >> 2) + 4 h, output row i
-        rb_acc_to_part_rows(part, wave, i, h, acc);
-    }
+    rb_stage_bits(bitsw, p.adj_bits + p.b_bits_off[b], rb, i, h, rb_half_words(W), tid);
+    rb_rows_product(part, lut, bitsw, p.Hin + (size_t)row0 * p.ldin, p.ldin, n, Fin, NCA, tid, wave, i, h);
     __syncthreads();
     {
         const int KP = (Fin + 15) & ~15;                          // the first Linear's contraction width (zero padded)
@@ -102,10 +82,7 @@ __global__ void __launch_bounds__(256) gnm_eval_layer_kernel(const ElArgs p) {
         for (int c = c8; c < NCA * 32; c += 8) {
             float v = 0.f;
             for (int k = 0; k < KS; ++k) v += part[(c >> 5) + NCA * k][row][c & 31];
-            const float hin = T1[row * kRbTS + c];
-            if (p.self_loop) v += hin;
-            if (p.average) v /= deg;                              // 0 / 0 -> NaN as in the reference
-            if (!p.self_loop) v += selfw * hin;
+            v = rb_pool_combine<false>(v, T1[row * kRbTS + c], deg, selfw, p.self_loop, p.average);
             if (c < KP) T0[row * kRbTS + c] = (vrow && c < Fin) ? v : 0.f;
         }
     }

@@ -1,12 +1,17 @@
 // The building blocks of the eval-mode kernels whose workgroup (4 waves, 256 threads) owns one 32-row block of a graph
-// (evallayer.hip, occlusion.hip, saliency.hip, edgesal.hip):
+// (evallayer.hip, occlusion.hip, lesion.hip, saliency.hip, edgesal.hip; aggm.hip and evalfwd.hip take single pieces):
 //   * the product of the block's adjacency BITS with rows of activations read from global memory (rb_bits_product and
 //     what feeds it): the activations are the A operand, "eight consecutive rows of one column per lane", split in
 //     registers into three exact bf16 planes; the bits are the B operand, expanded through a 16-entry LDS table;
 //   * the two ways an accumulator goes to the part[wave] tiles in LDS where the waves' partial tiles meet;
+//   * the aggregation stage of the forward layer kernels (rb_rows_product: the product over a graph's rows, to the part
+//     tiles) and the pooling rule of their combine pass (rb_pool_combine);
 //   * the forward MLP on the 32 x F tile in LDS (rb_mlp_*): folded BatchNorm, six-term split Linears (gnm_split.h);
-//   * the readout sum and the classifier head of the finish kernels.
-// Each kernel keeps what is its own: how it addresses the rows it multiplies, its combine pass, its epilogue.
+//   * the readout sum and the classifier head of the finish kernels;
+//   * the layer arguments that the virtual-graph forwards share (RbVirtualArgs; their finish body and host driver,
+//     gnm_virtual_forward, are defined in occlusion.hip and used by lesion.hip too).
+// Each kernel keeps what is its own: how it stages the bits, which rows it multiplies, its epilogue.  saliency.hip
+// addresses its rows differently (the row offset in the vector offset) and keeps its own product call.
 #pragma once
 #include "gnm_split.h"
 
@@ -16,7 +21,7 @@ static constexpr int kRbTS = kRbMaxH + 4;         // row stride of the LDS tiles
 static constexpr int kRbLinWords = 7;             // the parameter table of evalfwd.hip (gnm_eval_table_words)
 
 // words per HALF row of the bit adjacency of a graph of W row blocks (layout: aggm.hip gnm_adj_bits_build)
-__device__ __forceinline__ int rb_half_words(int W) { return (((W + 1) >> 1) + 3) & ~3; }
+__host__ __device__ __forceinline__ int rb_half_words(int W) { return (((W + 1) >> 1) + 3) & ~3; }
 
 // lut[128]: nibble e -> bf16 (bit 0, bit 1, bit 2, bit 3) as two words.  Visible after the next barrier.
 __device__ __forceinline__ void rb_lut_init(char* lut, int tid) {
@@ -115,6 +120,48 @@ __device__ __forceinline__ void rb_acc_to_part_rows(float (*part)[32][33], int w
 __device__ __forceinline__ void rb_acc_to_part_cols(float (*part)[32][33], int wave, int i, int h, const f32x16& acc) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) part[wave][(r & 3) + 8 * (r >> 2) + 4 * h][i] = acc[r];
+}
+
+// The aggregation stage of a forward layer kernel: this wave's share of (the block's bits, already staged in bitsw by
+// rb_stage_bits / rb_stage_bits_masked) x (rows 0 .. n - 1 of `base`, row stride ld floats, columns 0 .. width - 1; NCA
+// column tiles, the rest of the waves split k) -> part[wave].  Holds the barrier after which the lut, the staged bits
+// and whatever else the caller wrote to LDS before the call are visible.
+__device__ __forceinline__ void rb_rows_product(float (*part)[32][33], const char* lut, const unsigned (*bitsw)[256],
+                                                const float* base, int ld, int n, int width, int NCA, int tid, int wave,
+                                                int i, int h) {
+    const int ksteps = (n + 15) >> 4;
+    const int ct = wave % NCA, kh = wave / NCA, KS = 4 / NCA;
+    const unsigned xbytes = (unsigned)(((size_t)(n - 1) * ld + width) * 4);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)xbytes, 0x00020000);
+    const int c = 32 * ct + i;
+    const unsigned xvo = c < width ? (unsigned)((8 * h * ld + c) * 4) : 0x80000000u;   // (a column past width reads zero: past any buffer, and no wrap with the row offset)
+    const int xrow = ld * 4;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    __syncthreads();
+    auto request = [&](float (&d)[8], int s) {                    // rows past n: offsets past the descriptor, zeros
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xvo, (16 * s + j) * xrow, 0));
+    };
+    rb_bits_product(acc, request, kh, KS, ksteps, lut, bitsw, tid);
+    // accumulator (r, lane): input column 32 ct + (r & 3) + 8 (r >> 2) + 4 h, output row i
+    rb_acc_to_part_rows(part, wave, i, h, acc);
+}
+
+// The pooling rule of the combine pass for one element: t the neighbour sum (the waves' partial tiles added), hin the
+// row's own input, selfw = 1 + eps[layer] (graphcnn.py:161).  ZERO_DEG: a row with no neighbour left gives 0 / 0 -> NaN
+// as the reference does on the explicit copy, whatever its partial sum held.  SELF_IN_T: t already holds the self term
+// (occlusion's layer 0, whose S = (A + I) XW).
+template <bool ZERO_DEG, bool SELF_IN_T = false>
+__device__ __forceinline__ float rb_pool_combine(float t, float hin, float deg, float selfw, int self_loop, int average) {
+    if (self_loop && !SELF_IN_T) t += hin;
+    if (average) {
+        if (ZERO_DEG && deg == 0.f) t = 0.f;
+        t /= deg;                                                 // 0 / 0 -> NaN as in the reference
+    }
+    if (!self_loop) t += selfw * hin;
+    return t;
 }
 
 // ---- the forward MLP of a GIN layer on the 32 x F tile -------------------------------------------------------------
@@ -241,3 +288,23 @@ __device__ __forceinline__ float rb_readout_head(const float* gfl, const long lo
     if (lane < L) acc += reinterpret_cast<const float*>(th[2 * lane + 1])[cls];
     return wave_sum(acc);
 }
+
+// ---- the virtual-graph forwards (occlusion.hip, lesion.hip) -----------------------------------------------------------
+// What their layer kernels' arguments share (OcArgs and LsArgs derive from it).  The entry fills what holds for the whole
+// call; gnm_virtual_forward (occlusion.hip) checks that and fills the rest per layer.
+struct RbVirtualArgs {
+    const uint32_t* adj_bits; const int64_t* b_bits_off; const int32_t* node_off;
+    const int32_t* vgraph;                        // [V]: source graph of virtual graph q
+    const int64_t* vrow_off;                      // first activation row of a graph's virtual graphs / of a virtual graph
+    const float* XW; int ldxw;                    // layer 0: X W0^T of the SOURCE graphs, [N, H]
+    int L, m, H;
+    int average, self_loop;
+    float bn_eps;
+    const float* eps;                             // [L] on the device, or null (learn_eps False)
+    const long long* table;
+    // per layer:
+    const float* Hin;                             // layers >= 1: [rows, H]
+    int V, wmax, l;
+    float* Hout;                                  // [rows, H]
+    float* rpart;                                 // [V][wmax][H]: this layer's readout shares
+};

@@ -24,22 +24,8 @@
 #include "gnm_rowblock.h"
 #include <string.h>
 
-static constexpr int kLsMaxClasses = 8;           // classes per finish launch
-
-struct LsArgs {
-    const uint32_t* adj_bits; const int64_t* b_bits_off; const int32_t* node_off;
-    const int32_t* vgraph;                        // [V]: source graph of virtual graph q
-    const int64_t* vrow_off;                      // [V]: first activation row of virtual graph q (sum of n before q)
+struct LsArgs : RbVirtualArgs {                   // vrow_off [V]: sum of n before virtual graph q
     const uint32_t* masks; int mstride;           // [V][mstride]: the keep masks
-    const float* XW; int ldxw;                    // layer 0: X W0^T of the SOURCE graphs, [N, H]
-    const float* Hin;                             // layers >= 1: [rows, H]
-    int V, wmax, L, m, l, H;
-    int average, self_loop;
-    float bn_eps;
-    const float* eps;                             // [L] on the device, or null (learn_eps False)
-    const long long* table;
-    float* Hout;                                  // [rows, H]
-    float* rpart;                                 // [V][wmax][H]: this layer's readout shares
 };
 
 // FIRST: layer 0 (the masked product over the source graph's XW; the first Linear ran on the source graphs, its bias
@@ -103,29 +89,10 @@ __global__ void __launch_bounds__(256) gnm_lesion_layer_kernel(const LsArgs p) {
     const float* Hg = FIRST ? p.XW + (size_t)node0 * p.ldxw : p.Hin + row0 * H;
     const int ld = FIRST ? p.ldxw : H;
     for (int c = c8; c < H; c += 8) T1[row * kRbTS + c] = Hg[(size_t)vr * ld + c];           // the self term, parked
-    {
-        const int ksteps = (n + 15) >> 4;
-        const int ct = wave % NCA, kh = wave / NCA, KS = 4 / NCA;
-        const int pc = rb_stage_bits_masked(bitsw, gbits, mask, rb, i, h, HPW, tid);
-        const int pcr = pc + __shfl_xor(pc, 32, 64);              // both halves of row 32 rb + i
-        if (wave == 0 && h == 0) degs[i] = pcr;
-        const unsigned xbytes = (unsigned)(((size_t)(n - 1) * ld + H) * 4);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Hg), 0, (int)xbytes, 0x00020000);
-        const int c = 32 * ct + i;
-        const unsigned xvo = (unsigned)((8 * h * ld + c) * 4);
-        const int xrow = ld * 4;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        __syncthreads();                                          // the table, the vectors, the degrees
-        auto request = [&](float (&d)[8], int s) {                // rows past n: offsets past the descriptor, zeros
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xvo, (16 * s + j) * xrow, 0));
-        };
-        rb_bits_product(acc, request, kh, KS, ksteps, lut, bitsw, tid);
-        // accumulator (r, lane): input column 32 ct + (r & 3) + 8 (r >> 2) + 4 h, output row i
-        rb_acc_to_part_rows(part, wave, i, h, acc);
-    }
+    const int pc = rb_stage_bits_masked(bitsw, gbits, mask, rb, i, h, HPW, tid);
+    const int pcr = pc + __shfl_xor(pc, 32, 64);                  // both halves of row 32 rb + i
+    if (wave == 0 && h == 0) degs[i] = pcr;
+    rb_rows_product(part, lut, bitsw, Hg, ld, n, H, NCA, tid, wave, i, h);      // (its barrier: the degrees too)
     __syncthreads();
     {
         const int KS = 4 / NCA;
@@ -135,13 +102,7 @@ __global__ void __launch_bounds__(256) gnm_lesion_layer_kernel(const LsArgs p) {
         for (int c = c8; c < H; c += 8) {
             float t = 0.f;
             for (int k = 0; k < KS; ++k) t += part[(c >> 5) + NCA * k][row][c & 31];
-            const float hin = T1[row * kRbTS + c];
-            if (p.self_loop) t += hin;
-            if (p.average) {
-                if (deg == 0.f) t = 0.f;                          // no neighbour left: 0 / 0 -> NaN as in the reference
-                t /= deg;
-            }
-            if (!p.self_loop) t += selfw * hin;
+            t = rb_pool_combine<true>(t, T1[row * kRbTS + c], deg, selfw, p.self_loop, p.average);
             if (!keep) t = 0.f;
             if (FIRST) {                                          // the first Linear's bias and folded BatchNorm
                 t = gnm_relu((t + aff[0][0][c]) * aff[0][1][c] + aff[0][2][c]);
@@ -156,36 +117,6 @@ __global__ void __launch_bounds__(256) gnm_lesion_layer_kernel(const LsArgs p) {
     rb_mlp_forward<FIRST ? 1 : 0>(M, aff, part, Tin, Tout, p.m, H, H, wave, i, h, row, c8, last_rule);
     // the block's share of the lesioned graph's readout
     rb_readout_share(Tin, H, tid, rdst);
-}
-
-struct LsFinArgs {
-    const int32_t* node_off; const int32_t* vgraph; const int32_t* kept;
-    const float* rpart;                           // [L][V][wmax][H]
-    const long long* table;
-    int V, wmax, L, m, H, graph_avg;
-    int ncls; int cls[kLsMaxClasses];
-    float* out; long long ldo;                    // out[ci * ldo + q]
-};
-
-__global__ void __launch_bounds__(256) gnm_lesion_finish_kernel(const LsFinArgs p) {
-    extern __shared__ float gfl[];                // [L * H]
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const int b = p.vgraph[q];
-    const int n = p.node_off[b + 1] - p.node_off[b];
-    const int W = (n + 31) >> 5, H = p.H, LH = p.L * p.H;
-    const float scale = p.graph_avg ? 1.0f / (float)p.kept[q] : 1.f;   // the reference stores 1./len(graph.g) as fp32
-    for (int e = tid; e < LH; e += 256) {
-        const int l = e / H, c = e - l * H;
-        float s = rb_readout_sum(p.rpart, p.V, q, p.wmax, W, H, l, c);
-        if (p.graph_avg) s *= scale;
-        gfl[e] = s;
-    }
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6;   // a wave per class
-    for (int ci = wave; ci < p.ncls; ci += 4) {
-        const float acc = rb_readout_head(gfl, p.table, p.L, p.m, H, p.cls[ci], lane);
-        if (lane == 0) p.out[(size_t)ci * p.ldo + q] = acc;
-    }
 }
 
 // The keep masks and kept counts of V virtual graphs from removed [V, ld] (uint8, non-zero = removed; entries at columns
@@ -222,14 +153,22 @@ __global__ void __launch_bounds__(256) gnm_lesion_pack_kernel(const uint8_t* rem
     }
 }
 
-// Floats of scratch gnm_lesion needs: two [rows, H] activation arrays (rows = sum of n_g over the virtual graphs) and
-// the readout shares [L][V][ceil(n_max / 32)][H].
+// occlusion.hip: the scratch size, and the checks, layer loop and finish launches both forwards share
+extern "C" long long gnm_occlusion_scratch_floats(long long rows, long long V, int n_max, int H, int L);
+extern "C" int gnm_virtual_forward(RbVirtualArgs* a, int B, int n_max, long long V, long long rows, int C,
+                                   const int* classes_host, int n_classes, int graph_avg, const int32_t* kept,
+                                   float* scratch, float* out, long long ldo, hipStream_t s,
+                                   bool (*own_ok)(const void* ctx),
+                                   void (*launch)(const void* ctx, bool first, unsigned grid, hipStream_t s),
+                                   const void* ctx);
+
+// Floats of scratch gnm_lesion needs: gnm_occlusion's with rows = sum of n_g over the virtual graphs.
 extern "C" long long gnm_lesion_scratch_floats(long long rows, long long V, int n_max, int H, int L) {
-    if (rows < 0 || V < 0 || n_max < 0 || H < 0 || L < 0) return 0;
-    return 2 * rows * H + (long long)L * V * ((n_max + 31) / 32) * H;
+    return gnm_occlusion_scratch_floats(rows, V, n_max, H, L);
 }
 
-static int ls_half_words(int W) { return (((W + 1) >> 1) + 3) & ~3; }
+// Words of a keep mask that serves graphs of up to n_max nodes: both half rows (the mstride of the two entries below)
+extern "C" int gnm_lesion_mask_words(int n_max) { return 2 * rb_half_words((n_max + 31) / 32); }
 
 // masks [V][mstride] and kept [V] of the virtual graphs from removed [V, ld] (see include/gnm_hip.h)
 extern "C" int gnm_lesion_pack(const uint8_t* removed, long long ld, const int32_t* vgraph, const int32_t* node_off,
@@ -237,7 +176,7 @@ extern "C" int gnm_lesion_pack(const uint8_t* removed, long long ld, const int32
                                void* stream) {
     if (B == 0 || V == 0) return GNM_OK;
     if (n_max < 1 || n_max > kRbMaxN) return GNM_ERR_UNSUPPORTED;
-    if (B < 0 || V < 0 || ld < n_max || mstride < 2 * ls_half_words((n_max + 31) / 32) || mstride > 16) return GNM_ERR_BAD_ARG;
+    if (B < 0 || V < 0 || ld < n_max || mstride < gnm_lesion_mask_words(n_max) || mstride > 16) return GNM_ERR_BAD_ARG;
     if (!removed || !vgraph || !node_off || !masks || !kept) return GNM_ERR_BAD_ARG;
     if ((V + 15) / 16 >= (1LL << 31)) return GNM_ERR_UNSUPPORTED;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -255,55 +194,30 @@ extern "C" int gnm_lesion(const uint32_t* adj_bits, const int64_t* b_bits_off, c
                           const int* classes_host, int n_classes, int average, int self_loop, int graph_avg,
                           float bn_eps, const long long* table, const float* eps, float* scratch, float* out,
                           long long ldo, void* stream) {
-    if (B == 0 || V == 0) return GNM_OK;
-    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || C < 1 || C > 256 || n_max < 2 ||
-        n_max > kRbMaxN)
-        return GNM_ERR_UNSUPPORTED;
-    if (B < 0 || V < 0 || rows < V || ldo < V || !classes_host || n_classes < 1) return GNM_ERR_BAD_ARG;
-    for (int k = 0; k < n_classes; ++k)
-        if (classes_host[k] < 0 || classes_host[k] >= C) return GNM_ERR_BAD_ARG;
-    if (!adj_bits || !b_bits_off || !node_off || !vgraph || !vrow_off || !masks || !kept || !kept_host || !vn_host ||
-        !XW || !table || !scratch || !out)
-        return GNM_ERR_BAD_ARG;
-    if (ldxw < H) return GNM_ERR_BAD_ARG;
-    const int wmax = (n_max + 31) / 32;
-    if (mstride < 2 * ls_half_words(wmax) || mstride > 16) return GNM_ERR_BAD_ARG;
-    for (long long q = 0; q < V; ++q)               // a virtual graph keeps 1 .. n of its nodes (gnm_lesion_pack's counts)
-        if (vn_host[q] < 1 || vn_host[q] > n_max || kept_host[q] < 1 || kept_host[q] > vn_host[q]) return GNM_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(adj_bits) & 15) return GNM_ERR_UNSUPPORTED;
-    if (V * wmax >= (1LL << 31)) return GNM_ERR_UNSUPPORTED;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* act[2] = {scratch, scratch + (size_t)rows * H};
-    float* rpart = scratch + 2 * (size_t)rows * H;
-    for (int l = 0; l < L; ++l) {
-        LsArgs a;
-        memset(&a, 0, sizeof(a));
-        a.adj_bits = adj_bits; a.b_bits_off = b_bits_off; a.node_off = node_off;
-        a.vgraph = vgraph; a.vrow_off = vrow_off; a.masks = masks; a.mstride = mstride;
-        a.XW = XW; a.ldxw = ldxw;
-        a.Hin = act[(l + 1) & 1];
-        a.V = (int)V; a.wmax = wmax; a.L = L; a.m = m; a.l = l; a.H = H;
-        a.average = average; a.self_loop = self_loop; a.bn_eps = bn_eps;
-        a.eps = eps;
-        a.table = table;
-        a.Hout = act[l & 1];
-        a.rpart = rpart + (size_t)l * V * wmax * H;
-        if (l == 0)
-            hipLaunchKernelGGL(gnm_lesion_layer_kernel<true>, dim3((unsigned)(V * wmax)), dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL(gnm_lesion_layer_kernel<false>, dim3((unsigned)(V * wmax)), dim3(256), 0, s, a);
-        GNM_CHECK_LAUNCH();
-    }
-    for (int c0 = 0; c0 < n_classes; c0 += kLsMaxClasses) {
-        LsFinArgs f;
-        memset(&f, 0, sizeof(f));
-        f.node_off = node_off; f.vgraph = vgraph; f.kept = kept; f.rpart = rpart; f.table = table;
-        f.V = (int)V; f.wmax = wmax; f.L = L; f.m = m; f.H = H; f.graph_avg = graph_avg;
-        f.ncls = n_classes - c0 < kLsMaxClasses ? n_classes - c0 : kLsMaxClasses;
-        for (int k = 0; k < f.ncls; ++k) f.cls[k] = classes_host[c0 + k];
-        f.out = out + (size_t)c0 * ldo; f.ldo = ldo;
-        hipLaunchKernelGGL(gnm_lesion_finish_kernel, dim3((unsigned)V), dim3(256), (size_t)L * H * 4, s, f);
-        GNM_CHECK_LAUNCH();
-    }
-    return GNM_OK;
+    struct Call { LsArgs a; const int32_t *kept, *kept_host, *vn_host; int n_max; long long V; } k;
+    memset(&k, 0, sizeof(k));
+    LsArgs& a = k.a;
+    a.adj_bits = adj_bits; a.b_bits_off = b_bits_off; a.node_off = node_off; a.vgraph = vgraph; a.vrow_off = vrow_off;
+    a.XW = XW; a.ldxw = ldxw; a.L = L; a.m = m; a.H = H;
+    a.average = average; a.self_loop = self_loop; a.bn_eps = bn_eps; a.eps = eps; a.table = table;
+    a.masks = masks; a.mstride = mstride;
+    k.kept = kept; k.kept_host = kept_host; k.vn_host = vn_host; k.n_max = n_max; k.V = V;
+    return gnm_virtual_forward(
+        &a, B, n_max, V, rows, C, classes_host, n_classes, graph_avg, kept, scratch, out, ldo,
+        reinterpret_cast<hipStream_t>(stream),
+        [](const void* ctx) {
+            const Call& k = *static_cast<const Call*>(ctx);
+            if (!k.a.masks || !k.kept || !k.kept_host || !k.vn_host) return false;
+            if (k.a.mstride < gnm_lesion_mask_words(k.n_max) || k.a.mstride > 16) return false;
+            for (long long q = 0; q < k.V; ++q)     // a virtual graph keeps 1 .. n of its nodes (gnm_lesion_pack's counts)
+                if (k.vn_host[q] < 1 || k.vn_host[q] > k.n_max || k.kept_host[q] < 1 || k.kept_host[q] > k.vn_host[q])
+                    return false;
+            return true;
+        },
+        [](const void* ctx, bool first, unsigned grid, hipStream_t s) {
+            const LsArgs& a = static_cast<const Call*>(ctx)->a;
+            if (first) hipLaunchKernelGGL(gnm_lesion_layer_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(gnm_lesion_layer_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+        },
+        &k);
 }

@@ -25,21 +25,9 @@
 
 static constexpr int kOcMaxClasses = 8;           // classes per finish launch
 
-struct OcArgs {
-    const uint32_t* adj_bits; const int64_t* b_bits_off; const int32_t* node_off;
+struct OcArgs : RbVirtualArgs {                   // vrow_off [B]: sum of n^2 before graph g
     const int32_t* rowptr; const int64_t* b_rp_off;
-    const int32_t* vgraph;                        // [V]: source graph of virtual graph q
-    const int64_t* vrow_off;                      // [B]: first activation row of graph g's virtual graphs (sum of n^2 before g)
-    const float* XW; int ldxw;                    // layer 0: X W0^T and (A + I) X W0^T of the SOURCE graphs, [N, H]
-    const float* S; int lds;
-    const float* Hin;                             // layers >= 1: [rows, H]
-    int V, wmax, L, m, l, H;
-    int average, self_loop;
-    float bn_eps;
-    const float* eps;                             // [L] on the device, or null (learn_eps False)
-    const long long* table;
-    float* Hout;                                  // [rows, H]
-    float* rpart;                                 // [V][wmax][H]: this layer's readout shares
+    const float* S; int lds;                      // layer 0: (A + I) X W0^T of the SOURCE graphs, [N, H]
 };
 
 // FIRST: layer 0 (the first pre-activation from XW and S, see the file header; no product with the adjacency and no
@@ -78,7 +66,7 @@ __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p
     const int vr = min(rb * 32 + row, n - 1);
     const bool vrow = rb * 32 + row < n;
     const bool keep = vrow && vr != v;
-    const unsigned arv = (gbits[(size_t)vr * (2 * HPW) + ((v >> 3) & 1) * HPW + (v >> 6)] >> ((((v >> 4) & 3) << 3) + (v & 7))) & 1u;
+    const unsigned arv = rb_row_bit(gbits + (size_t)vr * (2 * HPW), HPW, v);
     float deg = 1.f;
     if (p.average) {
         const int32_t* rp = p.rowptr + p.b_rp_off[b];
@@ -104,11 +92,7 @@ __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p
             float t = sr[c];
             if (!p.self_loop && p.average) t -= xw;
             if (arv) t -= xwv[c];
-            if (p.average) {
-                if (deg == 0.f) t = 0.f;                          // no neighbour left: 0 / 0 -> NaN as in the reference
-                t /= deg;
-            }
-            if (!p.self_loop) t += p.average ? selfw * xw : eps_l * xw;
+            t = rb_pool_combine<true, true>(t, xw, deg, p.average ? selfw : eps_l, p.self_loop, p.average);
             float y = gnm_relu((t + aff[0][0][c]) * aff[0][1][c] + aff[0][2][c]);
             if (last) y = last_rule(c, y);
             T1[row * kRbTS + c] = y;
@@ -118,43 +102,16 @@ __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p
         const int NCA = NCT;
         const float* Hg = p.Hin + row0 * H;
         for (int c = c8; c < H; c += 8) T1[row * kRbTS + c] = Hg[(size_t)vr * H + c];       // the self term, parked
-        {
-            const int ksteps = (n + 15) >> 4;
-            const int ct = wave % NCA, kh = wave / NCA, KS = 4 / NCA;
-            rb_stage_bits(bitsw, gbits, rb, i, h, HPW, tid);
-            const unsigned xbytes = (unsigned)(((size_t)(n - 1) * H + H) * 4);
-            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Hg), 0, (int)xbytes, 0x00020000);
-            const int c = 32 * ct + i;
-            const unsigned xvo = (unsigned)((8 * h * H + c) * 4);
-            const int xrow = H * 4;
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            __syncthreads();                                      // the table
-            auto request = [&](float (&d)[8], int s) {            // rows past n: offsets past the descriptor, zeros
-#pragma unroll
-                for (int j = 0; j < 8; ++j) d[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xvo, (16 * s + j) * xrow, 0));
-            };
-            rb_bits_product(acc, request, kh, KS, ksteps, lut, bitsw, tid);
-            // accumulator (r, lane): input column 32 ct + (r & 3) + 8 (r >> 2) + 4 h, output row i
-            rb_acc_to_part_rows(part, wave, i, h, acc);
-        }
+        rb_stage_bits(bitsw, gbits, rb, i, h, HPW, tid);
+        rb_rows_product(part, lut, bitsw, Hg, H, n, H, NCA, tid, wave, i, h);
         __syncthreads();
-        {
-            const int KS = 4 / NCA;
-            const float selfw = 1.f + eps_l;                      // graphcnn.py:161 (1 + eps[layer]) h
-            for (int c = c8; c < H; c += 8) {
-                float t = 0.f;
-                for (int k = 0; k < KS; ++k) t += part[(c >> 5) + NCA * k][row][c & 31];
-                const float hin = T1[row * kRbTS + c];
-                if (p.self_loop) t += hin;
-                if (p.average) {
-                    if (deg == 0.f) t = 0.f;                      // no neighbour left: 0 / 0 -> NaN as in the reference
-                    t /= deg;
-                }
-                if (!p.self_loop) t += selfw * hin;
-                T0[row * kRbTS + c] = vrow ? t : 0.f;
-            }
+        const int KS = 4 / NCA;
+        const float selfw = 1.f + eps_l;                          // graphcnn.py:161 (1 + eps[layer]) h
+        for (int c = c8; c < H; c += 8) {
+            float t = 0.f;
+            for (int k = 0; k < KS; ++k) t += part[(c >> 5) + NCA * k][row][c & 31];
+            t = rb_pool_combine<true>(t, T1[row * kRbTS + c], deg, selfw, p.self_loop, p.average);
+            T0[row * kRbTS + c] = vrow ? t : 0.f;
         }
     }
     // ---- B. the MLP (layer 0: from its second Linear) ----------------------------------------------------------
@@ -165,8 +122,10 @@ __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p
     rb_readout_share(Tin, H, tid, p.rpart + ((size_t)q * p.wmax + rb) * H);
 }
 
+// The finish launch of both virtual-graph forwards (gnm_virtual_forward)
 struct OcFinArgs {
     const int32_t* node_off; const int32_t* vgraph;
+    const int32_t* kept;                          // [V]: nodes left in virtual graph q, or null: n - 1
     const float* rpart;                           // [L][V][wmax][H]
     const long long* table;
     int V, wmax, L, m, H, graph_avg;
@@ -174,16 +133,18 @@ struct OcFinArgs {
     float* out; long long ldo;                    // out[ci * ldo + q]
 };
 
-__global__ void __launch_bounds__(256) gnm_occlusion_finish_kernel(const OcFinArgs p) {
+__device__ __forceinline__ void oc_finish(const OcFinArgs& p) {
     extern __shared__ float gfl[];                // [L * H]
     const int q = blockIdx.x, tid = threadIdx.x;
     const int b = p.vgraph[q];
     const int n = p.node_off[b + 1] - p.node_off[b];
     const int W = (n + 31) >> 5, H = p.H, LH = p.L * p.H;
+    // the reference stores 1./len(graph.g) as fp32 (graphcnn.py:123,130)
+    const float scale = p.graph_avg ? 1.0f / (float)(p.kept ? p.kept[q] : n - 1) : 1.f;
     for (int e = tid; e < LH; e += 256) {
         const int l = e / H, c = e - l * H;
         float s = rb_readout_sum(p.rpart, p.V, q, p.wmax, W, H, l, c);
-        if (p.graph_avg) s *= 1.0f / (float)(n - 1);    // the reference stores 1./len(graph.g) as fp32 (graphcnn.py:123,130)
+        if (p.graph_avg) s *= scale;
         gfl[e] = s;
     }
     __syncthreads();
@@ -193,12 +154,64 @@ __global__ void __launch_bounds__(256) gnm_occlusion_finish_kernel(const OcFinAr
         if (lane == 0) p.out[(size_t)ci * p.ldo + q] = acc;
     }
 }
+// One finish under the name of either forward (profiles and the code-object tests know a forward's launches by its name)
+__global__ void __launch_bounds__(256) gnm_occlusion_finish_kernel(const OcFinArgs p) { oc_finish(p); }
+__global__ void __launch_bounds__(256) gnm_lesion_finish_kernel(const OcFinArgs p) { oc_finish(p); }
 
-// Floats of scratch gnm_occlusion needs: two [rows, H] activation arrays (rows = sum of n_g^2 over the batch) and the
-// readout shares [L][V][ceil(n_max / 32)][H] (V = N virtual graphs).
+// Floats of scratch gnm_occlusion / gnm_lesion need: two [rows, H] activation arrays (rows = sum of n_g^2 over the batch
+// / of n_g over the virtual graphs) and the readout shares [L][V][ceil(n_max / 32)][H] (occlusion: V = N virtual graphs).
 extern "C" long long gnm_occlusion_scratch_floats(long long rows, long long V, int n_max, int H, int L) {
     if (rows < 0 || V < 0 || n_max < 0 || H < 0 || L < 0) return 0;
     return 2 * rows * H + (long long)L * V * ((n_max + 31) / 32) * H;
+}
+
+// What gnm_occlusion and gnm_lesion share on the host: the checks of the arguments both have (`a` holds the call's own,
+// filled by the entry; own_ok(ctx): the entry's further BAD_ARG conditions, asked where those return), the split of
+// `scratch`, the ping-pong layer launches through launch(ctx, first, grid, stream) -- `a` is part of *ctx -- and the
+// finish launches, 8 classes at a time.  kept: OcFinArgs'.
+extern "C" __attribute__((visibility("hidden"))) int gnm_virtual_forward(
+    RbVirtualArgs* a, int B, int n_max, long long V, long long rows, int C, const int* classes_host, int n_classes,
+    int graph_avg, const int32_t* kept, float* scratch, float* out, long long ldo, hipStream_t s,
+    bool (*own_ok)(const void* ctx), void (*launch)(const void* ctx, bool first, unsigned grid, hipStream_t s),
+    const void* ctx) {
+    const int H = a->H, L = a->L, m = a->m;
+    if (B == 0 || V == 0) return GNM_OK;
+    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || C < 1 || C > 256 || n_max < 2 ||
+        n_max > kRbMaxN)
+        return GNM_ERR_UNSUPPORTED;
+    if (B < 0 || V < 0 || rows < V || ldo < V || !classes_host || n_classes < 1) return GNM_ERR_BAD_ARG;
+    for (int k = 0; k < n_classes; ++k)
+        if (classes_host[k] < 0 || classes_host[k] >= C) return GNM_ERR_BAD_ARG;
+    if (!a->adj_bits || !a->b_bits_off || !a->node_off || !a->vgraph || !a->vrow_off || !a->XW || !a->table || !scratch ||
+        !out || a->ldxw < H || !own_ok(ctx))
+        return GNM_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(a->adj_bits) & 15) return GNM_ERR_UNSUPPORTED;
+    const int wmax = (n_max + 31) / 32;
+    if (V * wmax >= (1LL << 31)) return GNM_ERR_UNSUPPORTED;
+    float* act[2] = {scratch, scratch + (size_t)rows * H};
+    float* rpart = scratch + 2 * (size_t)rows * H;
+    a->V = (int)V; a->wmax = wmax;
+    for (int l = 0; l < L; ++l) {
+        a->l = l;
+        a->Hin = act[(l + 1) & 1];
+        a->Hout = act[l & 1];
+        a->rpart = rpart + (size_t)l * V * wmax * H;
+        launch(ctx, l == 0, (unsigned)(V * wmax), s);
+        GNM_CHECK_LAUNCH();
+    }
+    for (int c0 = 0; c0 < n_classes; c0 += kOcMaxClasses) {
+        OcFinArgs f;
+        memset(&f, 0, sizeof(f));
+        f.node_off = a->node_off; f.vgraph = a->vgraph; f.kept = kept; f.rpart = rpart; f.table = a->table;
+        f.V = (int)V; f.wmax = wmax; f.L = L; f.m = m; f.H = H; f.graph_avg = graph_avg;
+        f.ncls = n_classes - c0 < kOcMaxClasses ? n_classes - c0 : kOcMaxClasses;
+        for (int k = 0; k < f.ncls; ++k) f.cls[k] = classes_host[c0 + k];
+        f.out = out + (size_t)c0 * ldo; f.ldo = ldo;
+        hipLaunchKernelGGL(kept ? gnm_lesion_finish_kernel : gnm_occlusion_finish_kernel, dim3((unsigned)V), dim3(256),
+                           (size_t)L * H * 4, s, f);
+        GNM_CHECK_LAUNCH();
+    }
+    return GNM_OK;
 }
 
 // The class scores of every node-deleted copy of every graph of a batch (see the file header and include/gnm_hip.h).
@@ -209,52 +222,23 @@ extern "C" int gnm_occlusion(const uint32_t* adj_bits, const int64_t* b_bits_off
                              int n_classes, int average, int self_loop, int graph_avg, float bn_eps,
                              const long long* table, const float* eps, float* scratch, float* out, long long ldo,
                              void* stream) {
-    if (B == 0 || V == 0) return GNM_OK;
-    if (!(H == 32 || H == 64 || H == 128) || m < 1 || m > 3 || L < 1 || L > 16 || C < 1 || C > 256 || n_max < 2 ||
-        n_max > kRbMaxN)
-        return GNM_ERR_UNSUPPORTED;
-    if (B < 0 || V < 0 || rows < V || ldo < V || !classes_host || n_classes < 1) return GNM_ERR_BAD_ARG;
-    for (int k = 0; k < n_classes; ++k)
-        if (classes_host[k] < 0 || classes_host[k] >= C) return GNM_ERR_BAD_ARG;
-    if (!adj_bits || !b_bits_off || !node_off || !rowptr || !b_rp_off || !vgraph || !vrow_off || !XW || !S || !table ||
-        !scratch || !out)
-        return GNM_ERR_BAD_ARG;
-    if (ldxw < H || lds < H) return GNM_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(adj_bits) & 15) return GNM_ERR_UNSUPPORTED;
-    const int wmax = (n_max + 31) / 32;
-    if (V * wmax >= (1LL << 31)) return GNM_ERR_UNSUPPORTED;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* act[2] = {scratch, scratch + (size_t)rows * H};
-    float* rpart = scratch + 2 * (size_t)rows * H;
-    for (int l = 0; l < L; ++l) {
-        OcArgs a;
-        memset(&a, 0, sizeof(a));
-        a.adj_bits = adj_bits; a.b_bits_off = b_bits_off; a.node_off = node_off; a.rowptr = rowptr; a.b_rp_off = b_rp_off;
-        a.vgraph = vgraph; a.vrow_off = vrow_off;
-        a.XW = XW; a.ldxw = ldxw; a.S = S; a.lds = lds;
-        a.Hin = act[(l + 1) & 1];
-        a.V = (int)V; a.wmax = wmax; a.L = L; a.m = m; a.l = l; a.H = H;
-        a.average = average; a.self_loop = self_loop; a.bn_eps = bn_eps;
-        a.eps = eps;
-        a.table = table;
-        a.Hout = act[l & 1];
-        a.rpart = rpart + (size_t)l * V * wmax * H;
-        if (l == 0)
-            hipLaunchKernelGGL(gnm_occlusion_layer_kernel<true>, dim3((unsigned)(V * wmax)), dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL(gnm_occlusion_layer_kernel<false>, dim3((unsigned)(V * wmax)), dim3(256), 0, s, a);
-        GNM_CHECK_LAUNCH();
-    }
-    for (int c0 = 0; c0 < n_classes; c0 += kOcMaxClasses) {
-        OcFinArgs f;
-        memset(&f, 0, sizeof(f));
-        f.node_off = node_off; f.vgraph = vgraph; f.rpart = rpart; f.table = table;
-        f.V = (int)V; f.wmax = wmax; f.L = L; f.m = m; f.H = H; f.graph_avg = graph_avg;
-        f.ncls = n_classes - c0 < kOcMaxClasses ? n_classes - c0 : kOcMaxClasses;
-        for (int k = 0; k < f.ncls; ++k) f.cls[k] = classes_host[c0 + k];
-        f.out = out + (size_t)c0 * ldo; f.ldo = ldo;
-        hipLaunchKernelGGL(gnm_occlusion_finish_kernel, dim3((unsigned)V), dim3(256), (size_t)L * H * 4, s, f);
-        GNM_CHECK_LAUNCH();
-    }
-    return GNM_OK;
+    OcArgs a;
+    memset(&a, 0, sizeof(a));
+    a.adj_bits = adj_bits; a.b_bits_off = b_bits_off; a.node_off = node_off; a.vgraph = vgraph; a.vrow_off = vrow_off;
+    a.XW = XW; a.ldxw = ldxw; a.L = L; a.m = m; a.H = H;
+    a.average = average; a.self_loop = self_loop; a.bn_eps = bn_eps; a.eps = eps; a.table = table;
+    a.rowptr = rowptr; a.b_rp_off = b_rp_off; a.S = S; a.lds = lds;
+    return gnm_virtual_forward(
+        &a, B, n_max, V, rows, C, classes_host, n_classes, graph_avg, nullptr, scratch, out, ldo,
+        reinterpret_cast<hipStream_t>(stream),
+        [](const void* ctx) {
+            const OcArgs& o = *static_cast<const OcArgs*>(ctx);
+            return o.rowptr && o.b_rp_off && o.S && o.lds >= o.H;
+        },
+        [](const void* ctx, bool first, unsigned grid, hipStream_t s) {
+            const OcArgs& o = *static_cast<const OcArgs*>(ctx);
+            if (first) hipLaunchKernelGGL(gnm_occlusion_layer_kernel<true>, dim3(grid), dim3(256), 0, s, o);
+            else hipLaunchKernelGGL(gnm_occlusion_layer_kernel<false>, dim3(grid), dim3(256), 0, s, o);
+        },
+        &a);
 }

@@ -87,6 +87,7 @@ SIGNATURES = {
     "gnm_occlusion": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _ll, _ll, _p, _i, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i,
                            _f, _p, _p, _p, _p, _ll, _p]),
     "gnm_lesion_scratch_floats": (_ll, [_ll, _ll, _i, _i, _i]),
+    "gnm_lesion_mask_words": (_i, [_i]),
     "gnm_lesion_pack": (_i, [_p, _ll, _p, _p, _i, _i, _ll, _i, _p, _p, _p]),
     "gnm_lesion": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _ll, _ll, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i,
                         _f, _p, _p, _p, _p, _ll, _p]),

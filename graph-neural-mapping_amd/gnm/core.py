@@ -887,6 +887,26 @@ def saliency_maps_hip(spec, batch, X, P, classes, out=None):
     return out
 
 
+def _first_linear_product(X, P, m, rows, F0, H):
+    """XW = X W0^T [rows, H] on the split-precision Linear: layer 0's first Linear without its bias, any input width"""
+    W0 = P["mlps.0.linear.weight" if m == 1 else "mlps.0.linears.0.weight"]
+    XW = torch.empty((rows, H), dtype=torch.float32, device=X.device)
+    _linear(X, W0, 0, None, XW, rows, F0, H, None, None)
+    return XW
+
+
+def _runs_within(count, floats_of, budget_bytes):
+    """Items 0 .. count - 1 in order as runs (i0, i1): each the longest run from i0, of at least one item, that stops
+    before the first item that would take 4 * floats_of(i0, i1) bytes (items i0 .. i1 - 1) over budget_bytes"""
+    i0 = 0
+    while i0 < count:
+        i1 = i0 + 1
+        while i1 < count and 4 * floats_of(i0, i1 + 1) <= budget_bytes:
+            i1 += 1
+        yield i0, i1
+        i0 = i1
+
+
 def edge_saliency_hip(spec, batch, X, P, classes, out=None):
     """The connectivity saliency d score[:, c] / d A[u, v] of a whole batch for every c in `classes` and every node
     pair (u, v) of each graph, A the dense Adj_block of graphcnn.py:84-106 (see include/gnm_hip.h gnm_edge_saliency):
@@ -898,9 +918,7 @@ def edge_saliency_hip(spec, batch, X, P, classes, out=None):
     with _saliency_launch(spec, batch, X, P, lambda N, H: lib.gnm_edge_saliency_scratch_floats(N, H, L)) as k:
         nm = int(batch.n_max)
         out = _out_array(out, (len(classes), k.N, nm), k.dev)
-        W0 = P["mlps.0.linear.weight" if spec.m == 1 else "mlps.0.linears.0.weight"]
-        Y = torch.empty((k.N, k.H), dtype=torch.float32, device=k.dev)
-        _linear(k.X, W0, 0, None, Y, k.N, k.F0, k.H, None, None)          # layer 0's term at width H: <dZ0, X W0^T>
+        Y = _first_linear_product(k.X, P, spec.m, k.N, k.F0, k.H)         # layer 0's term at width H: <dZ0, X W0^T>
         for ci, c in enumerate(classes):
             with _timed("edge_saliency_hip", B=k.B, N=k.N, H=k.H):
                 check(lib.gnm_edge_saliency(*batch.bits_ptrs(), batch.t_bits_off.data_ptr(), batch.node_off.data_ptr(),
@@ -941,32 +959,27 @@ def occlusion_hip(spec, batch, X, P, classes, out=None):
     cls = (C.c_int * len(classes))(*[int(c) for c in classes])
     offs = np.asarray(batch.node_off_host, dtype=np.int64)
     ns = np.diff(offs)
+    sq = np.concatenate([[0], np.cumsum(ns * ns)])          # activation rows before graph g: sum of n^2
     with torch.no_grad(), _stream_scope(dev):
         table = _eval_table(spec, P, dev)
         f32 = dict(dtype=torch.float32, device=dev)
-        W0 = P["mlps.0.linear.weight" if m == 1 else "mlps.0.linears.0.weight"]
-        XW, S = torch.empty((N, H), **f32), torch.empty((N, H), **f32)
-        _linear(X, W0, 0, None, XW, N, F0, H, None, None)
+        XW, S = _first_linear_product(X, P, m, N, F0, H), torch.empty((N, H), **f32)
         check(lib.gnm_agg(*batch.csr_ptrs(), *batch.deg_ptrs(), batch.node_off.data_ptr(), B, batch.n_max,
                           batch.nnz_max, XW.data_ptr(), XW.stride(0), S.data_ptr(), S.stride(0), H, None, 0, 1, 0,
                           None, 0, None, _stream()), "gnm_agg")
-        g0 = 0
-        while g0 < B:
-            g1, rows, need = g0, 0, 0
-            while g1 < B:                   # the longest run of graphs whose scratch fits the budget (at least one)
-                r = rows + int(ns[g1]) ** 2
-                k = int(lib.gnm_occlusion_scratch_floats(r, int(offs[g1 + 1] - offs[g0]), int(ns[g0:g1 + 1].max()), H, L))
-                if g1 > g0 and 4 * k > OCCLUSION_SCRATCH_BYTES:
-                    break
-                g1, rows, need = g1 + 1, r, k
+
+        def floats(g0, g1):
+            return int(lib.gnm_occlusion_scratch_floats(int(sq[g1] - sq[g0]), int(offs[g1] - offs[g0]),
+                                                        int(ns[g0:g1].max()), H, L))
+        for g0, g1 in _runs_within(B, floats, OCCLUSION_SCRATCH_BYTES):
             nc = ns[g0:g1]
-            V, r0 = int(nc.sum()), int(offs[g0])
+            V, r0, rows = int(nc.sum()), int(offs[g0]), int(sq[g1] - sq[g0])
             up = batch.arena._upload
             node_off = up(torch.as_tensor((offs[g0:g1 + 1] - offs[g0]).astype(np.int32)))
-            vrow_off = up(torch.as_tensor(np.concatenate([[0], np.cumsum(nc * nc)[:-1]]).astype(np.int64)))
+            vrow_off = up(torch.as_tensor(sq[g0:g1] - sq[g0]))
             vgraph = up(torch.as_tensor(np.repeat(np.arange(g1 - g0, dtype=np.int32), nc)))
             bits_off, rp_off = batch.bits_off[g0:g1], batch.rp_off[g0:g1]
-            scratch = torch.empty(need, **f32)
+            scratch = torch.empty(floats(g0, g1), **f32)
             dst = out[:, r0:r0 + V]
             with _timed("occlusion_hip", B=g1 - g0, N=V, H=H, L=L):
                 check(lib.gnm_occlusion(batch.arena.bits.buf.data_ptr(), bits_off.data_ptr(), node_off.data_ptr(),
@@ -976,7 +989,6 @@ def occlusion_hip(spec, batch, X, P, classes, out=None):
                                         int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS,
                                         table.data_ptr(), d.eps, scratch.data_ptr(), dst.data_ptr(), out.stride(0),
                                         _stream()), "gnm_occlusion")
-            g0 = g1
     return out
 
 
@@ -1014,27 +1026,21 @@ def lesion_hip(spec, batch, X, P, classes, removed, vgraph, out=None):
     cls = (C.c_int * len(classes))(*[int(c) for c in classes])
     offs = np.asarray(batch.node_off_host, dtype=np.int64)
     vn = np.diff(offs)[vgraph].astype(np.int32)             # node count of each virtual graph
+    cum = np.concatenate([[0], np.cumsum(vn, dtype=np.int64)])      # activation rows before virtual graph q
     with torch.no_grad(), _stream_scope(dev):
         table = _eval_table(spec, P, dev)
         f32 = dict(dtype=torch.float32, device=dev)
-        W0 = P["mlps.0.linear.weight" if m == 1 else "mlps.0.linears.0.weight"]
-        XW = torch.empty((N, H), **f32)
-        _linear(X, W0, 0, None, XW, N, F0, H, None, None)
+        XW = _first_linear_product(X, P, m, N, F0, H)
         up = batch.arena._upload
-        q0 = 0
-        while q0 < Vt:
-            q1, rows, need = q0, 0, 0
-            while q1 < Vt:                  # the longest run of virtual graphs whose scratch fits the budget (at least one)
-                r = rows + int(vn[q1])
-                k = int(lib.gnm_lesion_scratch_floats(r, q1 + 1 - q0, int(vn[q0:q1 + 1].max()), H, L))
-                if q1 > q0 and 4 * k > LESION_SCRATCH_BYTES:
-                    break
-                q1, rows, need = q1 + 1, r, k
+
+        def floats(q0, q1):
+            return int(lib.gnm_lesion_scratch_floats(int(cum[q1] - cum[q0]), q1 - q0, int(vn[q0:q1].max()), H, L))
+        for q0, q1 in _runs_within(Vt, floats, LESION_SCRATCH_BYTES):
             V, nc = q1 - q0, vn[q0:q1]
-            n_max = int(nc.max())
-            mstride = 2 * (((((n_max + 31) // 32 + 1) >> 1) + 3) & ~3)
+            n_max, rows = int(nc.max()), int(cum[q1] - cum[q0])
+            mstride = int(lib.gnm_lesion_mask_words(n_max))
             vg = up(torch.as_tensor(vgraph[q0:q1]))
-            vrow_off = up(torch.as_tensor(np.concatenate([[0], np.cumsum(nc, dtype=np.int64)[:-1]]).astype(np.int64)))
+            vrow_off = up(torch.as_tensor(cum[q0:q1] - cum[q0]))
             rem = up(torch.as_tensor(removed[q0:q1]))
             masks = torch.empty((V, mstride), dtype=torch.int32, device=dev)
             kept = torch.empty(V, dtype=torch.int32, device=dev)
@@ -1042,7 +1048,7 @@ def lesion_hip(spec, batch, X, P, classes, removed, vgraph, out=None):
                                       n_max, V, mstride, masks.data_ptr(), kept.data_ptr(), _stream()),
                   "gnm_lesion_pack")
             kept_host = kept.cpu().numpy()                  # the one read-back of the chunk
-            scratch = torch.empty(need, **f32)
+            scratch = torch.empty(floats(q0, q1), **f32)
             dst = out[:, q0:q1]
             with _timed("lesion_hip", B=B, N=V, H=H, L=L):
                 check(lib.gnm_lesion(batch.arena.bits.buf.data_ptr(), batch.bits_off.data_ptr(),
@@ -1052,7 +1058,6 @@ def lesion_hip(spec, batch, X, P, classes, removed, vgraph, out=None):
                                      int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS,
                                      table.data_ptr(), d.eps, scratch.data_ptr(), dst.data_ptr(), out.stride(0),
                                      _stream()), "gnm_lesion")
-            q0 = q1
     return out
 
 
@@ -1091,15 +1096,13 @@ def integrated_gradients_hip(spec, batch, X, P, classes, alphas, weights, baseli
     arena = batch.arena
     with torch.no_grad(), _stream_scope(dev):
         f32 = dict(dtype=torch.float32, device=dev)
-        lin0 = "mlps.0.linear" if m == 1 else "mlps.0.linears.0"
-        W0, b0 = P[lin0 + ".weight"], P[lin0 + ".bias"].contiguous()
+        b0 = P["mlps.0.linear.bias" if m == 1 else "mlps.0.linears.0.bias"].contiguous()
         al, wt = arena._upload(torch.as_tensor(a32)), arena._upload(torch.as_tensor(w32))
         eps_ptr = d.eps
 
         def pooled_product(src, rows):
             """pool(src) W0^T as pool(src W0^T): src is [rows, F0] (the batch's features, or ONE graph's baseline)"""
-            XW = torch.empty((rows, H), **f32)
-            _linear(src, W0, 0, None, XW, rows, F0, H, None, None)
+            XW = _first_linear_product(src, P, m, rows, F0, H)
             if rows != N:
                 XW = XW.repeat(B, 1)
             Pz = torch.empty((N, H), **f32)
@@ -1114,11 +1117,8 @@ def integrated_gradients_hip(spec, batch, X, P, classes, alphas, weights, baseli
                 raise GnmError("the baseline must be [n, %d] with n the node count of every graph" % F0)
             Qz = pooled_product(baseline, int(baseline.shape[0]))
         gh = batch.gids.cpu().numpy()
-        g0 = 0
-        while g0 < B:
-            g1 = g0 + 1                     # the longest run of graphs whose arrays fit the budget (at least one)
-            while g1 < B and 4 * _intgrad_floats(int(offs[g1 + 1] - offs[g0]), H, L, m, K) <= INTGRAD_SCRATCH_BYTES:
-                g1 += 1
+        for g0, g1 in _runs_within(B, lambda g0, g1: _intgrad_floats(int(offs[g1] - offs[g0]), H, L, m, K),
+                                   INTGRAD_SCRATCH_BYTES):
             r0, rows = int(offs[g0]), int(offs[g1] - offs[g0])
             sub = batch if (g0, g1) == (0, B) else arena.batch_from_gids(gh[g0:g1])
             vb = arena.batch_from_gids(np.repeat(gh[g0:g1], K))
@@ -1143,7 +1143,6 @@ def integrated_gradients_hip(spec, batch, X, P, classes, alphas, weights, baseli
                         int(baseline.shape[0]) if baseline is not None else 0, dst.data_ptr(), out.stride(1),
                         _stream()), "gnm_integrated_gradients")
             del saved, table, scratch, z0
-            g0 = g1
     return out
 
 

@@ -547,17 +547,23 @@ class GIN_InfoMaxReg(nn.Module):
             delta = [[base[ci, j] - o for j, o in enumerate(row)] for ci, row in enumerate(occ)]
         return (delta, base, occ) if return_scores else delta
 
+    def _virtual_prologue(self, method, decline, batch, P, classes):
+        """What occlusion() and lesion() do first with a batch: its features on the device, ValueError(`method` ...) if
+        decline(...) declines it, and its base scores [len(classes), B] from the ordinary eval forward"""
+        X = batch.arena.features(batch).detach()
+        launch_device(X, P["eps"])                          # no CPU fallback: GnmError before any shape question
+        why = decline(self._spec, batch, X, P)
+        if why is not None:
+            raise ValueError("%s does not cover this batch: %s" % (method, why))
+        with torch.no_grad():
+            c_logit, _, _ = self._run(batch, X, np.arange(batch.B, dtype=np.int64), want_disc=False)
+        return X, c_logit.detach()[:, classes].t().contiguous()
+
     def _occlusion_batch(self, chunk, batch, P, classes, dst, bases):
         """occlusion() of one batch: the occluded scores [len(classes), N] (dst when given); the batch's base scores
         [len(classes), B] are appended to `bases`"""
-        X = batch.arena.features(batch).detach()
-        launch_device(X, P["eps"])                          # no CPU fallback: GnmError before any shape question
-        why = occlusion_decline(self._spec, batch, X, P)
-        if why is not None:
-            raise ValueError("occlusion does not cover this batch: %s" % why)
-        with torch.no_grad():
-            c_logit, _, _ = self._run(batch, X, np.arange(batch.B, dtype=np.int64), want_disc=False)
-        bases.append(c_logit.detach()[:, classes].t().contiguous())
+        X, base = self._virtual_prologue("occlusion", occlusion_decline, batch, P, classes)
+        bases.append(base)
         bad = _nonfinite_graphs(batch, X)
         if bad is None:
             return occlusion_hip(self._spec, batch, X, P, classes, out=dst)
@@ -662,14 +668,7 @@ class GIN_InfoMaxReg(nn.Module):
 
     def _lesion_batch(self, chunk, batch, P, classes, sets):
         """lesion() of one batch: (base [len(classes), B], lesioned [len(classes), sum of S_g], graph by graph)"""
-        X = batch.arena.features(batch).detach()
-        launch_device(X, P["eps"])                          # no CPU fallback: GnmError before any shape question
-        why = lesion_decline(self._spec, batch, X, P)
-        if why is not None:
-            raise ValueError("lesion does not cover this batch: %s" % why)
-        with torch.no_grad():
-            c_logit, _, _ = self._run(batch, X, np.arange(batch.B, dtype=np.int64), want_disc=False)
-        base = c_logit.detach()[:, classes].t().contiguous()
+        X, base = self._virtual_prologue("lesion", lesion_decline, batch, P, classes)
 
         def run(b, Xb, which):
             """the virtual graphs of graphs `which` of the chunk, which are the graphs of batch b, in order"""

@@ -417,9 +417,10 @@ int gnm_occlusion(const uint32_t* adj_bits, const int64_t* b_bits_off, const int
  * gnm_lesion_pack: removed [V, ld] uint8 on the DEVICE (non-zero = removed; columns >= n of a row are ignored) ->
  * masks [V][mstride] (virtual graph q's KEEP mask in the first 2 hw words of its row, hw the half-row words of ITS
  * graph's bit adjacency, in that layout: column v is bit ((v >> 4) & 3) * 8 + (v & 7) of word ((v >> 3) & 1) * hw +
- * (v >> 6); bits at columns >= n and the other words are zero) and kept [V] int32 = n - |D|.  mstride: 8 for n_max <= 256,
- * else 16 (or 16 always).  node_off: the [B + 1] node offsets of the source graphs.  BAD_ARG: ld < n_max, mstride too
- * small or > 16, a NULL array; UNSUPPORTED: n_max outside 1..416.
+ * (v >> 6); bits at columns >= n and the other words are zero) and kept [V] int32 = n - |D|.  mstride: at least
+ * gnm_lesion_mask_words(n_max) = 2 hw of a graph of n_max nodes (8 for n_max <= 256, else 16), at most 16.  node_off:
+ * the [B + 1] node offsets of the source graphs.  BAD_ARG: ld < n_max, mstride too small or > 16, a NULL array;
+ * UNSUPPORTED: n_max outside 1..416.
  *
  * gnm_lesion: vrow_off [V] int64 = the first row of virtual graph q in the activation arrays = sum of n over the virtual
  * graphs before it; rows = that sum over all of them.  kept: gnm_lesion_pack's DEVICE counts; kept_host: the same counts
@@ -434,6 +435,7 @@ int gnm_occlusion(const uint32_t* adj_bits, const int64_t* b_bits_off, const int
  * ldo < V, rows < V, ldxw < H, a NULL array, mstride too small or > 16, a kept count outside 1..n.  Every sum has a fixed
  * order and no atomics are used: bitwise reproducible, and a virtual graph's result does not depend on the others. */
 long long gnm_lesion_scratch_floats(long long rows, long long V, int n_max, int H, int L);
+int gnm_lesion_mask_words(int n_max);
 int gnm_lesion_pack(const uint8_t* removed, long long ld, const int32_t* vgraph, const int32_t* node_off, int B, int n_max,
                     long long V, int mstride, uint32_t* masks, int32_t* kept, void* stream);
 int gnm_lesion(const uint32_t* adj_bits, const int64_t* b_bits_off, const int32_t* node_off, const int32_t* vgraph,

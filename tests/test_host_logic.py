@@ -573,6 +573,37 @@ def test_linear_backward_routing_table(monkeypatch, K, H, pro, below, need_dA):
                         assert (got.job.ws, got.job.dW, got.job.db, got.job.H, got.job.K) == tuple(got.job), what
 
 
+@pytest.mark.parametrize("sizes, budget", [
+    ([3, 3, 3, 3], 4 * 6),              # exact fits: two items each
+    ([3, 3, 3, 3], 4 * 6 - 1),          # one byte short of two
+    ([2, 9, 2, 2, 1], 4 * 5),           # a single item over the budget, alone in its run
+    ([5, 1, 7, 1, 1, 1], 1),            # a budget of 1: every item alone
+    ([1, 2, 3, 4, 5, 6, 7], 4 * 10),
+    ([4], 0), ([], 100),
+])
+def test_runs_within_against_brute_force(sizes, budget):
+    """core._runs_within (the chunking of occlusion_hip, lesion_hip and integrated_gradients_hip): in order, no run
+    empty, each run the longest that fits -- against the definition, tried run by run"""
+    from gnm import core
+    asked = []
+
+    def floats_of(i0, i1):
+        assert 0 <= i0 < i1 <= len(sizes)                       # never an empty or an out-of-range run
+        asked.append((i0, i1))
+        return sum(sizes[i0:i1]) + (i1 - i0) * max(sizes[i0:i1])      # not additive, as the scratch sizes are not
+
+    want, i0 = [], 0
+    while i0 < len(sizes):
+        fits = [i1 for i1 in range(i0 + 1, len(sizes) + 1) if 4 * floats_of(i0, i1) <= budget]
+        i1 = i0 + 1
+        while i1 + 1 in fits:           # stops BEFORE the first item that goes over, whatever fits behind it
+            i1 += 1
+        want.append((i0, i1))
+        i0 = i1
+    assert list(core._runs_within(len(sizes), floats_of, budget)) == want
+    assert [i for a, b in want for i in range(a, b)] == list(range(len(sizes)))     # every item once, in order
+
+
 def test_gradient_collector():
     """core._Grads, where the backward's kernels and torch ops leave the parameter gradients: with a sink
     (GinSpec.grad_sink) they go into its tensors and autograd gets None for every parameter; without one they are

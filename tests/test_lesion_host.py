@@ -15,7 +15,7 @@ from helpers import GOLDEN_DIR, RTOL, rel_err
 from test_occlusion_host import DeletedGraph, _G, _cpu_model, delete_node
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("gnm_lesion", "gnm_lesion_pack", "gnm_lesion_scratch_floats")
+NEW = ("gnm_lesion", "gnm_lesion_pack", "gnm_lesion_scratch_floats", "gnm_lesion_mask_words")
 LES_CASES = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN_DIR, "lesion", "les_*.npz")))
 
 

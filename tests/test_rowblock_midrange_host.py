@@ -101,6 +101,15 @@ def test_graphs_and_sets_are_what_the_table_says(n):
     assert len({(c.npool, c.gpool, c.eps) for c in T.cases(n) if any(T.ig_declined(c, g) for g in T.graphs_of(c))}) <= 1
 
 
+def test_the_library_and_the_table_agree_on_the_mask_width():
+    """gnm_lesion_mask_words (the one place the library and gnm/core.py take a keep mask's width from) against this
+    suite's independent copy of the half-row layout, at every node count the row-block kernels take"""
+    from gnm._cabi import lib
+    for n in range(1, 417):
+        assert lib.gnm_lesion_mask_words(n) == 2 * T.half_words(n), n
+    assert lib.gnm_lesion_mask_words(256) == 8 and lib.gnm_lesion_mask_words(257) == 16
+
+
 def _check_lesion_conditions(what, want_nan, base64, base32, les64, les32, names=None):
     assert np.isfinite(base64).all() and np.isfinite(base32).all(), what
     nan64 = np.isnan(les64)
