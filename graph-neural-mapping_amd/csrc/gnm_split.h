@@ -1,6 +1,8 @@
 // The project's "fp32-faithful on the bf16 pipe" arithmetic, in one place: the exact three-plane bf16 split of an fp32
 // value and the six-term matrix product built on it (v_mfma_f32_32x32x16_bf16, 16x the rate of the fp32 instruction).
-// Every kernel that multiplies this way includes this header; a change here changes all of them together.
+// Every kernel that multiplies this way -- the eval kernels through gnm_tile_step, the training kernels of linear.hip
+// through gnm_mma6 / gnm_mma6_planes -- includes this header and issues the product nowhere else; a change here changes
+// all of them together.
 #pragma once
 #include "gnm_common.h"
 
@@ -49,6 +51,19 @@ __device__ __forceinline__ void gnm_mma6(f32x16& acc, const gnm_bf16x8 a1, const
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
+}
+
+// The same with the B operand taken from a three-plane LDS image (plane stride ew entries), entry e
+__device__ __forceinline__ void gnm_mma6_planes(f32x16& acc, const gnm_bf16x8 a1, const gnm_bf16x8 a2, const gnm_bf16x8 a3,
+                                                const gnm_u32x4* Wp, int ew, int e) {
+    gnm_mma6(acc, a1, a2, a3, __builtin_bit_cast(gnm_bf16x8, Wp[e]), __builtin_bit_cast(gnm_bf16x8, Wp[ew + e]),
+             __builtin_bit_cast(gnm_bf16x8, Wp[2 * ew + e]));
+}
+// Eight consecutive floats at a 16-byte aligned address (an LDS tile row) -> the three operands
+__device__ __forceinline__ void gnm_load_split8(const float* src, gnm_bf16x8& a1, gnm_bf16x8& a2, gnm_bf16x8& a3) {
+    const float4 v0 = *reinterpret_cast<const float4*>(src), v1 = *reinterpret_cast<const float4*>(src + 4);
+    const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    gnm_split8(f, a1, a2, a3);
 }
 
 // The A operand of step s from a 32-row LDS tile T of row stride ts floats: row i of the lane, k = 16 s + 8 h + 0..7

@@ -101,6 +101,43 @@ static inline LinArgs lin_args(const float* X, int ldx, const float* W, int ldw,
     return a;
 }
 
+// W -> its three bf16 plane images in LDS (plane stride ew entries), for the six-term product with a 32-row tile whose
+// lanes hold k = KGS kg + 8 m + 0..7.  Entry (m, c, lane = 32 kg + n) is the eight contraction indices
+// kk = 8 m + KGS kg + 0..7 of output column nn = 32 c + n (CT column tiles): W[kk][nn] in the k-major form (dgrad: the
+// contraction runs over W's rows), W[nn][kk] in the forward form.  CLIP: W's columns at or past wcols read as zero.
+template <int CT, int KGS, bool KMAJOR, bool CLIP>
+__device__ __forceinline__ void lin_stage_planes(gnm_u32x4* Wp, int ew, const float* W, int ldw, int wcols, int tid, int nt) {
+    for (int e = tid; e < ew; e += nt) {
+        const int n = e & 31, kg = (e >> 5) & 1, c = (e >> 6) % CT, m = e / (64 * CT);
+        const int kk = 8 * m + KGS * kg, nn = 32 * c + n;
+        float f[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (KMAJOR) f[j] = (!CLIP || nn < wcols) ? W[(size_t)(kk + j) * ldw + nn] : 0.f;
+            else f[j] = (!CLIP || kk + j < wcols) ? W[(size_t)nn * ldw + kk + j] : 0.f;
+        }
+        gnm_u32x4 p1, p2, p3;
+        gnm_split8(f, p1, p2, p3);
+        Wp[e] = p1; Wp[ew + e] = p2; Wp[2 * ew + e] = p3;
+    }
+}
+
+// dacc += dZ W on the bf16 pipe for H = 64: lane (i, h) takes row i, k = 32 h + 8 m + 0..7 of the wave's dZ image Xs (row
+// stride xs floats) and multiplies by the k-major plane image Wp of lin_stage_planes.  (The caller zeroes dacc: with
+// the zeroing in here the narrow fused kernel's tile loop came out scheduled differently.)
+template <int KT, int HP>
+__device__ __forceinline__ void lin_dgrad_split(f32x16 (&dacc)[KT], const float* Xs, int xs, const gnm_u32x4* Wp, int i, int h,
+                                                int lane) {
+    static_assert(HP == 64, "four steps of 16 over H = 64: a lane half starts at k = 32 h");
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        gnm_bf16x8 x1, x2, x3;
+        gnm_load_split8(Xs + i * xs + 32 * h + 8 * m, x1, x2, x3);
+#pragma unroll
+        for (int c = 0; c < KT; ++c) gnm_mma6_planes(dacc[c], x1, x2, x3, Wp, 4 * KT * 64, (m * KT + c) * 64 + lane);
+    }
+}
+
 template <int KC, int HT>
 __global__ void __launch_bounds__(256) gnm_lin_kernel(const LinArgs p) {
     constexpr int HP = HT * 32;          // padded output width
@@ -896,17 +933,7 @@ __global__ void __launch_bounds__(kSplitWaves * 64) gnm_lin_split_kernel(const L
                              a3 = __builtin_bit_cast(gnm_bf16x8, A3m);
 #endif
 #pragma unroll
-            for (int c = 0; c < HT; ++c) {
-                const int e = (m * HT + c) * 64 + lane;
-                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wp[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wp[E + e]),
-                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wp[2 * E + e]);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc[c], 0, 0, 0);      // small terms first
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[c], 0, 0, 0);
-            }
+            for (int c = 0; c < HT; ++c) gnm_mma6_planes(acc[c], a1, a2, a3, Wp, E, (m * HT + c) * 64 + lane);
         }
         GNM_SSTAMP(5 + 6 * min(tk, 9))
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1155,17 +1182,7 @@ __global__ void __launch_bounds__(kSplit128Waves * 64) gnm_lin_split128_kernel(c
             const gnm_bf16x8 a1 = __builtin_bit_cast(gnm_bf16x8, A1), a2 = __builtin_bit_cast(gnm_bf16x8, A2),
                              a3 = __builtin_bit_cast(gnm_bf16x8, A3);
 #pragma unroll
-            for (int c = 0; c < HT; ++c) {
-                const int e = ((step * HT + c) << 6) + lane;
-                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wp[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wp[E + e]),
-                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wp[2 * E + e]);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc[c], 0, 0, 0);      // small terms first
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[c], 0, 0, 0);
-            }
+            for (int c = 0; c < HT; ++c) gnm_mma6_planes(acc[c], a1, a2, a3, Wp, E, ((step * HT + c) << 6) + lane);
             if (step < 7) {       // the next slice into the image (behind this step's reads, in order)
                 *reinterpret_cast<gnm_u32x4*>(xs_w) = ring0[(step + 1) % D];
                 *reinterpret_cast<gnm_u32x4*>(xs_w + 16 * XS) = ring1[(step + 1) % D];
@@ -1285,10 +1302,14 @@ static bool lin_no_split() {
     return v;
 }
 
-static size_t lin_lds_bytes(int K, int KC, int HT) {
+// gnm_lin_kernel's LDS: the zero-padded weight image and the four waves' input chunks ...
+static size_t lin_image_bytes(int K, int KC, int HT) {
     const int KP = ((K + KC - 1) / KC) * KC;
-    size_t b = (size_t)KP * HT * 32 * 4 + (size_t)4 * 32 * (KC + 4) * 4;
-    const size_t red = (size_t)4 * 2 * HT * 32 * 8;
+    return (size_t)KP * HT * 32 * 4 + (size_t)4 * 32 * (KC + 4) * 4;
+}
+// ... or the statistics combine that reuses it, whichever is larger
+static size_t lin_lds_bytes(int K, int KC, int HT) {
+    const size_t b = lin_image_bytes(K, KC, HT), red = (size_t)4 * 2 * HT * 32 * 8;
     return b > red ? b : red;
 }
 
@@ -1298,7 +1319,7 @@ static int launch_lin(const LinArgs& a0, int grid, hipStream_t s) {
     size_t lds = lin_lds_bytes(a.K, KC, HT);
     if (lds > (size_t)kLdsBudget) return GNM_ERR_UNSUPPORTED;
     // room for the output staging image (a wide first layer, K = 400 one-hot, has none: 4-byte column stores then)
-    const size_t wbytes = (size_t)(((a.K + KC - 1) / KC) * KC) * HT * 32 * 4 + (size_t)4 * 32 * (KC + 4) * 4;
+    const size_t wbytes = lin_image_bytes(a.K, KC, HT);
     const size_t obytes = (size_t)4 * 32 * (HT * 32 + 4) * 4;
     a.stage_out = wbytes + obytes <= (size_t)kLdsBudget / 2 ? 1 : 0;      // only while two workgroups still share a CU
     if (a.stage_out && wbytes + obytes > lds) lds = wbytes + obytes;
@@ -1563,7 +1584,14 @@ __global__ void __launch_bounds__(256) gnm_wgrad_fast_kernel(const WgArgs p) {
     bool kok[WJ];                 // columns past the window / K are clamped on load and zeroed by select
     float sc[WJ], sh[WJ];
 #pragma unroll
-    for (int a = 0; a < WI; ++a) { dbacc[a] = 0.f; hcol[a] = 32 * (qi * WI + a) + i; }
+    for (int a = 0; a < WI; ++a) {
+        dbacc[a] = 0.f;
+        hcol[a] = 32 * (qi * WI + a) + i;
+        // Two row quadrants of an odd number of 32-column tiles (H = 96): quadrant 1's second tile lies past H, and in the
+        // last row its loads would leave dZ.  Clamped like kcol; none of that tile's accumulators is written out below.
+        // With one quadrant the WI tiles are exactly H, and those instances keep the unclamped index.
+        if constexpr (QI > 1) hcol[a] = min(hcol[a], p.H - 1);
+    }
 #pragma unroll
     for (int b = 0; b < WJ; ++b) {
         const int kl = 32 * (qj * WJ + b) + i;
@@ -1748,25 +1776,13 @@ __global__ void __launch_bounds__(512) gnm_wgrad_split128_kernel(const WgArgs p)
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             dbs[a] += ((d[a][0] + d[a][1]) + (d[a][2] + d[a][3])) + ((d[a][4] + d[a][5]) + (d[a][6] + d[a][7]));
-            gnm_u32x4 p1, p2, p3;
-            gnm_split8(d[a], p1, p2, p3);
-            dp[a][0] = __builtin_bit_cast(gnm_bf16x8, p1); dp[a][1] = __builtin_bit_cast(gnm_bf16x8, p2);
-            dp[a][2] = __builtin_bit_cast(gnm_bf16x8, p3);
-            gnm_split8(x[a], p1, p2, p3);
-            xp[a][0] = __builtin_bit_cast(gnm_bf16x8, p1); xp[a][1] = __builtin_bit_cast(gnm_bf16x8, p2);
-            xp[a][2] = __builtin_bit_cast(gnm_bf16x8, p3);
+            gnm_split8(d[a], dp[a][0], dp[a][1], dp[a][2]);
+            gnm_split8(x[a], xp[a][0], xp[a][1], xp[a][2]);
         }
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][2], acc[a][b], 0, 0, 0);   // small terms first
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][2], xp[b][0], acc[a][b], 0, 0, 0);
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][1], xp[b][1], acc[a][b], 0, 0, 0);
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][1], acc[a][b], 0, 0, 0);
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][1], xp[b][0], acc[a][b], 0, 0, 0);
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][0], acc[a][b], 0, 0, 0);
-            }
+            for (int b = 0; b < 2; ++b) gnm_mma6(acc[a][b], dp[a][0], dp[a][1], dp[a][2], xp[b][0], xp[b][1], xp[b][2]);
     };
     // two register images: group g + 2 is requested before group g is split and multiplied
     float dA_[2][8], xA_[2][8], dB_[2][8], xB_[2][8];
@@ -1838,15 +1854,13 @@ extern "C" long long gnm_wgrad_workspace_floats(int N, int H, int K) {
 // [H x kw] window into dW (leading dimension ldw, column offset k0) and db.
 // 32 output elements per workgroup, 32 thread groups each summing every 32nd partial (so the
 // ~8 MB of partials are streamed by ~130 workgroups instead of 17), combined through LDS.
-__global__ void __launch_bounds__(1024) gnm_reduce_partials_kernel(const float* __restrict__ partial, int nblk,
-                                                                   long long stride, int H, int kw, int k0,
-                                                                   float* __restrict__ dW, int ldw,
-                                                                   float* __restrict__ db) {
-    __shared__ float red[32][32];
+// Element e of the sum over `nblk` partials, in the one summation order both reduce kernels use: thread group g
+// (32 groups of 32 lanes) sums partials g, g + 32, ... four at a time, and the groups are added in order through LDS.
+// The sum is returned to the first 32 threads of the workgroup.
+__device__ __forceinline__ float reduce_partials_element(const float* __restrict__ partial, int nblk, long long stride, int e,
+                                                         int count, float (&red)[32][32]) {
     const int tid = threadIdx.x;
-    const int grp = tid >> 5, ngrp = (int)blockDim.x >> 5;       // 32 groups of 32 lanes: group g sums partials g, g+32, ...
-    const int e = blockIdx.x * 32 + (tid & 31);
-    const int count = H * kw + H;
+    const int grp = tid >> 5, ngrp = (int)blockDim.x >> 5;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     if (e < count) {
         int b = grp;
@@ -1859,9 +1873,22 @@ __global__ void __launch_bounds__(1024) gnm_reduce_partials_kernel(const float* 
     }
     red[grp][tid & 31] = (s0 + s1) + (s2 + s3);
     __syncthreads();
-    if (tid < 32 && e < count) {
-        float s = 0.f;
+    float s = 0.f;
+    if (tid < 32 && e < count)
         for (int g = 0; g < ngrp; ++g) s += red[g][tid];
+    return s;
+}
+
+__global__ void __launch_bounds__(1024) gnm_reduce_partials_kernel(const float* __restrict__ partial, int nblk,
+                                                                   long long stride, int H, int kw, int k0,
+                                                                   float* __restrict__ dW, int ldw,
+                                                                   float* __restrict__ db) {
+    __shared__ float red[32][32];
+    const int tid = threadIdx.x;
+    const int e = blockIdx.x * 32 + (tid & 31);
+    const int count = H * kw + H;
+    const float s = reduce_partials_element(partial, nblk, stride, e, count, red);
+    if (tid < 32 && e < count) {
         if (e < H * kw) {
             const int row = e / kw, col = e - row * kw;
             dW[(size_t)row * ldw + k0 + col] = s;
@@ -1929,6 +1956,96 @@ static inline LbArgs lb_args(const float* G, int ldg, const float* mean, const f
     return a;
 }
 
+// LDS layouts of the fused backward kernels, in bytes, used by each kernel and by its launcher.  The dW / db dump of
+// lb_combine (NW waves of HT x KT tiles and HT db rows) reuses the kernel's LDS from the start, so a launch asks for
+// the larger of the two.
+constexpr size_t lb_dump_bytes(int HT, int KT, int NW) { return ((size_t)NW * HT * KT * 1024 + (size_t)NW * HT * 64) * 4; }
+// gnm_linear_bwd_fused_kernel (COEF = false) and gnm_linear_bwd_pipe_kernel (COEF = true): the weight image (fp32
+// [HP][KP], or SPLITD: three planes of EW operand entries), the four waves' tile images [32][XS], coef [5][HP]
+template <int KT, int HT, bool SPLITD, bool COEF>
+struct LbLds {
+    static constexpr int KP = KT * 32, HP = HT * 32, XS = (KP > HP ? KP : HP) + 4, EW = 4 * KT * 64;
+    static constexpr size_t xs_off = SPLITD ? (size_t)3 * EW * 16 : (size_t)HP * KP * 4;
+    static constexpr size_t coef_off = xs_off + (size_t)4 * 32 * XS * 4;
+    static constexpr size_t body = coef_off + (COEF ? (size_t)5 * HP * 4 : 0);
+    static constexpr size_t total = body > lb_dump_bytes(HT, KT, 4) ? body : lb_dump_bytes(HT, KT, 4);
+    static_assert((size_t)4 * 2 * KP * 8 <= body, "the lower BatchNorm's sums [4][2][KP] fp64 reuse the body");
+};
+// gnm_linear_bwd_rz_kernel and (NARROW) gnm_linear_bwd_rzn_kernel: forward planes Wf [3][EWF], k-major planes Wb
+// [3][EWB], the waves' tile images [32][XS], coef [6][64] and (not NARROW) the prologue vectors psv [2][64]
+static constexpr int kRzWaves = 8;
+template <bool NARROW>
+struct RzLds {
+    static constexpr int EWF = NARROW ? 128 : 512, EWB = NARROW ? 256 : 512, XS = 68, KT = NARROW ? 1 : 2;
+    static constexpr size_t wb_off = (size_t)3 * EWF * 16;
+    static constexpr size_t xs_off = wb_off + (size_t)3 * EWB * 16;
+    static constexpr size_t coef_off = xs_off + (size_t)kRzWaves * 32 * XS * 4;
+    static constexpr size_t psv_off = coef_off + (size_t)6 * 64 * 4;
+    static constexpr size_t body = psv_off + (NARROW ? 0 : (size_t)2 * 64 * 4);
+    static constexpr size_t total = body > lb_dump_bytes(2, KT, kRzWaves) ? body : lb_dump_bytes(2, KT, kRzWaves);
+};
+
+// The BatchNorm-backward coefficient vectors of a Linear's output columns into LDS: coef[5 or 6][HP] = mean, rstd, cA,
+// m1, m2 and (BIAS) the Linear's bias, zero when it has none.
+template <int HP, bool BIAS>
+__device__ __forceinline__ void lb_stage_coef(float* coef, const float* mean, const float* rstd, const float* cA,
+                                              const float* m1, const float* m2, const float* bias, int tid, int nt) {
+    for (int idx = tid; idx < HP; idx += nt) {
+        coef[idx] = mean[idx]; coef[HP + idx] = rstd[idx]; coef[2 * HP + idx] = cA[idx];
+        coef[3 * HP + idx] = m1[idx]; coef[4 * HP + idx] = m2[idx];
+        if (BIAS) coef[5 * HP + idx] = bias ? bias[idx] : 0.f;
+    }
+}
+
+// The dW / db epilogue of the fused backward kernels.  Every wave dumps its HT x KT accumulator tiles and its HT db
+// rows to LDS (over everything the tile loop kept there); each group of four waves is then summed, in the order
+// w = 0, 1, 2, 3, into one partial row [H * K + H]: row blockIdx.x * GROUPS + grp, when below part_rows (GROUPS > 1).
+// CLIP: columns of dW at or past K (a narrow input's zero padding) are not written.
+template <int HT, int KT, int GROUPS, bool CLIP>
+__device__ __forceinline__ void lb_combine(char* smem, const f32x16 (&wacc)[HT][KT], const float (&dbacc)[HT], float* partial,
+                                           int H, int K, int part_rows, int tid, int lane, int wave) {
+    constexpr int TILE = 16 * 64, WT = HT * KT * TILE, NW = 4 * GROUPS, NT = NW * 64;
+    __syncthreads();
+    float* dump = reinterpret_cast<float*>(smem);                 // [NW][HT*KT][16][64] + [NW][HT][64]
+    float* mine = dump + (size_t)wave * WT;
+#pragma unroll
+    for (int a = 0; a < HT; ++a)
+#pragma unroll
+        for (int b = 0; b < KT; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mine[(a * KT + b) * TILE + r * 64 + lane] = wacc[a][b][r];
+    float* dbdump = dump + (size_t)NW * WT;
+#pragma unroll
+    for (int a = 0; a < HT; ++a) dbdump[(wave * HT + a) * 64 + lane] = dbacc[a];
+    __syncthreads();
+    const size_t pstride = (size_t)H * K + H;
+    for (int idx = tid; idx < GROUPS * WT; idx += NT) {
+        const int grp = idx / WT, rem = idx - grp * WT;
+        const int prow = blockIdx.x * GROUPS + grp;
+        if (GROUPS > 1 && prow >= part_rows) continue;
+        const int ab = rem / TILE;
+        const int rl = rem - ab * TILE;
+        const int r = rl >> 6, ln = rl & 63;
+        const int a = ab / KT, b = ab - a * KT;
+        const int row = 32 * a + (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5);
+        const int col = 32 * b + (ln & 31);
+        if (CLIP && col >= K) continue;
+        float sum = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) sum += dump[(size_t)(4 * grp + w) * WT + rem];
+        partial[(size_t)prow * pstride + (size_t)row * K + col] = sum;
+    }
+    for (int idx = tid; idx < GROUPS * HT * 32; idx += NT) {
+        const int grp = idx / (HT * 32), a = (idx >> 5) % HT, ii = idx & 31;
+        const int prow = blockIdx.x * GROUPS + grp;
+        if (GROUPS > 1 && prow >= part_rows) continue;
+        float sum = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) sum += dbdump[((4 * grp + w) * HT + a) * 64 + ii] + dbdump[((4 * grp + w) * HT + a) * 64 + 32 + ii];
+        partial[(size_t)prow * pstride + (size_t)H * K + 32 * a + ii] = sum;
+    }
+}
+
 // NARROW: K < 32 (the first Linear of layer 0, K = F0): one zero-padded 32-column tile, guarded scalar
 // accesses to X / W / dX, which are small next to the [N,H] streams G and Z.
 // SAMEZ (with STATS): the lower BatchNorm's input sZ IS this Linear's input X and its scale/shift ARE the prologue
@@ -1940,8 +2057,8 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
     static_assert(!SPLITD || (HT == 2 && ((SAMEZ && KT == 2) || NARROW)), "SPLITD: H = 64, the SAMEZ K = 64 form or the narrow one");
     static_assert(!NARROW || (KT == 1 && !STATS), "narrow K: one tile, no lower BatchNorm");
     static_assert(!SAMEZ || STATS, "SAMEZ is a STATS variant");
-    constexpr int KP = KT * 32, HP = HT * 32;
-    constexpr int XS = (KP > HP ? KP : HP) + 4;
+    using L = LbLds<KT, HT, SPLITD, false>;
+    constexpr int KP = L::KP, HP = L::HP, XS = L::XS, EW = L::EW;
     constexpr int H4 = HP / 4;                    // float4 per dZ row
     constexpr int NLD = (32 * H4) / 64;           // float4 loads per lane for a [32][HP] tile
     constexpr int RSTEP = 64 / H4;
@@ -1950,10 +2067,9 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // SPLITD (the SAMEZ K = H = 64 form): the dgrad product runs on the bf16 matrix pipe with dZ and W split into three
     // exact bf16 planes each (see gnm_lin_split_kernel); the weight image is then the three operand planes (24 KB)
-    constexpr int EW = 4 * KT * 64;
     float* Wt = reinterpret_cast<float*>(smem);                   // [HP][KP]: W itself (contraction index first)
     gnm_u32x4* Wp = reinterpret_cast<gnm_u32x4*>(smem);                   // SPLITD: [3][EW] operand entries instead
-    float* Xs_all = SPLITD ? reinterpret_cast<float*>(smem + (size_t)3 * EW * 16) : Wt + (size_t)HP * KP;   // [4][32][XS]
+    float* Xs_all = reinterpret_cast<float*>(smem + L::xs_off);   // [4][32][XS]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2080,29 +2196,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
                 for (int c = 0; c < KT; ++c)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) dacc[c][r] = 0.f;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const float4 v0 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m);
-                    const float4 v1 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m + 4);
-                    const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                    gnm_u32x4 A1, A2, A3;
-                    gnm_split8(f, A1, A2, A3);
-                    const gnm_bf16x8 x1 = __builtin_bit_cast(gnm_bf16x8, A1), x2 = __builtin_bit_cast(gnm_bf16x8, A2),
-                                     x3 = __builtin_bit_cast(gnm_bf16x8, A3);
-#pragma unroll
-                    for (int c = 0; c < KT; ++c) {
-                        const int e = (m * KT + c) * 64 + lane;
-                        const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wp[e]),
-                                         b2 = __builtin_bit_cast(gnm_bf16x8, Wp[EW + e]),
-                                         b3 = __builtin_bit_cast(gnm_bf16x8, Wp[2 * EW + e]);
-                        dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b3, dacc[c], 0, 0, 0);
-                        dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, b1, dacc[c], 0, 0, 0);
-                        dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b2, dacc[c], 0, 0, 0);
-                        dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b2, dacc[c], 0, 0, 0);
-                        dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b1, dacc[c], 0, 0, 0);
-                        dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b1, dacc[c], 0, 0, 0);
-                    }
-                }
+                lin_dgrad_split<KT, HP>(dacc, Xs, XS, Wp, i, h, lane);
             }
         } else if (p.dA) {
             float a[KH];
@@ -2274,41 +2368,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
         }
     }
 
-    // ---- combine the 4 waves' dW / db in a fixed order: one partial per block -------------
-    __syncthreads();
-    constexpr int TILE = 16 * 64;
-    float* dump = reinterpret_cast<float*>(smem);                 // [4][HT*KT][16][64] + [4][HT][64]
-    float* mine = dump + (size_t)wave * HT * KT * TILE;
-#pragma unroll
-    for (int a = 0; a < HT; ++a)
-#pragma unroll
-        for (int b = 0; b < KT; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mine[(a * KT + b) * TILE + r * 64 + lane] = wacc[a][b][r];
-    float* dbdump = dump + (size_t)4 * HT * KT * TILE;
-#pragma unroll
-    for (int a = 0; a < HT; ++a) dbdump[(wave * HT + a) * 64 + lane] = dbacc[a];
-    __syncthreads();
-    float* out = p.partial + (size_t)blockIdx.x * ((size_t)p.H * p.K + p.H);
-    for (int idx = tid; idx < HT * KT * TILE; idx += 256) {
-        const int ab = idx / TILE;
-        const int rl = idx - ab * TILE;
-        const int r = rl >> 6, ln = rl & 63;
-        const int a = ab / KT, b = ab - a * KT;
-        const int row = 32 * a + (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5);
-        const int col = 32 * b + (ln & 31);
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) sum += dump[(size_t)w * HT * KT * TILE + idx];
-        if (!NARROW || col < p.K) out[(size_t)row * p.K + col] = sum;
-    }
-    for (int idx = tid; idx < HT * 32; idx += 256) {
-        const int a = idx >> 5, ii = idx & 31;
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) sum += dbdump[(w * HT + a) * 64 + ii] + dbdump[(w * HT + a) * 64 + 32 + ii];
-        out[(size_t)p.H * p.K + 32 * a + ii] = sum;
-    }
+    lb_combine<HT, KT, 1, NARROW>(smem, wacc, dbacc, p.partial, p.H, p.K, 0, tid, lane, wave);
     GNM_LSTAMP(63)
 }
 
@@ -2332,34 +2392,25 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
 template <int KT, int HT, bool SPLITD = false>
 __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArgs p) {
     static_assert(!SPLITD || (KT == 2 && HT == 2), "SPLITD: K = H = 64 only");
-    constexpr int KP = KT * 32, HP = HT * 32;
-    constexpr int XS = (KP > HP ? KP : HP) + 4;
+    using L = LbLds<KT, HT, SPLITD, true>;
+    constexpr int KP = L::KP, HP = L::HP, XS = L::XS, EW = L::EW;
     constexpr int H4 = HP / 4;
     constexpr int NLD = (32 * H4) / 64;
     constexpr int RSTEP = 64 / H4;
     constexpr int KH = HP / 2;
     constexpr int O4 = KP / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int EW = 4 * KT * 64;
     float* Wt = reinterpret_cast<float*>(smem);                   // [HP][KP]
     gnm_u32x4* Wp = reinterpret_cast<gnm_u32x4*>(smem);                   // SPLITD: [3][EW] bf16 operand entries of W instead
-    float* Xs_all = SPLITD ? reinterpret_cast<float*>(smem + (size_t)3 * EW * 16) : Wt + (size_t)HP * KP;   // [4][32][XS]
-    float* coef = Xs_all + 4 * 32 * XS;                           // [5][HP]: mean, rstd, cA, m1, m2 of the BatchNorm
+    float* Xs_all = reinterpret_cast<float*>(smem + L::xs_off);   // [4][32][XS]
+    float* coef = reinterpret_cast<float*>(smem + L::coef_off);   // [5][HP]: mean, rstd, cA, m1, m2 of the BatchNorm
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, h = lane >> 5;
     float* Xs = Xs_all + wave * 32 * XS;
     if constexpr (SPLITD) {
-        for (int e = tid; e < EW; e += 256) {
-            const int n = e & 31, kg = (e >> 5) & 1, c = (e >> 6) % KT, m = e / (64 * KT);
-            float f[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = p.W[(size_t)(8 * m + 32 * kg + j) * p.ldw + 32 * c + n];
-            gnm_u32x4 p1, p2, p3;
-            gnm_split8(f, p1, p2, p3);
-            Wp[e] = p1; Wp[EW + e] = p2; Wp[2 * EW + e] = p3;
-        }
+        lin_stage_planes<KT, 32, true, false>(Wp, EW, p.W, p.ldw, 0, tid, 256);
     } else {
         for (int idx = tid; idx < HP * KP; idx += 256) {
             const int hh = idx / KP, k = idx - hh * KP;
@@ -2368,10 +2419,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArg
     }
     // the BatchNorm-backward coefficient vectors live in LDS and are read per tile (5 ds_read_b128: they count on
     // lgkmcnt, so re-reading them costs no place in the in-order vector-memory queue and no registers across the tile)
-    for (int idx = tid; idx < HP; idx += 256) {
-        coef[idx] = p.mean[idx]; coef[HP + idx] = p.rstd[idx]; coef[2 * HP + idx] = p.cA[idx];
-        coef[3 * HP + idx] = p.m1[idx]; coef[4 * HP + idx] = p.m2[idx];
-    }
+    lb_stage_coef<HP, false>(coef, p.mean, p.rstd, p.cA, p.m1, p.m2, nullptr, tid, 256);
     const int c4 = lane % H4, lrow0 = lane / H4;
     float psc[KT], psh[KT];
 #pragma unroll
@@ -2455,28 +2503,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArg
             for (int c = 0; c < KT; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) dacc[c][r] = 0.f;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float4 v0 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m);
-                const float4 v1 = *reinterpret_cast<const float4*>(Xs + i * XS + KH * h + 8 * m + 4);
-                const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                gnm_u32x4 A1, A2, A3;
-                gnm_split8(f, A1, A2, A3);
-                const gnm_bf16x8 x1 = __builtin_bit_cast(gnm_bf16x8, A1), x2 = __builtin_bit_cast(gnm_bf16x8, A2),
-                                 x3 = __builtin_bit_cast(gnm_bf16x8, A3);
-#pragma unroll
-                for (int c = 0; c < KT; ++c) {
-                    const int e = (m * KT + c) * 64 + lane;
-                    const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wp[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wp[EW + e]),
-                                     b3 = __builtin_bit_cast(gnm_bf16x8, Wp[2 * EW + e]);
-                    dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b3, dacc[c], 0, 0, 0);
-                    dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, b1, dacc[c], 0, 0, 0);
-                    dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b2, dacc[c], 0, 0, 0);
-                    dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b2, dacc[c], 0, 0, 0);
-                    dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b1, dacc[c], 0, 0, 0);
-                    dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b1, dacc[c], 0, 0, 0);
-                }
-            }
+            lin_dgrad_split<KT, HP>(dacc, Xs, XS, Wp, i, h, lane);
         } else {
             float a[KH];
 #pragma unroll
@@ -2554,50 +2581,12 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArg
         }
     }
 
-    // ---- combine the 4 waves' dW / db in a fixed order: one partial per block (as in the kernel above) ----
-    __syncthreads();
-    constexpr int TILE = 16 * 64;
-    float* dump = reinterpret_cast<float*>(smem);
-    float* mine = dump + (size_t)wave * HT * KT * TILE;
-#pragma unroll
-    for (int a = 0; a < HT; ++a)
-#pragma unroll
-        for (int b = 0; b < KT; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mine[(a * KT + b) * TILE + r * 64 + lane] = wacc[a][b][r];
-    float* dbdump = dump + (size_t)4 * HT * KT * TILE;
-#pragma unroll
-    for (int a = 0; a < HT; ++a) dbdump[(wave * HT + a) * 64 + lane] = dbacc[a];
-    __syncthreads();
-    float* out = p.partial + (size_t)blockIdx.x * ((size_t)p.H * p.K + p.H);
-    for (int idx = tid; idx < HT * KT * TILE; idx += 256) {
-        const int ab = idx / TILE;
-        const int rl = idx - ab * TILE;
-        const int r = rl >> 6, ln = rl & 63;
-        const int a = ab / KT, b = ab - a * KT;
-        const int row = 32 * a + (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5);
-        const int col = 32 * b + (ln & 31);
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) sum += dump[(size_t)w * HT * KT * TILE + idx];
-        out[(size_t)row * p.K + col] = sum;
-    }
-    for (int idx = tid; idx < HT * 32; idx += 256) {
-        const int a = idx >> 5, ii = idx & 31;
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) sum += dbdump[(w * HT + a) * 64 + ii] + dbdump[(w * HT + a) * 64 + 32 + ii];
-        out[(size_t)p.H * p.K + 32 * a + ii] = sum;
-    }
+    lb_combine<HT, KT, 1, false>(smem, wacc, dbacc, p.partial, p.H, p.K, 0, tid, lane, wave);
 }
 
 template <int KT, int HT, bool SPLITD = false>
 static int launch_lb_pipe(const LbArgs& a, int grid, hipStream_t s) {
-    constexpr int KP = KT * 32, HP = HT * 32;
-    constexpr int XS = (KP > HP ? KP : HP) + 4;
-    size_t lds = (SPLITD ? (size_t)3 * 4 * KT * 64 * 16 : (size_t)HP * KP * 4) + (size_t)4 * 32 * XS * 4 + (size_t)5 * HP * 4;
-    const size_t dump = ((size_t)4 * HT * KT * 1024 + (size_t)4 * HT * 64) * 4;
-    if (dump > lds) lds = dump;
+    const size_t lds = LbLds<KT, HT, SPLITD, true>::total;
     GNM_ALLOW_FULL_LDS((&gnm_linear_bwd_pipe_kernel<KT, HT, SPLITD>));
     hipLaunchKernelGGL((gnm_linear_bwd_pipe_kernel<KT, HT, SPLITD>), dim3(grid), dim3(256), lds, s, a);
     GNM_CHECK_LAUNCH();
@@ -2606,11 +2595,7 @@ static int launch_lb_pipe(const LbArgs& a, int grid, hipStream_t s) {
 
 template <int KT, int HT, bool STATS, bool NARROW = false, bool SAMEZ = false, bool SPLITD = false>
 static int launch_lb(const LbArgs& a, int grid, hipStream_t s) {
-    constexpr int KP = KT * 32, HP = HT * 32;
-    constexpr int XS = (KP > HP ? KP : HP) + 4;
-    size_t lds = (SPLITD ? (size_t)3 * 4 * KT * 64 * 16 : (size_t)HP * KP * 4) + (size_t)4 * 32 * XS * 4;
-    const size_t dump = ((size_t)4 * HT * KT * 1024 + (size_t)4 * HT * 64) * 4;
-    if (dump > lds) lds = dump;
+    const size_t lds = LbLds<KT, HT, SPLITD, false>::total;
     GNM_ALLOW_FULL_LDS((&gnm_linear_bwd_fused_kernel<KT, HT, STATS, NARROW, SAMEZ, SPLITD>));
     hipLaunchKernelGGL((gnm_linear_bwd_fused_kernel<KT, HT, STATS, NARROW, SAMEZ, SPLITD>), dim3(grid), dim3(256), lds, s, a);
     GNM_CHECK_LAUNCH();
@@ -2639,16 +2624,50 @@ static int launch_lb(const LbArgs& a, int grid, hipStream_t s) {
 // No lower BatchNorm statistics: the second Linear of an MLP keeps gnm_linear_bwd_fused_kernel (DESIGN_HISTORY.md,
 // "Retired variants").
 // ---------------------------------------------------------------------------------
-static constexpr int kRzWaves = 8;
+// What gnm_linear_bwd_rz_kernel and its narrow form share beyond the helpers above.
+// G of a tile in the accumulator layout (lane = column 32 a + i, rows (r & 3) + 8 (r >> 2) + 4 h): 4-byte loads clipped by
+// the tile's descriptor; a tile past the end gets an empty one and no traffic.
+__device__ __forceinline__ void rz_load_g(float (&g)[2][16], const float* G, int ldg, int N, int tile, int g_voff) {
+    const long long row0 = (long long)tile * 32;
+    const long long rows = min((long long)N - row0, 32LL);
+    const __amdgpu_buffer_rsrc_t rg = gnm_tile_rsrc(G + row0 * ldg, rows, ldg, 64);
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+            g[a][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rg, g_voff + 128 * a, ((r & 3) + 8 * (r >> 2)) * ldg * 4, 0));
+}
+// The BatchNorm backward on one column tile of the accumulators (lane = column col): dz holds Z - bias on entry and
+// dZ = cA (G - m1 - xhat m2) on exit, zero in rows past `rows`; dZ is also written to the wave's image Xs (for dgrad).
+// Returns the lane's column sum of dZ.
+__device__ __forceinline__ float rz_bn_bwd(f32x16& dz, const float (&g)[16], const float* coef, int col, int rows, float* Xs,
+                                           int xs, int h) {
+    const float mu = coef[col], rs = coef[64 + col], ca = coef[128 + col], a1 = coef[192 + col], a2 = coef[256 + col],
+                bz = coef[320 + col];
+    float dsum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int lrow = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const float z = dz[r] + bz;
+        float d = ca * (g[r] - a1 - (z - mu) * rs * a2);
+        if (lrow >= rows) d = 0.f;
+        dz[r] = d;
+        dsum += d;
+        Xs[lrow * xs + col] = d;
+    }
+    return dsum;
+}
 
 __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const LbArgs p) {
-    constexpr int KP = 64, HP = 64, XS = 68, EW = 512, NW = kRzWaves, NT = NW * 64, TILE = 16 * 64;
+    using L = RzLds<false>;
+    constexpr int KP = 64, HP = 64, XS = L::XS, EW = 512, NW = kRzWaves, NT = NW * 64;
+    static_assert(L::EWF == EW && L::EWB == EW, "both plane images hold 4 m x 2 c x 64 entries");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     gnm_u32x4* Wf = reinterpret_cast<gnm_u32x4*>(smem);                   // [3][EW]: (m, c, lane = 32 kg + n) = W[32c+n][8m+32kg+j]
-    gnm_u32x4* Wb = Wf + 3 * EW;                                      // [3][EW]: (m, c, lane = 32 kg + n) = W[8m+32kg+j][32c+n]
-    float* Xs_all = reinterpret_cast<float*>(smem + (size_t)6 * EW * 16);     // [NW][32][XS]
-    float* coef = Xs_all + NW * 32 * XS;                          // [6][64]: mean, rstd, cA, m1, m2, bias
-    float* psv = coef + 6 * 64;                                   // [2][64]: prologue scale, shift
+    gnm_u32x4* Wb = reinterpret_cast<gnm_u32x4*>(smem + L::wb_off);       // [3][EW]: (m, c, lane = 32 kg + n) = W[8m+32kg+j][32c+n]
+    float* Xs_all = reinterpret_cast<float*>(smem + L::xs_off);   // [NW][32][XS]
+    float* coef = reinterpret_cast<float*>(smem + L::coef_off);   // [6][64]: mean, rstd, cA, m1, m2, bias
+    float* psv = reinterpret_cast<float*>(smem + L::psv_off);     // [2][64]: prologue scale, shift
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2656,22 +2675,10 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
     float* Xs = Xs_all + wave * 32 * XS;
     const bool pro = p.pro_scale != nullptr;
     GNM_RSTAMP(0)
-    for (int e = tid; e < EW; e += NT) {
-        const int n = e & 31, kg = (e >> 5) & 1, c = (e >> 6) & 1, m = e >> 7;
-        float f[8];
-        gnm_u32x4 p1, p2, p3;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = p.W[(size_t)(32 * c + n) * p.ldw + 8 * m + 32 * kg + j];
-        gnm_split8(f, p1, p2, p3);
-        Wf[e] = p1; Wf[EW + e] = p2; Wf[2 * EW + e] = p3;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = p.W[(size_t)(8 * m + 32 * kg + j) * p.ldw + 32 * c + n];
-        gnm_split8(f, p1, p2, p3);
-        Wb[e] = p1; Wb[EW + e] = p2; Wb[2 * EW + e] = p3;
-    }
+    lin_stage_planes<2, 32, false, false>(Wf, EW, p.W, p.ldw, 0, tid, NT);
+    lin_stage_planes<2, 32, true, false>(Wb, EW, p.W, p.ldw, 0, tid, NT);
+    lb_stage_coef<64, true>(coef, p.mean, p.rstd, p.cA, p.m1, p.m2, p.bias, tid, NT);
     for (int idx = tid; idx < 64; idx += NT) {
-        coef[idx] = p.mean[idx]; coef[64 + idx] = p.rstd[idx]; coef[128 + idx] = p.cA[idx];
-        coef[192 + idx] = p.m1[idx]; coef[256 + idx] = p.m2[idx]; coef[320 + idx] = p.bias ? p.bias[idx] : 0.f;
         psv[idx] = pro ? p.pro_scale[idx] : 1.f;
         psv[64 + idx] = pro ? p.pro_shift[idx] : 0.f;
     }
@@ -2716,16 +2723,6 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
             xa[m][1] = __builtin_amdgcn_raw_buffer_load_b128(rx, xa_voff, 32 * m + 16, 0);
         }
     };
-    auto load_next_g = [&](int tile) {
-        const long long row0 = (long long)tile * 32;
-        const long long rows = min((long long)p.N - row0, 32LL);
-        const __amdgpu_buffer_rsrc_t rg = gnm_tile_rsrc(p.G + row0 * p.ldg, rows, p.ldg, HP);
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-                g[a][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rg, g_voff + 128 * a, ((r & 3) + 8 * (r >> 2)) * p.ldg * 4, 0));
-    };
     auto do_tile = [&](int t, int t_next) {
         const int r0 = t * 32;
         const int rows = min(p.N - r0, 32);
@@ -2754,43 +2751,15 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
                     for (int j = 0; j < 8; ++j) f[j] = gnm_relu(f[j]);
                 }
             }
-            gnm_u32x4 A1, A2, A3;
-            gnm_split8(f, A1, A2, A3);
-            const gnm_bf16x8 a1 = __builtin_bit_cast(gnm_bf16x8, A1), a2 = __builtin_bit_cast(gnm_bf16x8, A2),
-                             a3 = __builtin_bit_cast(gnm_bf16x8, A3);
+            gnm_bf16x8 a1, a2, a3;
+            gnm_split8(f, a1, a2, a3);
 #pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int e = (m * 2 + c) * 64 + lane;
-                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wf[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wf[EW + e]),
-                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wf[2 * EW + e]);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, dz[c], 0, 0, 0);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, dz[c], 0, 0, 0);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, dz[c], 0, 0, 0);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, dz[c], 0, 0, 0);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, dz[c], 0, 0, 0);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, dz[c], 0, 0, 0);
-            }
+            for (int c = 0; c < 2; ++c) gnm_mma6_planes(dz[c], a1, a2, a3, Wf, EW, (m * 2 + c) * 64 + lane);
         }
         GNM_RSTAMP(3 + 6 * min(tk, 9))
         // ---- dZ = cA (G - m1 - xhat m2) on the accumulators; rows past N are zero; image for dgrad ------------
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int col = 32 * a + i;
-            const float mu = coef[col], rs = coef[64 + col], ca = coef[128 + col], a1 = coef[192 + col],
-                        a2 = coef[256 + col], bz = coef[320 + col];
-            float dsum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int lrow = (r & 3) + 8 * (r >> 2) + 4 * h;
-                const float z = dz[a][r] + bz;
-                float d = ca * (g[a][r] - a1 - (z - mu) * rs * a2);
-                if (lrow >= rows) d = 0.f;
-                dz[a][r] = d;
-                dsum += d;
-                Xs[lrow * XS + col] = d;
-            }
-            dbacc[a] += dsum;
-        }
+        for (int a = 0; a < 2; ++a) dbacc[a] += rz_bn_bwd(dz[a], g[a], coef, 32 * a + i, rows, Xs, XS, h);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -2813,28 +2782,7 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
         for (int c = 0; c < 2; ++c)
 #pragma unroll
             for (int r = 0; r < 16; ++r) dacc[c][r] = 0.f;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const float4 v0 = *reinterpret_cast<const float4*>(Xs + i * XS + 32 * h + 8 * m);
-            const float4 v1 = *reinterpret_cast<const float4*>(Xs + i * XS + 32 * h + 8 * m + 4);
-            const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-            gnm_u32x4 A1, A2, A3;
-            gnm_split8(f, A1, A2, A3);
-            const gnm_bf16x8 x1 = __builtin_bit_cast(gnm_bf16x8, A1), x2 = __builtin_bit_cast(gnm_bf16x8, A2),
-                             x3 = __builtin_bit_cast(gnm_bf16x8, A3);
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int e = (m * 2 + c) * 64 + lane;
-                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wb[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wb[EW + e]),
-                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wb[2 * EW + e]);
-                dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b3, dacc[c], 0, 0, 0);
-                dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, b1, dacc[c], 0, 0, 0);
-                dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b2, dacc[c], 0, 0, 0);
-                dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b2, dacc[c], 0, 0, 0);
-                dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b1, dacc[c], 0, 0, 0);
-                dacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b1, dacc[c], 0, 0, 0);
-            }
-        }
+        lin_dgrad_split<2, HP>(dacc, Xs, XS, Wb, i, h, lane);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();          // the dZ image has been read
         GNM_RSTAMP(5 + 6 * min(tk, 9))
@@ -2860,7 +2808,7 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
         __builtin_amdgcn_wave_barrier();
         GNM_RSTAMP(6 + 6 * min(tk, 9))
         // the next tile: G and the row-wise X fragments before the weight-gradient product
-        load_next_g(t_next);                      // past the wave's last tile: empty descriptors, no traffic
+        rz_load_g(g, p.G, p.ldg, p.N, t_next, (int)g_voff);                      // past the wave's last tile: empty descriptors, no traffic
         load_next_x(t_next);
         // ---- dW += dZ^T f(X): both operands from registers, batch rows in the accumulators' order ---------------------
 #pragma unroll
@@ -2869,12 +2817,9 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 float f[8];
-                gnm_u32x4 p1, p2, p3;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) f[j] = dz[a][8 * m + j];
-                gnm_split8(f, p1, p2, p3);
-                dp[a][0] = __builtin_bit_cast(gnm_bf16x8, p1); dp[a][1] = __builtin_bit_cast(gnm_bf16x8, p2);
-                dp[a][2] = __builtin_bit_cast(gnm_bf16x8, p3);
+                gnm_split8(f, dp[a][0], dp[a][1], dp[a][2]);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     float x = xv[8 * m + j][a];
@@ -2884,21 +2829,12 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
                     }
                     f[j] = x;
                 }
-                gnm_split8(f, p1, p2, p3);
-                xp[a][0] = __builtin_bit_cast(gnm_bf16x8, p1); xp[a][1] = __builtin_bit_cast(gnm_bf16x8, p2);
-                xp[a][2] = __builtin_bit_cast(gnm_bf16x8, p3);
+                gnm_split8(f, xp[a][0], xp[a][1], xp[a][2]);
             }
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][2], wacc[a][b], 0, 0, 0);
-                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][2], xp[b][0], wacc[a][b], 0, 0, 0);
-                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][1], xp[b][1], wacc[a][b], 0, 0, 0);
-                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][1], wacc[a][b], 0, 0, 0);
-                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][1], xp[b][0], wacc[a][b], 0, 0, 0);
-                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dp[a][0], xp[b][0], wacc[a][b], 0, 0, 0);
-                }
+                for (int b = 0; b < 2; ++b) gnm_mma6(wacc[a][b], dp[a][0], dp[a][1], dp[a][2], xp[b][0], xp[b][1], xp[b][2]);
         }
         GNM_RSTAMP(7 + 6 * min(tk, 9))
         ++tk;
@@ -2906,7 +2842,7 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
     {
         int t = gw;
         load_next_x(t);
-        load_next_g(t);
+        rz_load_g(g, p.G, p.ldg, p.N, t, (int)g_voff);
         if (t < ntiles) {
             do_tile(t, t + tstride);                  // peeled (see gnm_linear_bwd_pipe_kernel)
             for (t += tstride; t < ntiles; t += tstride) do_tile(t, t + tstride);
@@ -2915,51 +2851,12 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
     __builtin_amdgcn_s_waitcnt(0x0F70);
     GNM_RSTAMP(62)
 
-    // ---- dW / db: the waves of each half in a fixed order ----
-    __syncthreads();
-    float* dump = reinterpret_cast<float*>(smem);                 // [NW][4][16][64] + [NW][2][64]
-    float* mine = dump + (size_t)wave * 4 * TILE;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mine[(a * 2 + b) * TILE + r * 64 + lane] = wacc[a][b][r];
-    float* dbdump = dump + (size_t)NW * 4 * TILE;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) dbdump[(wave * 2 + a) * 64 + lane] = dbacc[a];
-    __syncthreads();
-    for (int idx = tid; idx < 2 * 4 * TILE; idx += NT) {
-        const int grp = idx / (4 * TILE), rem = idx - grp * 4 * TILE;
-        const int prow = blockIdx.x * 2 + grp;
-        if (prow >= p.part_rows) continue;
-        const int ab = rem / TILE;
-        const int rl = rem - ab * TILE;
-        const int r = rl >> 6, ln = rl & 63;
-        const int a = ab >> 1, b = ab & 1;
-        const int row = 32 * a + (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5);
-        const int col = 32 * b + (ln & 31);
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) sum += dump[(size_t)(4 * grp + w) * 4 * TILE + rem];
-        p.partial[(size_t)prow * ((size_t)HP * KP + HP) + (size_t)row * KP + col] = sum;
-    }
-    for (int idx = tid; idx < 2 * 64; idx += NT) {
-        const int grp = idx >> 6, a = (idx >> 5) & 1, ii = idx & 31;
-        const int prow = blockIdx.x * 2 + grp;
-        if (prow >= p.part_rows) continue;
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) sum += dbdump[((4 * grp + w) * 2 + a) * 64 + ii] + dbdump[((4 * grp + w) * 2 + a) * 64 + 32 + ii];
-        p.partial[(size_t)prow * ((size_t)HP * KP + HP) + (size_t)HP * KP + 32 * a + ii] = sum;
-    }
+    lb_combine<2, 2, 2, false>(smem, wacc, dbacc, p.partial, HP, KP, p.part_rows, tid, lane, wave);
     GNM_RSTAMP(63)
 }
 
 static int launch_lb_rz(const LbArgs& a, int grid, hipStream_t s) {
-    size_t lds = (size_t)6 * 512 * 16 + (size_t)kRzWaves * 32 * 68 * 4 + (size_t)8 * 64 * 4;
-    const size_t dump = ((size_t)kRzWaves * 4 * 1024 + (size_t)kRzWaves * 2 * 64) * 4;
-    if (dump > lds) lds = dump;
+    const size_t lds = RzLds<false>::total;
     GNM_ALLOW_FULL_LDS((&gnm_linear_bwd_rz_kernel));
     hipLaunchKernelGGL(gnm_linear_bwd_rz_kernel, dim3((grid + 1) / 2), dim3(kRzWaves * 64), lds, s, a);
     GNM_CHECK_LAUNCH();
@@ -2975,40 +2872,22 @@ static int launch_lb_rz(const LbArgs& a, int grid, hipStream_t s) {
 // are K floats wide and not 16-byte addressable: 4-byte accesses, clipped by their buffer descriptors.
 // ---------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const LbArgs p) {
-    constexpr int HP = 64, XS = 68, NW = kRzWaves, NT = NW * 64, TILE = 16 * 64;
+    using L = RzLds<true>;
+    constexpr int HP = 64, XS = L::XS, NW = kRzWaves, NT = NW * 64, TILE = 16 * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     gnm_u32x4* Wf = reinterpret_cast<gnm_u32x4*>(smem);                   // [3][2 c][64]: (c, lane = 32 kg + n) = W[32c+n][8kg+j], k < K
-    gnm_u32x4* Wb = Wf + 3 * 128;                                     // [3][4 m][64]: (m, lane = 32 kg + n) = W[8m+32kg+j][n], n < K
-    float* Xs_all = reinterpret_cast<float*>(smem + (size_t)(3 * 128 + 3 * 256) * 16);    // [NW][32][XS]
-    float* coef = Xs_all + NW * 32 * XS;                          // [6][64]: mean, rstd, cA, m1, m2, bias
+    gnm_u32x4* Wb = reinterpret_cast<gnm_u32x4*>(smem + L::wb_off);       // [3][4 m][64]: (m, lane = 32 kg + n) = W[8m+32kg+j][n], n < K
+    float* Xs_all = reinterpret_cast<float*>(smem + L::xs_off);   // [NW][32][XS]
+    float* coef = reinterpret_cast<float*>(smem + L::coef_off);   // [6][64]: mean, rstd, cA, m1, m2, bias
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, h = lane >> 5;
     float* Xs = Xs_all + wave * 32 * XS;
     const int K = p.K;
-    for (int e = tid; e < 128; e += NT) {
-        const int n = e & 31, kg = (e >> 5) & 1, c = e >> 6;
-        float f[8];
-        gnm_u32x4 p1, p2, p3;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = 8 * kg + j < K ? p.W[(size_t)(32 * c + n) * p.ldw + 8 * kg + j] : 0.f;
-        gnm_split8(f, p1, p2, p3);
-        Wf[e] = p1; Wf[128 + e] = p2; Wf[256 + e] = p3;
-    }
-    for (int e = tid; e < 256; e += NT) {
-        const int n = e & 31, kg = (e >> 5) & 1, m = e >> 6;
-        float f[8];
-        gnm_u32x4 p1, p2, p3;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = n < K ? p.W[(size_t)(8 * m + 32 * kg + j) * p.ldw + n] : 0.f;
-        gnm_split8(f, p1, p2, p3);
-        Wb[e] = p1; Wb[256 + e] = p2; Wb[512 + e] = p3;
-    }
-    for (int idx = tid; idx < 64; idx += NT) {
-        coef[idx] = p.mean[idx]; coef[64 + idx] = p.rstd[idx]; coef[128 + idx] = p.cA[idx];
-        coef[192 + idx] = p.m1[idx]; coef[256 + idx] = p.m2[idx]; coef[320 + idx] = p.bias ? p.bias[idx] : 0.f;
-    }
+    lin_stage_planes<2, 8, false, true>(Wf, L::EWF, p.W, p.ldw, K, tid, NT);
+    lin_stage_planes<1, 32, true, true>(Wb, L::EWB, p.W, p.ldw, K, tid, NT);
+    lb_stage_coef<64, true>(coef, p.mean, p.rstd, p.cA, p.m1, p.m2, p.bias, tid, NT);
     __builtin_amdgcn_s_waitcnt(0x0F70);
     __syncthreads();
 
@@ -3027,16 +2906,6 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const
     const unsigned da_voff = i < K ? (unsigned)((4 * h * p.lda + i) * 4) : kclip;     // dX[row(r, h)][i]
 
     float g[2][16];
-    auto load_next_g = [&](int tile) {
-        const long long row0 = (long long)tile * 32;
-        const long long rows = min((long long)p.N - row0, 32LL);
-        const __amdgpu_buffer_rsrc_t rg = gnm_tile_rsrc(p.G + row0 * p.ldg, rows, p.ldg, HP);
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-                g[a][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rg, g_voff + 128 * a, ((r & 3) + 8 * (r >> 2)) * p.ldg * 4, 0));
-    };
     auto do_tile = [&](int t, int t_next) {
         const int r0 = t * 32;
         const int rows = min(p.N - r0, 32);
@@ -3057,113 +2926,59 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const
 #pragma unroll
             for (int r = 0; r < 16; ++r) dz[c][r] = 0.f;
         {
-            gnm_u32x4 A1, A2, A3;
-            gnm_split8(fx, A1, A2, A3);
-            const gnm_bf16x8 a1 = __builtin_bit_cast(gnm_bf16x8, A1), a2 = __builtin_bit_cast(gnm_bf16x8, A2),
-                             a3 = __builtin_bit_cast(gnm_bf16x8, A3);
+            gnm_bf16x8 a1, a2, a3;
+            gnm_split8(fx, a1, a2, a3);
 #pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int e = c * 64 + lane;
-                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wf[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wf[128 + e]),
-                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wf[256 + e]);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, dz[c], 0, 0, 0);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, dz[c], 0, 0, 0);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, dz[c], 0, 0, 0);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, dz[c], 0, 0, 0);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, dz[c], 0, 0, 0);
-                dz[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, dz[c], 0, 0, 0);
-            }
+            for (int c = 0; c < 2; ++c) gnm_mma6_planes(dz[c], a1, a2, a3, Wf, L::EWF, c * 64 + lane);
         }
         // ---- dZ = cA (G - m1 - xhat m2) on the accumulators; image for dgrad -----------------------------------------
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int col = 32 * a + i;
-            const float mu = coef[col], rs = coef[64 + col], ca = coef[128 + col], a1 = coef[192 + col],
-                        a2 = coef[256 + col], bz = coef[320 + col];
-            float dsum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int lrow = (r & 3) + 8 * (r >> 2) + 4 * h;
-                const float z = dz[a][r] + bz;
-                float d = ca * (g[a][r] - a1 - (z - mu) * rs * a2);
-                if (lrow >= rows) d = 0.f;
-                dz[a][r] = d;
-                dsum += d;
-                Xs[lrow * XS + col] = d;
-            }
-            dbacc[a] += dsum;
-        }
+        for (int a = 0; a < 2; ++a) dbacc[a] += rz_bn_bwd(dz[a], g[a], coef, 32 * a + i, rows, Xs, XS, h);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         // ---- dX = dZ W: one column tile (columns past K are zero and not stored) ------------------------------------
         if (p.dA) {
-            f32x16 dacc;
+            f32x16 dacc[1];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) dacc[r] = 0.f;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float4 v0 = *reinterpret_cast<const float4*>(Xs + i * XS + 32 * h + 8 * m);
-                const float4 v1 = *reinterpret_cast<const float4*>(Xs + i * XS + 32 * h + 8 * m + 4);
-                const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                gnm_u32x4 A1, A2, A3;
-                gnm_split8(f, A1, A2, A3);
-                const gnm_bf16x8 x1 = __builtin_bit_cast(gnm_bf16x8, A1), x2 = __builtin_bit_cast(gnm_bf16x8, A2),
-                                 x3 = __builtin_bit_cast(gnm_bf16x8, A3);
-                const int e = m * 64 + lane;
-                const gnm_bf16x8 b1 = __builtin_bit_cast(gnm_bf16x8, Wb[e]), b2 = __builtin_bit_cast(gnm_bf16x8, Wb[256 + e]),
-                                 b3 = __builtin_bit_cast(gnm_bf16x8, Wb[512 + e]);
-                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b3, dacc, 0, 0, 0);
-                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, b1, dacc, 0, 0, 0);
-                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b2, dacc, 0, 0, 0);
-                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b2, dacc, 0, 0, 0);
-                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, b1, dacc, 0, 0, 0);
-                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, b1, dacc, 0, 0, 0);
-            }
+            for (int r = 0; r < 16; ++r) dacc[0][r] = 0.f;
+            lin_dgrad_split<1, HP>(dacc, Xs, XS, Wb, i, h, lane);
             const __amdgpu_buffer_rsrc_t rd = gnm_tile_rsrc(p.dA + (size_t)r0 * p.lda, rows, p.lda, K);
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dacc[r]), rd, da_voff, ((r & 3) + 8 * (r >> 2)) * p.lda * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dacc[0][r]), rd, da_voff, ((r & 3) + 8 * (r >> 2)) * p.lda * 4, 0);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();          // the dZ image has been read
-        load_next_g(t_next);                      // past the wave's last tile: empty descriptors, no traffic
+        rz_load_g(g, p.G, p.ldg, p.N, t_next, (int)g_voff);                      // past the wave's last tile: empty descriptors, no traffic
         // ---- dW += dZ^T X: both operands from registers, batch rows in the accumulators' order -----------------------
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             float f[8];
-            gnm_u32x4 p1, p2, p3;
+            gnm_bf16x8 x1, x2, x3, d1, d2, d3;
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = xv[8 * m + j];
-            gnm_split8(f, p1, p2, p3);
-            const gnm_bf16x8 x1 = __builtin_bit_cast(gnm_bf16x8, p1), x2 = __builtin_bit_cast(gnm_bf16x8, p2),
-                             x3 = __builtin_bit_cast(gnm_bf16x8, p3);
+            gnm_split8(f, x1, x2, x3);
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) f[j] = dz[a][8 * m + j];
-                gnm_split8(f, p1, p2, p3);
-                const gnm_bf16x8 d1 = __builtin_bit_cast(gnm_bf16x8, p1), d2 = __builtin_bit_cast(gnm_bf16x8, p2),
-                                 d3 = __builtin_bit_cast(gnm_bf16x8, p3);
-                wacc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d1, x3, wacc[a], 0, 0, 0);
-                wacc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d3, x1, wacc[a], 0, 0, 0);
-                wacc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d2, x2, wacc[a], 0, 0, 0);
-                wacc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d1, x2, wacc[a], 0, 0, 0);
-                wacc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d2, x1, wacc[a], 0, 0, 0);
-                wacc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d1, x1, wacc[a], 0, 0, 0);
+                gnm_split8(f, d1, d2, d3);
+                gnm_mma6(wacc[a], d1, d2, d3, x1, x2, x3);
             }
         }
     };
     {
         int t = gw;
-        load_next_g(t);
+        rz_load_g(g, p.G, p.ldg, p.N, t, (int)g_voff);
         if (t < ntiles) {
             do_tile(t, t + tstride);
             for (t += tstride; t < ntiles; t += tstride) do_tile(t, t + tstride);
         }
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);
-    // ---- dW [64 x K] / db: the waves of each half in a fixed order ----
+    // ---- dW [64 x K] / db: the waves of each half in a fixed order (lb_combine<2, 1, 2, true>, spelled out: through the
+    //      helper hipcc of ROCm 7.2 moved an MFMA inside this kernel's tile loop; fold it in when the toolchain changes) ----
     __syncthreads();
     float* dump = reinterpret_cast<float*>(smem);                 // [NW][2][16][64] + [NW][2][64]
     float* mine = dump + (size_t)wave * 2 * TILE;
@@ -3203,9 +3018,7 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const
 }
 
 static int launch_lb_rzn(const LbArgs& a, int grid, hipStream_t s) {
-    size_t lds = (size_t)(3 * 128 + 3 * 256) * 16 + (size_t)kRzWaves * 32 * 68 * 4 + (size_t)6 * 64 * 4;
-    const size_t dump = ((size_t)kRzWaves * 2 * 1024 + (size_t)kRzWaves * 2 * 64) * 4;
-    if (dump > lds) lds = dump;
+    const size_t lds = RzLds<true>::total;
     GNM_ALLOW_FULL_LDS((&gnm_linear_bwd_rzn_kernel));
     hipLaunchKernelGGL(gnm_linear_bwd_rzn_kernel, dim3((grid + 1) / 2), dim3(kRzWaves * 64), lds, s, a);
     GNM_CHECK_LAUNCH();
@@ -3309,7 +3122,7 @@ extern "C" int gnm_linear_bwd_fused_rz(const float* G, int ldg, const float* bia
 
 // The dW / db partial reductions of several gnm_linear_bwd_fused calls (dW = NULL there) in ONE launch: nothing in
 // the backward depends on a weight gradient, so the ten ~5-us reductions of a step need not sit between its kernels.
-// Same summation order per element as gnm_reduce_partials_kernel.
+// The per-element summation is gnm_reduce_partials_kernel's (reduce_partials_element).
 #define GNM_MAX_REDUCE_JOBS 32
 struct ReduceJobs {
     const float* partial[GNM_MAX_REDUCE_JOBS];
@@ -3327,24 +3140,10 @@ __global__ void __launch_bounds__(1024) gnm_reduce_partials_multi_kernel(const R
     const int nblk = J.nblk[j], H = J.H[j], kw = J.K[j];
     const long long stride = (long long)H * kw + H;
     const int tid = threadIdx.x;
-    const int grp = tid >> 5, ngrp = (int)blockDim.x >> 5;
     const int e = ((int)blockIdx.x - J.first_block[j]) * 32 + (tid & 31);
     const int count = H * kw + H;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (e < count) {
-        int b = grp;
-        for (; b + 3 * ngrp < nblk; b += 4 * ngrp) {
-            const float v0 = partial[(size_t)(b + 0 * ngrp) * stride + e], v1 = partial[(size_t)(b + 1 * ngrp) * stride + e];
-            const float v2 = partial[(size_t)(b + 2 * ngrp) * stride + e], v3 = partial[(size_t)(b + 3 * ngrp) * stride + e];
-            s0 += v0; s1 += v1; s2 += v2; s3 += v3;
-        }
-        for (; b < nblk; b += ngrp) s0 += partial[(size_t)b * stride + e];
-    }
-    red[grp][tid & 31] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
+    const float s = reduce_partials_element(partial, nblk, stride, e, count, red);
     if (tid < 32 && e < count) {
-        float s = 0.f;
-        for (int g = 0; g < ngrp; ++g) s += red[g][tid];
         if (e < H * kw) {
             const int row = e / kw, col = e - row * kw;
             J.dW[j][(size_t)row * J.ldw[j] + col] = s;
