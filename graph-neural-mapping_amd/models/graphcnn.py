@@ -812,7 +812,11 @@ class GIN_InfoMaxReg(nn.Module):
             ident = np.arange(batch.B, dtype=np.int64)
             X0 = torch.zeros_like(X) if baseline is None else baseline.repeat(batch.B, 1)
             with torch.no_grad():
-                c1 = self._run(batch, X, ident, want_disc=False)[0]
+                # base is predict()'s logit to the bit: layer 0's aggregate from the arena's cache, as forward_batch
+                # takes it (an input wider than the evaluation encoder's 128 columns runs the training kernels,
+                # where A X formed per batch differs from the cached one in the last bits)
+                P0 = batch.arena.features_and_agg0(batch, self._spec.n_avg, not self._spec.learn_eps)[1]
+                c1 = self._run(batch, X, ident, want_disc=False, P0=P0)[0]
                 c0 = self._run(batch, X0, ident, want_disc=False)[0]
             scores.append((c1.detach()[:, classes].t().contiguous(), c0.detach()[:, classes].t().contiguous()))
         run = functools.partial(integrated_gradients_hip, alphas=alphas, weights=weights, baseline=baseline)
