@@ -2054,7 +2054,7 @@ __device__ __forceinline__ void lb_combine(char* smem, const f32x16 (&wacc)[HT][
 // rows are its dX accumulator rows, and no second pass over that array is made.
 template <int KT, int HT, bool STATS, bool NARROW = false, bool SAMEZ = false, bool SPLITD = false>
 __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbArgs p) {   // 2 waves/SIMD: <= 256 registers
-    static_assert(!SPLITD || (HT == 2 && ((SAMEZ && KT == 2) || NARROW)), "SPLITD: H = 64, the SAMEZ K = 64 form or the narrow one");
+    static_assert(!SPLITD || (HT == 2 && NARROW), "SPLITD: H = 64, the narrow form (SAMEZ K = 64: gnm_linear_bwd_pipe_sz_kernel)");
     static_assert(!NARROW || (KT == 1 && !STATS), "narrow K: one tile, no lower BatchNorm");
     static_assert(!SAMEZ || STATS, "SAMEZ is a STATS variant");
     using L = LbLds<KT, HT, SPLITD, false>;
@@ -2065,8 +2065,8 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
     constexpr int KH = HP / 2;                    // dgrad MFMA steps (contraction over H)
     constexpr int O4 = KP / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // SPLITD (the SAMEZ K = H = 64 form): the dgrad product runs on the bf16 matrix pipe with dZ and W split into three
-    // exact bf16 planes each (see gnm_lin_split_kernel); the weight image is then the three operand planes (24 KB)
+    // SPLITD (the narrow H = 64 form): the dgrad product runs on the bf16 matrix pipe with dZ and W split into three
+    // exact bf16 planes each (see gnm_lin_split_kernel); the weight image is then the three operand planes
     float* Wt = reinterpret_cast<float*>(smem);                   // [HP][KP]: W itself (contraction index first)
     gnm_u32x4* Wp = reinterpret_cast<gnm_u32x4*>(smem);                   // SPLITD: [3][EW] operand entries instead
     float* Xs_all = reinterpret_cast<float*>(smem + L::xs_off);   // [4][32][XS]
@@ -2381,9 +2381,11 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_fused_kernel(const LbAr
 // one (not a drain that also waits for the dX stores issued after the request) every access between them is
 // unconditional: tile loads and dX stores go through buffer descriptors that clip rows past N, and the first tile is
 // peeled so that the loop is entered with the same queue its back edge carries (see gnm_lin_stream_kernel).
-// The statistics variants above stay as they are: at 256 registers they have no room for a tile in flight (tried, in
-// the shared template and as a SAMEZ flavour of this kernel with the request behind the wgrad MFMAs: 31-150 spills),
-// and any restructuring of that kernel's body moved its register allocation.
+// The statistics variants above stay as they are: at 256 registers they have no room for a tile in flight in their phase
+// order (tried, in the shared template and as a SAMEZ flavour of this kernel with the request behind the wgrad MFMAs:
+// 31-150 spills), and any restructuring of that kernel's body moved its register allocation.  The one the step runs,
+// SAMEZ at K = H = 64, is pipelined in a kernel of its own with the epilogue IN FRONT of the weight-gradient product,
+// which frees the dX accumulators before the request: gnm_linear_bwd_pipe_sz_kernel below.
 // ---------------------------------------------------------------------------------
 // SPLITD (K = H = 64): the dgrad product on the bf16 matrix pipe, dZ and W as three exact bf16 planes each (see
 // gnm_lin_split_kernel).  wgrad keeps the fp32 instruction: on the bf16 pipe as well (a separate kernel, batch row as
@@ -2593,6 +2595,252 @@ static int launch_lb_pipe(const LbArgs& a, int grid, hipStream_t s) {
     return GNM_OK;
 }
 
+// ---------------------------------------------------------------------------------
+// The SAMEZ + SPLITD form of gnm_linear_bwd_fused_kernel (K = H = 64, the second Linear of every MLP: five launches of
+// the headline step), software-pipelined across tiles like the kernel above.  What makes room for a G / Z tile in
+// flight is the phase order: the epilogue (ReLU mask of the lower BatchNorm, its two sums, the dX stores) runs straight
+// behind dgrad, IN FRONT of the weight-gradient product, so the 32 dX accumulators are dead when the next tile is
+// requested and the product runs with  wacc 64 + xv 32 + G/Z in flight 64  live.  The dZ image is still needed by that
+// product, so dX is not transposed through it but through a second, 16-row image per wave: 16 rows at a time, with the
+// 16-byte row-contiguous stores of the other kernels (76 KB of LDS per workgroup: two still share a CU).  (4-byte buffer
+// stores straight from the accumulators -- one instruction = two 128-byte row segments, no second image -- came out
+// 2-3 us per launch behind in the step and were not consistently ahead of the unpipelined kernel: profiles/linbwd_pipeline_ab.md.)
+// Between the next-tile request and its wait (the top of the next tile) the wave issues no vector-memory operation at
+// all, so that wait is a plain drain; X of a tile is requested in the accumulator row order (SAMEZ's contraction order)
+// through the tile's descriptor, which returns 0 for rows past N (their dZ is 0 and they are kept out of the sums).
+// Every fp32 sum keeps the order of the unpipelined form it replaces (gnm_linear_bwd_fused_kernel<2, 2, true, false,
+// true, true>, DESIGN_HISTORY.md "Retired variants"): same tiles per wave, same MFMA sequence into wacc, cs1 / cs2 added
+// c-major, r ascending -- the results are that kernel's bit for bit.  256 registers, no scratch.
+// Not here: the weight gradient on the bf16 pipe (gnm_linear_bwd_rz_kernel's 48 instructions: 84-228 bytes of scratch in
+// three arrangements, never launched); the X request in front of the dZ phase (no faster, paired); GNM_LSTAMP stamps
+// (their guarded stores turn the counted waits into drains: a stamped build ran 152 us against 94).
+// ---------------------------------------------------------------------------------
+struct LbSzLds {
+    using L = LbLds<2, 2, true, true>;
+    static constexpr size_t half_off = L::body;                   // [4 waves][16][XS]
+    static constexpr size_t body = L::body + (size_t)4 * 16 * L::XS * 4;
+    static constexpr size_t total = body > lb_dump_bytes(2, 2, 4) ? body : lb_dump_bytes(2, 2, 4);
+    static_assert(total <= 80 * 1024, "two workgroups share a CU");
+};
+__global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_sz_kernel(const LbArgs p) {
+    constexpr int KT = 2, HT = 2;
+    using L = LbLds<KT, HT, true, true>;
+    constexpr int KP = L::KP, HP = L::HP, XS = L::XS, EW = L::EW;
+    constexpr int H4 = HP / 4;
+    constexpr int NLD = (32 * H4) / 64;
+    constexpr int RSTEP = 64 / H4;
+    constexpr int O4 = KP / 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    gnm_u32x4* Wp = reinterpret_cast<gnm_u32x4*>(smem);           // [3][EW] bf16 operand entries of W
+    float* Xs_all = reinterpret_cast<float*>(smem + L::xs_off);   // [4][32][XS]
+    float* coef = reinterpret_cast<float*>(smem + L::coef_off);   // [5][HP]
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 31, h = lane >> 5;
+    float* Xs = Xs_all + wave * 32 * XS;
+    float* Hs = reinterpret_cast<float*>(smem + LbSzLds::half_off) + wave * 16 * XS;   // the dX half image
+    lin_stage_planes<KT, 32, true, false>(Wp, EW, p.W, p.ldw, 0, tid, 256);
+    lb_stage_coef<HP, false>(coef, p.mean, p.rstd, p.cA, p.m1, p.m2, nullptr, tid, 256);
+    const int c4 = lane % H4, lrow0 = lane / H4;
+    float psc[KT], psh[KT], cmu[KT], crs[KT], cs1[KT], cs2[KT];   // this lane's columns 32b + i: prologue = lower BatchNorm
+#pragma unroll
+    for (int b = 0; b < KT; ++b) {
+        psc[b] = p.pro_scale ? p.pro_scale[32 * b + i] : 1.f;
+        psh[b] = p.pro_scale ? p.pro_shift[32 * b + i] : 0.f;
+        cmu[b] = p.s_mean[32 * b + i];
+        crs[b] = p.s_rstd[32 * b + i];
+        cs1[b] = 0.f; cs2[b] = 0.f;
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);           // vmcnt(0): nothing from the preamble is pending inside the tile loop
+    __syncthreads();
+    f32x16 wacc[HT][KT];
+#pragma unroll
+    for (int a = 0; a < HT; ++a)
+#pragma unroll
+        for (int b = 0; b < KT; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) wacc[a][b][r] = 0.f;
+    float dbacc[HT];
+#pragma unroll
+    for (int a = 0; a < HT; ++a) dbacc[a] = 0.f;
+
+    const int ntiles = (p.N + 31) / 32;
+    const int tstride = gridDim.x * 4;
+    const int gz_voff_g = (lrow0 * p.ldg + 4 * c4) * 4, gz_step_g = RSTEP * p.ldg * 4;
+    const int gz_voff_z = (lrow0 * p.ldz + 4 * c4) * 4, gz_step_z = RSTEP * p.ldz * 4;
+    const int x_voff = (4 * h * p.ldx + i) * 4;                   // X[r0 + (s & 3) + 8 (s >> 2) + 4 h][32 b + i]
+    const int out_voff = ((lane / O4) * p.lda + 4 * (lane % O4)) * 4;   // dX: 16-byte chunk lane % O4 of the half image's row lane / O4
+
+    gnm_u32x4 g4[NLD], z4[NLD];
+    auto load_gz = [&](int tile) {
+        const long long row0 = (long long)tile * 32;
+        const long long rows = min((long long)p.N - row0, 32LL);
+        const __amdgpu_buffer_rsrc_t rg = gnm_tile_rsrc(p.G + row0 * p.ldg, rows, p.ldg, HP);
+        const __amdgpu_buffer_rsrc_t rz = gnm_tile_rsrc(p.Z + row0 * p.ldz, rows, p.ldz, HP);
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            g4[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, gz_voff_g, j * gz_step_g, 0);
+            z4[j] = __builtin_amdgcn_raw_buffer_load_b128(rz, gz_voff_z, j * gz_step_z, 0);
+        }
+    };
+    auto do_tile = [&](int t, int t_next) {
+        const int r0 = t * 32;
+        const int rows = min(p.N - r0, 32);
+        // ---- 1. dZ tile -> LDS (rows past N are zero: they must not contribute) ----------
+        const float4 mu = *reinterpret_cast<const float4*>(coef + 4 * c4);
+        const float4 rs = *reinterpret_cast<const float4*>(coef + HP + 4 * c4);
+        const float4 ca = *reinterpret_cast<const float4*>(coef + 2 * HP + 4 * c4);
+        const float4 a1 = *reinterpret_cast<const float4*>(coef + 3 * HP + 4 * c4);
+        const float4 a2 = *reinterpret_cast<const float4*>(coef + 4 * HP + 4 * c4);
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int lrow = lrow0 + j * RSTEP;
+            const float4 gj = __builtin_bit_cast(float4, g4[j]), zj = __builtin_bit_cast(float4, z4[j]);
+            float4 d;
+            d.x = ca.x * (gj.x - a1.x - (zj.x - mu.x) * rs.x * a2.x);
+            d.y = ca.y * (gj.y - a1.y - (zj.y - mu.y) * rs.y * a2.y);
+            d.z = ca.z * (gj.z - a1.z - (zj.z - mu.z) * rs.z * a2.z);
+            d.w = ca.w * (gj.w - a1.w - (zj.w - mu.w) * rs.w * a2.w);
+            if (lrow >= rows) d = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(Xs + lrow * XS + 4 * c4) = d;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // ---- 2. X of the tile, in the accumulator row order: xv[s] sits on the rows of dacc[.][s]; in flight during dgrad
+        float xv[16][KT];
+        {
+            const __amdgpu_buffer_rsrc_t rx = gnm_tile_rsrc(p.X + (size_t)r0 * p.ldx, rows, p.ldx, KP);
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+#pragma unroll
+                for (int b = 0; b < KT; ++b)
+                    xv[s][b] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                        rx, x_voff, (((s & 3) + 8 * (s >> 2)) * p.ldx + 32 * b) * 4, 0));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- 3. dX = dZ W ------------------------------------------------------------------
+        f32x16 dacc[KT];
+#pragma unroll
+        for (int c = 0; c < KT; ++c)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dacc[c][r] = 0.f;
+        lin_dgrad_split<KT, HP>(dacc, Xs, XS, Wp, i, h, lane);
+        // ---- 4. ReLU mask of the lower BatchNorm and its backward sums on the accumulator, dX out ----------------
+        {
+            const __amdgpu_buffer_rsrc_t rd = gnm_tile_rsrc(p.dA + (size_t)r0 * p.lda, rows, p.lda, KP);
+            auto mask_sum = [&](int c, int r) {
+                const float z = xv[r][c];
+                float g = dacc[c][r];
+                if (z * psc[c] + psh[c] <= 0.f) g = 0.f;
+                if ((r & 3) + 8 * (r >> 2) + 4 * h < rows) {
+                    cs1[c] += g;
+                    cs2[c] += g * ((z - cmu[c]) * crs[c]);
+                }
+                return g;
+            };
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {                           // accumulator registers 8q .. 8q + 7 are rows 16q .. 16q + 15
+                float gq[KT][8];
+#pragma unroll
+                for (int c = 0; c < KT; ++c)
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) gq[c][r] = mask_sum(c, 8 * q + r);
+#pragma unroll
+                for (int c = 0; c < KT; ++c)
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) Hs[((r & 3) + 8 * (r >> 2) + 4 * h) * XS + 32 * c + i] = gq[c][r];
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+                for (int st = 0; st < (16 * O4) / 64; ++st) {
+                    const int idx = lane + 64 * st;
+                    const int row = idx / O4, oc = idx - row * O4;
+                    const gnm_u32x4 v = *reinterpret_cast<const gnm_u32x4*>(Hs + row * XS + 4 * oc);
+                    // (row step in the vector offset: see gnm_lin_stream_kernel)
+                    __builtin_amdgcn_raw_buffer_store_b128(v, rd, out_voff + (16 * q + (64 / O4) * st) * p.lda * 4, 0, 0);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();          // the half image has been read
+            }
+        }
+        // ---- 5. G and Z of the wave's next tile (past its last tile: empty descriptors, no traffic) ---------------
+        // (pinned between the stores and the product: left alone, the scheduler sinks the 16 loads behind the last MFMAs)
+        __builtin_amdgcn_sched_barrier(0);
+        load_gz(t_next);
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- 6. dW += dZ^T f(X), db += column sums of dZ -----------------------------------
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            float av[HT];
+            const int krow = (s & 3) + 8 * (s >> 2) + 4 * h;
+#pragma unroll
+            for (int a = 0; a < HT; ++a) av[a] = Xs[krow * XS + 32 * a + i];
+            float xf[KT];
+#pragma unroll
+            for (int b = 0; b < KT; ++b) {
+                float x = xv[s][b];
+                if (p.pro_scale) {
+                    x = x * psc[b] + psh[b];
+                    if (p.pro_relu) x = gnm_relu(x);
+                }
+                xf[b] = x;
+            }
+#pragma unroll
+            for (int a = 0; a < HT; ++a) {
+                dbacc[a] += av[a];
+#pragma unroll
+                for (int b = 0; b < KT; ++b)
+                    wacc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], xf[b], wacc[a][b], 0, 0, 0);
+            }
+        }
+        // ---- 7. everyone is done reading the dZ image ---------------------------------------
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+    {
+        int t = lin_first_tile(wave, 1, gridDim.x);
+        load_gz(t);
+        if (t < ntiles) {
+            do_tile(t, t + tstride);                  // peeled
+            for (t += tstride; t < ntiles; t += tstride) do_tile(t, t + tstride);
+        }
+    }
+
+    // ---- lower-BatchNorm sums: the two half-waves hold the same columns, then the 4 waves (fixed order) ----
+    __syncthreads();
+    double* sred = reinterpret_cast<double*>(smem);               // [4 waves][2][KP]
+#pragma unroll
+    for (int c = 0; c < KT; ++c) {
+        double d1 = (double)cs1[c], d2 = (double)cs2[c];
+        d1 += __shfl_xor(d1, 32, 64);
+        d2 += __shfl_xor(d2, 32, 64);
+        if (h == 0) {
+            sred[(wave * 2 + 0) * KP + 32 * c + i] = d1;
+            sred[(wave * 2 + 1) * KP + 32 * c + i] = d2;
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < 2 * KP; idx += 256) {
+        const int which = idx / KP, col = idx - which * KP;
+        double sum = 0.0;
+        for (int w = 0; w < 4; ++w) sum += sred[(w * 2 + which) * KP + col];
+        p.s_partial[((size_t)blockIdx.x * 2 + which) * p.K + col] = sum;
+    }
+
+    lb_combine<HT, KT, 1, false>(smem, wacc, dbacc, p.partial, p.H, p.K, 0, tid, lane, wave);
+}
+
+static int launch_lb_pipe_sz(const LbArgs& a, int grid, hipStream_t s) {
+    const size_t lds = LbSzLds::total;
+    GNM_ALLOW_FULL_LDS((&gnm_linear_bwd_pipe_sz_kernel));
+    hipLaunchKernelGGL(gnm_linear_bwd_pipe_sz_kernel, dim3(grid), dim3(256), lds, s, a);
+    GNM_CHECK_LAUNCH();
+    return GNM_OK;
+}
+
 template <int KT, int HT, bool STATS, bool NARROW = false, bool SAMEZ = false, bool SPLITD = false>
 static int launch_lb(const LbArgs& a, int grid, hipStream_t s) {
     const size_t lds = LbLds<KT, HT, SPLITD, false>::total;
@@ -2618,11 +2866,12 @@ static int launch_lb(const LbArgs& a, int grid, hipStream_t s) {
 //    product runs as 48 bf16 instructions instead of 64 fp32 ones (a quarter of the matrix-pipe time);
 //  * only dgrad still needs the transpose: dZ goes through the wave's LDS image once, row-wise out;
 //  * G AND the row-wise X fragments of the wave's next tile are requested before the weight-gradient product (the
-//    registers Z used to occupy) -- the statistics form above had no room for that;
+//    registers Z used to occupy) -- the statistics form had no room for that in its phase order (its pipelined
+//    kernel, gnm_linear_bwd_pipe_sz_kernel, moves the epilogue in front of this product to make it);
 //  * eight waves per workgroup share the two weight images (forward orientation for Z, k-major for dgrad: 48 KB) and the
 //    workgroup writes TWO rows of partials (waves 0-3, 4-7), so gnm_linear_bwd_grid(N) rows exist as before.
-// No lower BatchNorm statistics: the second Linear of an MLP keeps gnm_linear_bwd_fused_kernel (DESIGN_HISTORY.md,
-// "Retired variants").
+// No lower BatchNorm statistics: the second Linear of an MLP keeps the stored-Z pass, gnm_linear_bwd_pipe_sz_kernel
+// (DESIGN_HISTORY.md, "Retired variants").
 // ---------------------------------------------------------------------------------
 // What gnm_linear_bwd_rz_kernel and its narrow form share beyond the helpers above.
 // G of a tile in the accumulator layout (lane = column 32 a + i, rows (r & 3) + 8 (r >> 2) + 4 h): 4-byte loads clipped by
@@ -3083,8 +3332,7 @@ extern "C" int gnm_linear_bwd_fused(const float* G, int ldg, const float* Z, int
     // the second Linear of an MLP: the lower BatchNorm's input is this Linear's input and its affine is the prologue
     const bool samez = sZ && sZ == X && ldsz == ldx && s_scale == pro_scale && s_shift == pro_shift && pro_relu;
     if (sZ && KT == 2 && HT == 2)
-        rc = samez ? (lin_no_split() ? launch_lb<2, 2, true, false, true>(a, grid, s)
-                                     : launch_lb<2, 2, true, false, true, true>(a, grid, s))
+        rc = samez ? (lin_no_split() ? launch_lb<2, 2, true, false, true>(a, grid, s) : launch_lb_pipe_sz(a, grid, s))
                    : launch_lb<2, 2, true>(a, grid, s);
     if (rc != GNM_OK || !dW) return rc;      // dW = NULL: the partials stay in `workspace` for gnm_reduce_partials_multi
     return launch_reduce_partials(workspace, grid, H, K, 0, dW, lddw, db, s);
