@@ -1,5 +1,5 @@
 // The building blocks of the eval-mode kernels whose workgroup (4 waves, 256 threads) owns one 32-row block of a graph
-// (evallayer.hip, occlusion.hip, lesion.hip, saliency.hip, edgesal.hip; aggm.hip and evalfwd.hip take single pieces):
+// (evallayer.hip, occlusion.hip, lesion.hip, disconnect.hip, saliency.hip, edgesal.hip; aggm.hip and evalfwd.hip take single pieces):
 //   * the product of the block's adjacency BITS with rows of activations read from global memory (rb_bits_product and
 //     what feeds it): the activations are the A operand, "eight consecutive rows of one column per lane", split in
 //     registers into three exact bf16 planes; the bits are the B operand, expanded through a 16-entry LDS table;
@@ -9,7 +9,7 @@
 //   * the forward MLP on the 32 x F tile in LDS (rb_mlp_*): folded BatchNorm, six-term split Linears (gnm_split.h);
 //   * the readout sum and the classifier head of the finish kernels;
 //   * the layer arguments that the virtual-graph forwards share (RbVirtualArgs; their finish body and host driver,
-//     gnm_virtual_forward, are defined in occlusion.hip and used by lesion.hip too).
+//     gnm_virtual_forward, are defined in occlusion.hip and used by lesion.hip and disconnect.hip too).
 // Each kernel keeps what is its own: how it stages the bits, which rows it multiplies, its epilogue.  saliency.hip
 // addresses its rows differently (the row offset in the vector offset) and keeps its own product call.
 #pragma once
@@ -71,6 +71,41 @@ __device__ __forceinline__ int rb_stage_bits_masked(unsigned (*bitsw)[256], cons
     return pc;
 }
 
+// rb_stage_bits with a keep mask that depends on the ROW (disconnect.hip: the edges between two node sets A and B cut).
+// ka / kb: the virtual graph's two masks of the half-row layout, the complements of A and of B within n (zero at
+// columns >= n).  Row r = 32 rb + i is in A iff its own column is clear in ka, in B iff clear in kb; its words are ANDed
+// with kb if it is in A and with ka if it is in B -- both, or neither.  The choice is per lane, so each mask word is
+// selected against an all-ones word (two v_cndmask and two v_and per staged word) rather than taken as one operand.
+// Rows at or past n (zero rows of the bit adjacency) are in neither set: they stage their words as rb_stage_bits does.
+// Returns the popcount of this lane's masked half row, as rb_stage_bits_masked.
+__device__ __forceinline__ int rb_stage_bits_cut(unsigned (*bitsw)[256], const uint32_t* gbits, const uint32_t* ka,
+                                                 const uint32_t* kb, int rb, int i, int h, int HPW, int n, int tid) {
+    const int r = rb * 32 + i;
+    const gnm_u32x4* rp = reinterpret_cast<const gnm_u32x4*>(gbits + (size_t)r * (2 * HPW) + h * HPW);
+    const int rc = min(r, n - 1);
+    const bool in_a = r < n && rb_row_bit(ka, HPW, rc) == 0u;
+    const bool in_b = r < n && rb_row_bit(kb, HPW, rc) == 0u;
+    const uint32_t* pa = ka + h * HPW;
+    const uint32_t* pb = kb + h * HPW;
+    const gnm_u32x4 z4 = {0u, 0u, 0u, 0u};
+    const gnm_u32x4 a0 = rp[0];
+    const gnm_u32x4 a1 = HPW > 4 ? rp[1] : z4;
+    int pc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned ma0 = pa[j], mb0 = pb[j];                  // loaded whatever the row is in: no divergent load
+        const unsigned w0 = a0[j] & (in_a ? mb0 : ~0u) & (in_b ? ma0 : ~0u);
+        unsigned w1 = 0u;
+        if (HPW > 4) {                                            // (workgroup-uniform)
+            const unsigned ma1 = pa[4 + j], mb1 = pb[4 + j];
+            w1 = a1[j] & (in_a ? mb1 : ~0u) & (in_b ? ma1 : ~0u);
+        }
+        bitsw[j][tid] = w0; bitsw[4 + j][tid] = w1;
+        pc += __popc(w0) + __popc(w1);
+    }
+    return pc;
+}
+
 // The 8 bits of (row 32 rb + i, columns 16 s + 8 h ..) as a bf16x8 operand: byte s & 3 of word s >> 2 of the lane's half row
 __device__ __forceinline__ gnm_bf16x8 rb_bits_operand(const char* lut, const unsigned (*bitsw)[256], int s, int tid) {
     const unsigned pkw = bitsw[s >> 2][tid];
@@ -123,7 +158,7 @@ __device__ __forceinline__ void rb_acc_to_part_cols(float (*part)[32][33], int w
 }
 
 // The aggregation stage of a forward layer kernel: this wave's share of (the block's bits, already staged in bitsw by
-// rb_stage_bits / rb_stage_bits_masked) x (rows 0 .. n - 1 of `base`, row stride ld floats, columns 0 .. width - 1; NCA
+// rb_stage_bits / rb_stage_bits_masked / rb_stage_bits_cut) x (rows 0 .. n - 1 of `base`, row stride ld floats, columns 0 .. width - 1; NCA
 // column tiles, the rest of the waves split k) -> part[wave].  Holds the barrier after which the lut, the staged bits
 // and whatever else the caller wrote to LDS before the call are visible.
 __device__ __forceinline__ void rb_rows_product(float (*part)[32][33], const char* lut, const unsigned (*bitsw)[256],
@@ -289,8 +324,8 @@ __device__ __forceinline__ float rb_readout_head(const float* gfl, const long lo
     return wave_sum(acc);
 }
 
-// ---- the virtual-graph forwards (occlusion.hip, lesion.hip) -----------------------------------------------------------
-// What their layer kernels' arguments share (OcArgs and LsArgs derive from it).  The entry fills what holds for the whole
+// ---- the virtual-graph forwards (occlusion.hip, lesion.hip, disconnect.hip) ------------------------------------------
+// What their layer kernels' arguments share (OcArgs, LsArgs and DcArgs derive from it).  The entry fills what holds for the whole
 // call; gnm_virtual_forward (occlusion.hip) checks that and fills the rest per layer.
 struct RbVirtualArgs {
     const uint32_t* adj_bits; const int64_t* b_bits_off; const int32_t* node_off;
@@ -308,3 +343,14 @@ struct RbVirtualArgs {
     float* Hout;                                  // [rows, H]
     float* rpart;                                 // [V][wmax][H]: this layer's readout shares
 };
+
+// Which finish kernel gnm_virtual_forward launches: one body (oc_finish) under the name of the forward it serves
+enum RbFinish { kRbFinishOcclusion = 0, kRbFinishLesion = 1, kRbFinishDisconnect = 2 };
+
+// occlusion.hip: the scratch size, and the checks, layer loop and finish launches the virtual-graph forwards share
+extern "C" long long gnm_occlusion_scratch_floats(long long rows, long long V, int n_max, int H, int L);
+extern "C" __attribute__((visibility("hidden"))) int gnm_virtual_forward(
+    RbVirtualArgs* a, int B, int n_max, long long V, long long rows, int C, const int* classes_host, int n_classes,
+    int graph_avg, RbFinish finish, const int32_t* kept, float* scratch, float* out, long long ldo, hipStream_t s,
+    bool (*own_ok)(const void* ctx), void (*launch)(const void* ctx, bool first, unsigned grid, hipStream_t s),
+    const void* ctx);

@@ -153,15 +153,6 @@ __global__ void __launch_bounds__(256) gnm_lesion_pack_kernel(const uint8_t* rem
     }
 }
 
-// occlusion.hip: the scratch size, and the checks, layer loop and finish launches both forwards share
-extern "C" long long gnm_occlusion_scratch_floats(long long rows, long long V, int n_max, int H, int L);
-extern "C" int gnm_virtual_forward(RbVirtualArgs* a, int B, int n_max, long long V, long long rows, int C,
-                                   const int* classes_host, int n_classes, int graph_avg, const int32_t* kept,
-                                   float* scratch, float* out, long long ldo, hipStream_t s,
-                                   bool (*own_ok)(const void* ctx),
-                                   void (*launch)(const void* ctx, bool first, unsigned grid, hipStream_t s),
-                                   const void* ctx);
-
 // Floats of scratch gnm_lesion needs: gnm_occlusion's with rows = sum of n_g over the virtual graphs.
 extern "C" long long gnm_lesion_scratch_floats(long long rows, long long V, int n_max, int H, int L) {
     return gnm_occlusion_scratch_floats(rows, V, n_max, H, L);
@@ -203,7 +194,7 @@ extern "C" int gnm_lesion(const uint32_t* adj_bits, const int64_t* b_bits_off, c
     a.masks = masks; a.mstride = mstride;
     k.kept = kept; k.kept_host = kept_host; k.vn_host = vn_host; k.n_max = n_max; k.V = V;
     return gnm_virtual_forward(
-        &a, B, n_max, V, rows, C, classes_host, n_classes, graph_avg, kept, scratch, out, ldo,
+        &a, B, n_max, V, rows, C, classes_host, n_classes, graph_avg, kRbFinishLesion, kept, scratch, out, ldo,
         reinterpret_cast<hipStream_t>(stream),
         [](const void* ctx) {
             const Call& k = *static_cast<const Call*>(ctx);

@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(256) gnm_occlusion_layer_kernel(const OcArgs p
     rb_readout_share(Tin, H, tid, p.rpart + ((size_t)q * p.wmax + rb) * H);
 }
 
-// The finish launch of both virtual-graph forwards (gnm_virtual_forward)
+// The finish launch of the virtual-graph forwards (gnm_virtual_forward)
 struct OcFinArgs {
     const int32_t* node_off; const int32_t* vgraph;
     const int32_t* kept;                          // [V]: nodes left in virtual graph q, or null: n - 1
@@ -154,9 +154,10 @@ __device__ __forceinline__ void oc_finish(const OcFinArgs& p) {
         if (lane == 0) p.out[(size_t)ci * p.ldo + q] = acc;
     }
 }
-// One finish under the name of either forward (profiles and the code-object tests know a forward's launches by its name)
+// One finish under the name of each forward (profiles and the code-object tests know a forward's launches by its name)
 __global__ void __launch_bounds__(256) gnm_occlusion_finish_kernel(const OcFinArgs p) { oc_finish(p); }
 __global__ void __launch_bounds__(256) gnm_lesion_finish_kernel(const OcFinArgs p) { oc_finish(p); }
+__global__ void __launch_bounds__(256) gnm_disconnect_finish_kernel(const OcFinArgs p) { oc_finish(p); }
 
 // Floats of scratch gnm_occlusion / gnm_lesion need: two [rows, H] activation arrays (rows = sum of n_g^2 over the batch
 // / of n_g over the virtual graphs) and the readout shares [L][V][ceil(n_max / 32)][H] (occlusion: V = N virtual graphs).
@@ -165,13 +166,13 @@ extern "C" long long gnm_occlusion_scratch_floats(long long rows, long long V, i
     return 2 * rows * H + (long long)L * V * ((n_max + 31) / 32) * H;
 }
 
-// What gnm_occlusion and gnm_lesion share on the host: the checks of the arguments both have (`a` holds the call's own,
-// filled by the entry; own_ok(ctx): the entry's further BAD_ARG conditions, asked where those return), the split of
-// `scratch`, the ping-pong layer launches through launch(ctx, first, grid, stream) -- `a` is part of *ctx -- and the
-// finish launches, 8 classes at a time.  kept: OcFinArgs'.
+// What gnm_occlusion, gnm_lesion and gnm_disconnect share on the host: the checks of the arguments all have (`a` holds
+// the call's own, filled by the entry; own_ok(ctx): the entry's further BAD_ARG conditions, asked where those return),
+// the split of `scratch`, the ping-pong layer launches through launch(ctx, first, grid, stream) -- `a` is part of *ctx
+// -- and the finish launches under the name `finish` says, 8 classes at a time.  kept: OcFinArgs'.
 extern "C" __attribute__((visibility("hidden"))) int gnm_virtual_forward(
     RbVirtualArgs* a, int B, int n_max, long long V, long long rows, int C, const int* classes_host, int n_classes,
-    int graph_avg, const int32_t* kept, float* scratch, float* out, long long ldo, hipStream_t s,
+    int graph_avg, RbFinish finish, const int32_t* kept, float* scratch, float* out, long long ldo, hipStream_t s,
     bool (*own_ok)(const void* ctx), void (*launch)(const void* ctx, bool first, unsigned grid, hipStream_t s),
     const void* ctx) {
     const int H = a->H, L = a->L, m = a->m;
@@ -207,8 +208,10 @@ extern "C" __attribute__((visibility("hidden"))) int gnm_virtual_forward(
         f.ncls = n_classes - c0 < kOcMaxClasses ? n_classes - c0 : kOcMaxClasses;
         for (int k = 0; k < f.ncls; ++k) f.cls[k] = classes_host[c0 + k];
         f.out = out + (size_t)c0 * ldo; f.ldo = ldo;
-        hipLaunchKernelGGL(kept ? gnm_lesion_finish_kernel : gnm_occlusion_finish_kernel, dim3((unsigned)V), dim3(256),
-                           (size_t)L * H * 4, s, f);
+        void (*fin)(const OcFinArgs) = finish == kRbFinishDisconnect ? gnm_disconnect_finish_kernel
+                                       : finish == kRbFinishLesion   ? gnm_lesion_finish_kernel
+                                                                     : gnm_occlusion_finish_kernel;
+        hipLaunchKernelGGL(fin, dim3((unsigned)V), dim3(256), (size_t)L * H * 4, s, f);
         GNM_CHECK_LAUNCH();
     }
     return GNM_OK;
@@ -229,7 +232,7 @@ extern "C" int gnm_occlusion(const uint32_t* adj_bits, const int64_t* b_bits_off
     a.average = average; a.self_loop = self_loop; a.bn_eps = bn_eps; a.eps = eps; a.table = table;
     a.rowptr = rowptr; a.b_rp_off = b_rp_off; a.S = S; a.lds = lds;
     return gnm_virtual_forward(
-        &a, B, n_max, V, rows, C, classes_host, n_classes, graph_avg, nullptr, scratch, out, ldo,
+        &a, B, n_max, V, rows, C, classes_host, n_classes, graph_avg, kRbFinishOcclusion, nullptr, scratch, out, ldo,
         reinterpret_cast<hipStream_t>(stream),
         [](const void* ctx) {
             const OcArgs& o = *static_cast<const OcArgs*>(ctx);

@@ -1061,6 +1061,74 @@ def lesion_hip(spec, batch, X, P, classes, removed, vgraph, out=None):
     return out
 
 
+# csrc/disconnect.hip takes what csrc/lesion.hip takes, for the same reasons (no node is removed, but the virtual graphs
+# run through the same row-block forward): one predicate, one set of strings
+disconnect_decline = lesion_decline
+
+
+def disconnect_hip(spec, batch, X, P, classes, in_a, in_b, vgraph, out=None):
+    """The eval-mode class scores of edge-cut copies of the graphs of a batch (csrc/disconnect.hip, include/gnm_hip.h
+    gnm_disconnect): out[ci, q] = c_logit[classes[ci]] of graph vgraph[q] of the batch without the edges (u, v) with
+    (in_a[q, u] and in_b[q, v]) or (in_b[q, u] and in_a[q, v]); every node and feature row stays.  in_a, in_b: host
+    uint8 / bool arrays [V, >= n_max] (entries past a graph's n are ignored); vgraph: V host ints in [0, B).  Per batch
+    XW = X W0^T (the split-precision Linear, any input width); then, per chunk of whole virtual graphs whose scratch fits
+    LESION_SCRATCH_BYTES, ONE gnm_lesion_pack launch over the chunk's A rows followed by its B rows (the two keep masks),
+    L layer launches and the finish launch.  Nothing is read back: the readout runs over n, which the host knows.  The
+    shapes disconnect_decline takes.  Parameters, buffers and the numpy RNG are not touched; the device parameter table
+    is eval_forward_fused's.  Returns a float32 [len(classes), V] tensor (`out` when given)."""
+    d = _launch_dims(spec, batch, X, P)
+    dev, L, m, N, B, H, Cn, F0, X = d.dev, d.L, d.m, d.N, d.B, d.H, d.Cn, d.F0, d.X
+    in_a = np.ascontiguousarray(np.asarray(in_a) != 0, dtype=np.uint8)
+    in_b = np.ascontiguousarray(np.asarray(in_b) != 0, dtype=np.uint8)
+    vgraph = np.ascontiguousarray(vgraph, dtype=np.int32)
+    Vt = int(vgraph.shape[0])
+    nm = int(batch.n_max)
+    for name, a in (("in_a", in_a), ("in_b", in_b)):
+        if a.ndim != 2 or a.shape[0] != Vt or a.shape[1] < nm:
+            raise GnmError("%s must be [%d, >= %d], got %s" % (name, Vt, nm, list(a.shape)))
+    if in_a.shape != in_b.shape:
+        raise GnmError("in_a and in_b must have one shape, got %s and %s" % (list(in_a.shape), list(in_b.shape)))
+    if Vt and (vgraph.min() < 0 or vgraph.max() >= B):
+        raise GnmError("vgraph entries must be graphs of the batch, 0 .. %d" % (B - 1))
+    out = _out_array(out, (len(classes), Vt), dev)
+    cls = (C.c_int * len(classes))(*[int(c) for c in classes])
+    offs = np.asarray(batch.node_off_host, dtype=np.int64)
+    vn = np.diff(offs)[vgraph].astype(np.int32)             # node count of each virtual graph
+    cum = np.concatenate([[0], np.cumsum(vn, dtype=np.int64)])      # activation rows before virtual graph q
+    with torch.no_grad(), _stream_scope(dev):
+        table = _eval_table(spec, P, dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        XW = _first_linear_product(X, P, m, N, F0, H)
+        up = batch.arena._upload
+
+        def floats(q0, q1):
+            return int(lib.gnm_disconnect_scratch_floats(int(cum[q1] - cum[q0]), q1 - q0, int(vn[q0:q1].max()), H, L))
+        for q0, q1 in _runs_within(Vt, floats, LESION_SCRATCH_BYTES):
+            V, nc = q1 - q0, np.ascontiguousarray(vn[q0:q1])
+            n_max, rows = int(nc.max()), int(cum[q1] - cum[q0])
+            mstride = int(lib.gnm_lesion_mask_words(n_max))
+            vg2 = up(torch.as_tensor(np.concatenate([vgraph[q0:q1], vgraph[q0:q1]])))       # A's rows, then B's (gnm_disconnect reads the first V)
+            vrow_off = up(torch.as_tensor(cum[q0:q1] - cum[q0]))
+            rem = up(torch.as_tensor(np.concatenate([in_a[q0:q1], in_b[q0:q1]])))
+            kept = up(torch.as_tensor(nc))                  # the readout's divisor: every node stays
+            masks = torch.empty((2 * V, mstride), dtype=torch.int32, device=dev)
+            counts = torch.empty(2 * V, dtype=torch.int32, device=dev)      # gnm_lesion_pack's kept counts: not used
+            check(lib.gnm_lesion_pack(rem.data_ptr(), rem.stride(0), vg2.data_ptr(), batch.node_off.data_ptr(), B,
+                                      n_max, 2 * V, mstride, masks.data_ptr(), counts.data_ptr(), _stream()),
+                  "gnm_lesion_pack")
+            scratch = torch.empty(floats(q0, q1), **f32)
+            dst = out[:, q0:q1]
+            with _timed("disconnect_hip", B=B, N=V, H=H, L=L):
+                check(lib.gnm_disconnect(batch.arena.bits.buf.data_ptr(), batch.bits_off.data_ptr(),
+                                         batch.node_off.data_ptr(), vg2.data_ptr(), vrow_off.data_ptr(),
+                                         masks.data_ptr(), masks[V:].data_ptr(), mstride, kept.data_ptr(),
+                                         nc.ctypes.data, B, n_max, V, rows, XW.data_ptr(), XW.stride(0), H, L, m, Cn,
+                                         cls, len(classes), int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg),
+                                         BN_EPS, table.data_ptr(), d.eps, scratch.data_ptr(), dst.data_ptr(),
+                                         out.stride(0), _stream()), "gnm_disconnect")
+    return out
+
+
 # integrated_gradients_hip's device arrays per chunk of source graphs stay under this many bytes: the virtual batch's
 # forward keeps every Linear's z and every layer's aggregation, (m L + L - 1) K N H floats, next to 4 K N H of scratch.
 # K = 32, 8 graphs of 400 nodes, H = 64, m = 2, L = 5: 0.26 GB of z, 0.47 GB in all.

@@ -1,5 +1,6 @@
 """Host side of GIN_InfoMaxReg.lesion() / deletion_curve(): the removed-node sets of a deletion curve from a per-ROI
-ranking, and the curve's area.  numpy only; nothing here touches the device."""
+ranking, and the curve's area; and of disconnect() / disconnection_matrix(): the set pairs of a network labelling and
+the number of edges a cut removes.  numpy only; nothing here touches the device."""
 import numpy as np
 
 ORDERS = ("descending", "ascending")
@@ -52,6 +53,45 @@ def masks_from_ranking(ranking, fractions, order="descending"):
         masks.append(pos[None, :] < cnt[:, None])
         counts.append(cnt)
     return masks, counts
+
+
+def pair_sets(labels, K=None):
+    """The set pairs of a network-by-network disconnection matrix.  labels: an int [n] vector, entry r the network id
+    of node r in 0 .. K - 1, or -1 for a node of no network (it is in no set); K: the number of networks, default
+    max(labels) + 1.  Returns (a, b, pairs): bool [S, n] arrays and an int64 [S, 2] array, S = K (K + 1) / 2, the
+    unordered pairs (p, q), p <= q, in the order (0, 0), (0, 1), ..., (0, K - 1), (1, 1), ...; a[s] = network p,
+    b[s] = network q.  Pair (p, p) is the cut inside network p."""
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or lab.dtype.kind not in "iu":
+        raise ValueError("labels must be an int [n] vector, got dtype %s shape %s" % (lab.dtype, list(lab.shape)))
+    lab = lab.astype(np.int64)
+    if lab.size and lab.min() < -1:
+        raise ValueError("labels must be network ids >= 0, or -1 for no network")
+    top = int(lab.max()) + 1 if lab.size else 0
+    if K is None:
+        K = top
+    K = int(K)
+    if K < top:
+        raise ValueError("labels hold network %d but K = %d" % (top - 1, K))
+    pairs = np.array([(p, q) for p in range(K) for q in range(p, K)], dtype=np.int64).reshape(-1, 2)
+    member = lab[None, :] == np.arange(K, dtype=np.int64)[:, None]        # [K, n]; -1 matches none
+    return member[pairs[:, 0]], member[pairs[:, 1]], pairs
+
+
+def cut_edge_counts(edge_mat, a, b):
+    """How many columns (u, v) of edge_mat [2, E] each cut removes: those with (a[s, u] and b[s, v]) or (b[s, u] and
+    a[s, v]).  a, b: bool or 0/1 [S, n].  Returns an int64 [S] array -- the size a delta is to be read against (an
+    undirected graph stored as both (u, v) and (v, u) counts both)."""
+    a = np.asarray(a) != 0
+    b = np.asarray(b) != 0
+    if a.ndim != 2 or a.shape != b.shape:
+        raise ValueError("a and b must be [S, n] arrays of one shape, got %s and %s" % (list(a.shape), list(b.shape)))
+    em = edge_mat.detach().cpu().numpy() if hasattr(edge_mat, "detach") else np.asarray(edge_mat)
+    em = em.astype(np.int64).reshape(2, -1)
+    if em.size and (em.min() < 0 or em.max() >= a.shape[1]):
+        raise ValueError("edge_mat names a node outside the %d-node masks" % a.shape[1])
+    u, v = em
+    return ((a[:, u] & b[:, v]) | (b[:, u] & a[:, v])).sum(1).astype(np.int64)
 
 
 def curve_area(scores, realised_fractions):

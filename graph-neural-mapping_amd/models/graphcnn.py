@@ -33,11 +33,12 @@ for _p in (_PKG, _HERE):
 from mlp import MLP  # noqa: E402
 from discriminator import Discriminator  # noqa: E402
 from gnm.arena import GraphArena  # noqa: E402
-from gnm.core import (DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, edge_saliency_hip,  # noqa: E402
-                      eval_forward_fused, eval_fused_ok, integrated_gradients_hip, launch_device, lesion_decline,
-                      lesion_hip, occlusion_decline, occlusion_hip, saliency_decline, saliency_hip, saliency_maps_hip)
+from gnm.core import (DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, disconnect_decline,  # noqa: E402
+                      disconnect_hip, edge_saliency_hip, eval_forward_fused, eval_fused_ok, integrated_gradients_hip,
+                      launch_device, lesion_decline, lesion_hip, occlusion_decline, occlusion_hip, saliency_decline,
+                      saliency_hip, saliency_maps_hip)
 from gnm.intgrad import quadrature  # noqa: E402
-from gnm.lesion import curve_area, default_fractions, masks_from_ranking  # noqa: E402
+from gnm.lesion import curve_area, default_fractions, masks_from_ranking, pair_sets  # noqa: E402
 
 __all__ = ["GIN_InfoMaxReg", "GraphCNN", "MLP", "Discriminator"]
 
@@ -604,6 +605,15 @@ class GIN_InfoMaxReg(nn.Module):
         train / eval mode is restored on exit."""
         single, classes = self._interpret_args("lesion", graphs, cls, batch_size)
         sets = self._lesion_sets(graphs, rois)
+        return self._set_scores(graphs, single, classes, batch_size, [int(s.shape[0]) for s in sets], return_scores,
+                                lambda chunk, batch, P, i0: self._lesion_batch(chunk, batch, P, classes,
+                                                                               sets[i0:i0 + len(chunk)]))
+
+    def _set_scores(self, graphs, single, classes, batch_size, counts, return_scores, run_batch):
+        """The batching and the result layout lesion() and disconnect() share: eval mode with the previous mode restored
+        on exit, chunks of batch_size graphs -- run_batch(chunk, batch, P, i0) returns (base [len(classes), B], scores
+        [len(classes), sum of S_g over the chunk]) of the chunk that starts at graph i0 -- then delta = base - scores
+        as a [.., len(graphs), S] tensor when every graph has S = counts[g] sets and as per-graph lists otherwise."""
         was_training = self.training
         self.eval()
         try:
@@ -613,14 +623,13 @@ class GIN_InfoMaxReg(nn.Module):
             bases, parts = [], []
             for i0 in range(0, len(graphs), batch_size):
                 chunk = graphs[i0:i0 + batch_size]
-                base, les = self._lesion_batch(chunk, self._batch_of(chunk), P, classes, sets[i0:i0 + len(chunk)])
+                base, les = run_batch(chunk, self._batch_of(chunk), P, i0)
                 bases.append(base)
                 parts.append(les)
         finally:
             self.train(was_training)
         base = torch.cat(bases, 1)                          # [len(classes), len(graphs)]
         flat = torch.cat(parts, 1)                          # [len(classes), sum of S_g]
-        counts = [int(s.shape[0]) for s in sets]
         if all(k == counts[0] for k in counts):
             les = flat.view(len(classes), len(graphs), counts[0])
             delta = base.unsqueeze(-1) - les
@@ -634,59 +643,75 @@ class GIN_InfoMaxReg(nn.Module):
         return (delta, base, les) if return_scores else delta
 
     @staticmethod
-    def _lesion_sets(graphs, rois):
-        """lesion()'s `rois` as one bool [S_g, n_g] array per graph, checked"""
+    def _shared_mask(rois):
+        """whether `rois` is ONE [S, n] mask for all graphs (an array, a tensor or nested rows), not a per-graph list"""
+        return torch.is_tensor(rois) or isinstance(rois, np.ndarray) or (
+            isinstance(rois, (list, tuple)) and len(rois) > 0 and np.ndim(rois[0]) == 1 and not torch.is_tensor(rois[0]))
+
+    @staticmethod
+    def _lesion_sets(graphs, rois, method="lesion", name="rois", proper=True):
+        """lesion()'s `rois` (disconnect()'s `a` / `b`: `method`, `name`) as one bool [S_g, n_g] array per graph,
+        checked; proper: a set must leave a node of its graph (a lesion; a cut may name every node)"""
         def as_mask(a, what):
             a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
             if a.ndim != 2:
-                raise ValueError("lesion: %s must be a 2-D [sets, nodes] array, got shape %s" % (what, list(a.shape)))
+                raise ValueError("%s: %s must be a 2-D [sets, nodes] array, got shape %s" % (method, what, list(a.shape)))
             if a.dtype != np.bool_:
                 if a.dtype.kind not in "iuf" or not np.isin(a, (0, 1)).all():
-                    raise ValueError("lesion: %s must be bool or hold only 0 and 1" % what)
+                    raise ValueError("%s: %s must be bool or hold only 0 and 1" % (method, what))
                 a = a != 0
             return a
         ns = [len(g.g) for g in graphs]
-        shared = torch.is_tensor(rois) or isinstance(rois, np.ndarray) or (
-            isinstance(rois, (list, tuple)) and len(rois) > 0 and np.ndim(rois[0]) == 1 and not torch.is_tensor(rois[0]))
-        if shared:
-            a = as_mask(rois, "rois")
+        if GIN_InfoMaxReg._shared_mask(rois):
+            a = as_mask(rois, name)
             if any(k != ns[0] for k in ns):
-                raise ValueError("lesion: a shared [S, n] mask needs graphs of one node count")
+                raise ValueError("%s: a shared [S, n] mask needs graphs of one node count" % method)
             sets = [a] * len(graphs)
         else:
             if not isinstance(rois, (list, tuple)) or len(rois) != len(graphs):
-                raise ValueError("lesion: rois must be one [S, n] array or a list of one [S_g, n_g] array per graph")
-            sets = [as_mask(a, "rois[%d]" % j) for j, a in enumerate(rois)]
+                raise ValueError("%s: %s must be one [S, n] array or a list of one [S_g, n_g] array per graph"
+                                 % (method, name))
+            sets = [as_mask(a, "%s[%d]" % (name, j)) for j, a in enumerate(rois)]
         for j, (a, n) in enumerate(zip(sets, ns)):
             if n < 2:
-                raise ValueError("lesion: a graph of fewer than 2 nodes has no lesioned copy")
+                raise ValueError("%s: a graph of fewer than 2 nodes has no %s copy"
+                                 % (method, "lesioned" if proper else "edge-cut"))
             if a.shape[1] != n:
-                raise ValueError("lesion: the mask of graph %d is %d wide for a %d-node graph" % (j, a.shape[1], n))
-            if a.shape[0] and a.all(1).any():
-                raise ValueError("lesion: a set removes every node of graph %d" % j)
+                raise ValueError("%s: the mask of graph %d is %d wide for a %d-node graph" % (method, j, a.shape[1], n))
+            if proper and a.shape[0] and a.all(1).any():
+                raise ValueError("%s: a set removes every node of graph %d" % (method, j))
         return sets
+
+    @staticmethod
+    def _stacked_sets(sets, which, nm):
+        """The sets of graphs `which` of a chunk (bool [S_j, n_j] each), graph by graph, as the rows of one uint8
+        [sum of S_j, nm] array, and the row's graph as its position in `which` (int32): the virtual graphs of a batch"""
+        rows = np.zeros((sum(sets[j].shape[0] for j in which), nm), dtype=np.uint8)
+        vgraph = np.concatenate([np.full(sets[j].shape[0], k, dtype=np.int32) for k, j in enumerate(which)])
+        q = 0
+        for j in which:
+            s = sets[j]
+            rows[q:q + s.shape[0], :s.shape[1]] = s
+            q += s.shape[0]
+        return rows, vgraph
 
     def _lesion_batch(self, chunk, batch, P, classes, sets):
         """lesion() of one batch: (base [len(classes), B], lesioned [len(classes), sum of S_g], graph by graph)"""
-        X, base = self._virtual_prologue("lesion", lesion_decline, batch, P, classes)
-
         def run(b, Xb, which):
             """the virtual graphs of graphs `which` of the chunk, which are the graphs of batch b, in order"""
-            nm = int(b.n_max)
-            removed = np.zeros((sum(sets[j].shape[0] for j in which), nm), dtype=np.uint8)
-            vgraph = np.concatenate([np.full(sets[j].shape[0], k, dtype=np.int32) for k, j in enumerate(which)])
-            q = 0
-            for j in which:
-                s = sets[j]
-                removed[q:q + s.shape[0], :s.shape[1]] = s
-                q += s.shape[0]
+            removed, vgraph = self._stacked_sets(sets, which, int(b.n_max))
             return lesion_hip(self._spec, b, Xb, P, classes, removed, vgraph)
+        return self._sets_batch("lesion", lesion_decline, chunk, batch, P, classes,
+                                [sets[j].shape[0] for j in range(batch.B)], run)
 
+    def _sets_batch(self, method, decline, chunk, batch, P, classes, cnt, run):
+        """One batch of lesion() / disconnect(): (base [len(classes), B], scores [len(classes), sum of cnt], graph by
+        graph) with graph j's cnt[j] virtual graphs from run(batch, X, which) -- see _lesion_batch"""
+        X, base = self._virtual_prologue(method, decline, batch, P, classes)
         bad = _nonfinite_graphs(batch, X)
         if bad is None:
             return base, run(batch, X, list(range(batch.B)))
         # a graph with a non-finite feature: all-NaN results; the others run as a batch of their own
-        cnt = [sets[j].shape[0] for j in range(batch.B)]
         out = torch.full((len(classes), sum(cnt)), float("nan"), dtype=torch.float32, device=self.eps.device)
         good = [j for j in range(batch.B) if not bad[j]]
         if good:
@@ -729,6 +754,106 @@ class GIN_InfoMaxReg(nn.Module):
         _, _, scores = self.lesion(graphs, cls, masks, batch_size=batch_size, return_scores=True)
         realised = np.stack([c / float(len(g.g)) for c, g in zip(counts, graphs)])       # [G, K]
         return scores, curve_area(scores.cpu().numpy(), realised)
+
+    def disconnect(self, graphs, cls, a, b=None, batch_size=8, return_scores=False):
+        """Virtual disconnection of ROI-SET PAIRS of many graphs in batches: how far the class score moves when the
+        connections between two sets of nodes -- two resting-state networks, the hemispheres -- are cut; the
+        perturbation check of edge_saliency(), as occlusion() / lesion() are of the node maps.  With G (/) (A, B) the
+        graph G without every edge (u, v) of edge_mat for which (u in A and v in B) or (u in B and v in A) -- ALL n
+        nodes, all feature rows and every other edge untouched -- and score_c the eval logit of lesion():
+
+            disconnected[c, g, s] = score_c(G_g (/) (A_s, B_s)),   base[c, g] = score_c(G_g),
+            delta = base - disconnected  (fp32)
+
+        The readout runs over all n nodes (graph "average": the fp32 1/n); neighbour "average" divides by the cut
+        graph's own degree.  The self loop added when learn_eps is off is not an edge and is never cut; an explicit
+        (v, v) edge is cut when v is in A and in B.  The rule is symmetric, so directed graphs need no special case and
+        disconnect(a, b) is disconnect(b, a).  b=None means b = a: the connections INSIDE each set.  Empty sets (an empty
+        cut) and sets holding every node (A = B = all: the edgeless graph) are taken.
+
+        a, b (True / 1 = in the set): lesion()'s forms of `rois` -- ONE bool or 0/1 array or tensor [S, n] applied to
+        every graph, which then all have n nodes, or a list of len(graphs) arrays [S_g, n_g] -- agreeing in form and
+        shape.  No copy of a graph is built: csrc/disconnect.hip runs every (graph, pair) as a virtual graph over the
+        source graph's bit adjacency under a keep mask chosen per row (include/gnm_hip.h gnm_disconnect); base is the
+        model's ordinary eval forward.  gnm/lesion.py cut_edge_counts gives the number of edges a cut removes, which a
+        delta is to be read against.
+
+        cls, the result shapes, return_scores (-> (delta, base, disconnected)), the declined shapes (ValueError naming
+        the condition, through lesion()'s predicate) and the policy for a non-finite feature (all-NaN results for that
+        graph, its batch-mates run as a clean batch) are lesion()'s.  If a cut leaves a node without neighbours under
+        neighbour "average" with learned eps, the reference's 0/0 row makes that score NaN: disconnected[:, g, s] is NaN
+        and no other entry is.  A mask of the wrong width or with an entry other than 0 / 1, a and b of different
+        shapes and a shared mask over graphs of different node counts raise ValueError.
+
+        The result is bitwise the same run to run, for any batch_size, any chunking (gnm/core.py LESION_SCRATCH_BYTES)
+        and whatever other pairs share the call.  No parameter .grad, BatchNorm buffer or numpy RNG state is touched,
+        and the train / eval mode is restored on exit."""
+        single, classes = self._interpret_args("disconnect", graphs, cls, batch_size)
+        sa = self._lesion_sets(graphs, a, "disconnect", "a", proper=False)
+        if b is None:
+            sb = sa
+        else:
+            if self._shared_mask(a) != self._shared_mask(b):
+                raise ValueError("disconnect: a and b must take one form, one [S, n] array or a list of per-graph arrays")
+            sb = self._lesion_sets(graphs, b, "disconnect", "b", proper=False)
+            for j, (x, y) in enumerate(zip(sa, sb)):
+                if x.shape != y.shape:
+                    raise ValueError("disconnect: a and b of graph %d have shapes %s and %s"
+                                     % (j, list(x.shape), list(y.shape)))
+        return self._set_scores(graphs, single, classes, batch_size, [int(s.shape[0]) for s in sa], return_scores,
+                                lambda chunk, batch, P, i0: self._disconnect_batch(
+                                    chunk, batch, P, classes, sa[i0:i0 + len(chunk)], sb[i0:i0 + len(chunk)]))
+
+    def _disconnect_batch(self, chunk, batch, P, classes, sa, sb):
+        """disconnect() of one batch: (base [len(classes), B], disconnected [len(classes), sum of S_g], graph by graph)"""
+        def run(bt, Xb, which):
+            """the virtual graphs of graphs `which` of the chunk, which are the graphs of batch bt, in order"""
+            in_a, vgraph = self._stacked_sets(sa, which, int(bt.n_max))
+            in_b, _ = self._stacked_sets(sb, which, int(bt.n_max))
+            return disconnect_hip(self._spec, bt, Xb, P, classes, in_a, in_b, vgraph)
+        return self._sets_batch("disconnect", disconnect_decline, chunk, batch, P, classes,
+                                [sa[j].shape[0] for j in range(batch.B)], run)
+
+    def disconnection_matrix(self, graphs, cls, labels, batch_size=8, return_scores=False):
+        """The network-by-network disconnection matrix: disconnect() on every unordered pair of the networks of a
+        labelling.  labels: ONE int [n] vector for all graphs (which then all have n nodes) or a list of per-graph
+        [n_g] vectors; entry r is the network id of node r in 0 .. K - 1, or -1 for no network; K is the largest id
+        over all graphs + 1.  The K (K + 1) / 2 pairs (p <= q) with A = network p, B = network q (gnm/lesion.py
+        pair_sets) run in ONE disconnect() call, and delta is scattered into a symmetric float32 device tensor
+        [len(graphs), K, K] for an int `cls` ([len(cls), len(graphs), K, K] for a sequence): entry (p, q) = (q, p) is the
+        score lost by cutting networks p and q apart, entry (p, p) by cutting the connections inside network p.
+        return_scores=True returns (delta, base, scores), scores laid out as delta -- bitwise disconnect()'s values
+        for those pairs.  A network without nodes in a graph gives an empty cut.  Otherwise as disconnect()."""
+        self._interpret_args("disconnection_matrix", graphs, cls, batch_size)
+        as_np = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)     # noqa: E731
+        shared = torch.is_tensor(labels) or isinstance(labels, np.ndarray) or (
+            isinstance(labels, (list, tuple)) and len(labels) > 0 and np.ndim(labels[0]) == 0)
+        per = [as_np(labels)] if shared else [as_np(v) for v in labels]
+        if not shared and len(per) != len(graphs):
+            raise ValueError("disconnection_matrix: %d label vectors for %d graphs" % (len(per), len(graphs)))
+        for v in per:
+            if v.ndim != 1 or v.dtype.kind not in "iu":
+                raise ValueError("disconnection_matrix: labels must be int [n] vectors, got dtype %s shape %s"
+                                 % (v.dtype, list(v.shape)))
+        K = max([int(v.max()) + 1 for v in per if v.size] + [0])
+        if K < 1:
+            raise ValueError("disconnection_matrix: the labels name no network")
+        try:
+            sets = [pair_sets(v, K) for v in per]
+        except ValueError as e:
+            raise ValueError("disconnection_matrix: %s" % e) from None
+        pairs = sets[0][2]
+        a, b = (sets[0][0], sets[0][1]) if shared else ([s[0] for s in sets], [s[1] for s in sets])
+        delta, base, scores = self.disconnect(graphs, cls, a, b, batch_size=batch_size, return_scores=True)
+        p, q = torch.as_tensor(pairs[:, 0], device=delta.device), torch.as_tensor(pairs[:, 1], device=delta.device)
+
+        def square(flat):
+            mat = flat.new_empty(flat.shape[:-1] + (K, K))
+            mat[..., p, q] = flat
+            mat[..., q, p] = flat
+            return mat
+        delta = square(delta)
+        return (delta, base, square(scores)) if return_scores else delta
 
     def integrated_gradients(self, graphs, cls, steps=32, baseline=None, method="midpoint", batch_size=8,
                              return_scores=False):

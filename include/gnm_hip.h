@@ -445,6 +445,28 @@ int gnm_lesion(const uint32_t* adj_bits, const int64_t* b_bits_off, const int32_
                float bn_eps, const long long* table, const float* eps, float* scratch, float* out, long long ldo,
                void* stream);
 
+/* ---- Eval-mode virtual disconnection of ROI-set pairs (csrc/disconnect.hip) ------------------------------------------
+ * out[ci * ldo + q] = the eval-mode class score c_logit[classes_host[ci]] of virtual graph q = (source graph vgraph[q],
+ * set pair (A_q, B_q)): the graph with every edge (u, v) removed for which (u in A and v in B) or (u in B and v in A).
+ * ALL n nodes and feature rows stay: the readout runs over n nodes (graph "average": the fp32 1 / n), neighbour
+ * "average" divides by the cut graph's own degree (0 / 0 -> NaN for a row left without a neighbour under learned eps, as
+ * the reference computes it on the explicit copy), and the self loop added when learn_eps is off is never cut (an explicit
+ * (v, v) edge is, when v is in A and in B).  Empty sets and sets holding every node are taken.
+ * keep_a, keep_b: [V][mstride] each, the KEEP masks of A and of B in gnm_lesion_pack's layout (its output for "removed"
+ * arrays A and B: the complements within n); mstride as gnm_lesion's.  kept: [V] int32 on the DEVICE holding each
+ * virtual graph's node count n (the readout's divisor); vn_host: the same counts on the HOST.  The other arguments, the
+ * scratch size (gnm_disconnect_scratch_floats = gnm_lesion_scratch_floats), the launches (L over (virtual graph, 32-row
+ * block), one finish per 8 classes) and the return codes are gnm_lesion's, nothing launched on any error: BAD_ARG also
+ * for a NULL mask and a node count outside 1..n_max.  Fixed summation orders, no atomics: bitwise reproducible, and a
+ * virtual graph's result does not depend on the others. */
+long long gnm_disconnect_scratch_floats(long long rows, long long V, int n_max, int H, int L);
+int gnm_disconnect(const uint32_t* adj_bits, const int64_t* b_bits_off, const int32_t* node_off, const int32_t* vgraph,
+                   const int64_t* vrow_off, const uint32_t* keep_a, const uint32_t* keep_b, int mstride,
+                   const int32_t* kept, const int32_t* vn_host, int B, int n_max, long long V, long long rows,
+                   const float* XW, int ldxw, int H, int L, int m, int C, const int* classes_host, int n_classes,
+                   int average, int self_loop, int graph_avg, float bn_eps, const long long* table, const float* eps,
+                   float* scratch, float* out, long long ldo, void* stream);
+
 /* ---- Eval-mode integrated gradients (csrc/intgrad.hip over csrc/saliency.hip's layer launches) ----------------------
  * attr[node_off[g] + r, :] = (X - x')[g, r, :] * sum_k w_k d score[cls] / d X (x' + alpha_k (X_g - x'))[r, :] for every
  * graph g of a batch, x' the baseline (zeros, or one [n_base, F0] block every graph shares), (alpha_k, w_k), k < K, a
