@@ -631,3 +631,192 @@ def attr_bound(ref32, ref64):
     """helpers.Calibrated's rule on attr_noise: max(RTOL, 4 x the fp32 reference's distance from fp64)"""
     from helpers import RTOL, TRUE_SHAPE_FACTOR
     return max(RTOL, TRUE_SHAPE_FACTOR * attr_noise(ref32, ref64))
+
+
+# =========================================================================== disconnect
+# disconnect() / disconnection_matrix() (csrc/disconnect.hip, rb_stage_bits_cut of csrc/gnm_rowblock.h) on the same table
+# (tests/test_gpu_disconnect_midrange.py on the GPU, tests/test_disconnect_midrange_host.py without one).  What a cut has
+# that a lesion has not is a lookup per ROW -- whether row r is in A, in B, in both or in neither (rb_row_bit on the two
+# keep masks) -- so the pairs below name rows by the fields of that lookup: the word r >> 6, the half (r >> 3) & 1, the
+# byte (r >> 4) & 3.  A case that breaks a condition of the host test is used as a variant with another model seed
+# (dc_case: the id gains "-d"); SEEDS, GRAD_SEEDS and the cases above stay as they are.
+DC_SEEDS = {
+    # case id: seed, with the condition's value before -> after.  No case needs one: with the table's seeds the fp32 CPU
+    # forward is at most 4.3e-6 from fp64 on the cut copies (cap 5e-6) and every wrong formulation at least 1.9e-4 away
+}
+WORD_EDGES = (63, 127, 191, 255)                    # rows e, e + 1: either side of a 64-row word of the keep masks
+MATRIX_NETWORKS = 5
+
+DisconnectRef = collections.namedtuple("DisconnectRef", "a b names want_nan base64 base32 dis64 dis32")
+
+
+def dc_case(case):
+    """the case as the disconnect tests use it: itself, or its reseeded "-d" variant (same graphs, other model)"""
+    if case.id not in DC_SEEDS:
+        return case
+    return case._replace(seed=DC_SEEDS[case.id], id=case.id + "-d")
+
+
+def dc_cases(n):
+    return tuple(dc_case(c) for c in cases(n))
+
+
+def all_dc_cases():
+    """the 63 cases of the matrix and the one-hot case of n = 257"""
+    return tuple(c for n in NODES for c in dc_cases(n))
+
+
+def dc_matrix_case(n):
+    """the case of n that carries the disconnection_matrix() test: H = 64, m = 2, dense features"""
+    return next(c for c in dc_cases(n) if c.H == 64 and c.m == 2 and not c.one_hot)
+
+
+def disconnect_pairs(case, d):
+    """the set pairs of graph d of a case: (names, A [S, n] bool, B [S, n] bool)"""
+    n = case.n
+    rng = np.random.default_rng(case.seed * 11 + d + n)
+    idx = np.arange(n)
+    W = row_blocks(n)
+    none, every = np.zeros(n, dtype=bool), np.ones(n, dtype=bool)
+    P = [("empty", none, none),
+         ("last-node x all", idx == n - 1, every),                                # a node isolated, dead rows behind it
+         ("block-0 x block-1", block_of(n, 0), block_of(n, 1)),                   # the ring edge 31 -> 32 is cut
+         ("block-%d x block-%d" % (W - 2, W - 1), block_of(n, W - 2), block_of(n, W - 1)),
+         ("block-2 within itself", block_of(n, 2), block_of(n, 2)),               # rows in A and in B: both masks
+         ("half rows", ((idx >> 3) & 1) == 0, ((idx >> 3) & 1) == 1),             # the h * HPW half select
+         ("bytes", ((idx >> 4) & 3) == 1, ((idx >> 4) & 3) == 3)]                 # the byte shift
+    for e in WORD_EDGES:
+        if n > e + 1:
+            P.append(("word edge %d" % e, np.isin(idx, (e, e + 1)),
+                      np.isin(idx, (e + 1, min(e + 2, n - 1))) | block_of(n, 0)))
+    half = np.isin(idx, rng.choice(n, n // 2, replace=False))
+    P.append(("half x complement", half, ~half))
+    P.append(("overlapping random sets", rng.random(n) < 0.35, rng.random(n) < 0.35))
+    P.append(("all x all", every, every))                                         # the edgeless graph
+    return [k for k, _, _ in P], np.stack([a for _, a, _ in P]), np.stack([b for _, _, b in P])
+
+
+def disconnect_reference_of(state, spec, graph, a, b, npool, eps):
+    """(base64 [C], base32, disconnected64 [S, C], disconnected32, want_nan [S]) of a graph's pairs: the fp64 oracle and
+    the independent fp32 CPU forward on explicit edge-cut copies (test_disconnect_host.cut_edges)"""
+    from test_disconnect_host import cut_edges, expect_nan_cut
+    copies = [graph] + [cut_edges(graph, A, B) for A, B in zip(a, b)]
+    r64 = oracle_scores64(state, spec, copies)
+    r32 = torch_scores32(state, spec, copies)
+    want = np.array([expect_nan_cut(graph, A, B, npool, eps) for A, B in zip(a, b)], dtype=bool)
+    return r64[0], r32[0], r64[1:], r32[1:], want
+
+
+@functools.lru_cache(maxsize=None)
+def disconnect_reference(case):
+    """per graph of the case: DisconnectRef(A [S, n], B [S, n], the pairs' names, expect_nan_cut per pair, base [C] and
+    disconnected [S, C] through the fp64 oracle and through the fp32 CPU forward, both on explicit copies)"""
+    out = []
+    for d, g in enumerate(graphs_of(case)):
+        names, a, b = disconnect_pairs(case, d)
+        b64, b32, d64, d32, want = disconnect_reference_of(state_of(case), spec_of(case), g, a, b, case.npool, case.eps)
+        out.append(DisconnectRef(a, b, names, want, b64, b32, d64, d32))
+    return tuple(out)
+
+
+def matrix_labels(case, d):
+    """the network labelling of graph d for disconnection_matrix(): MATRIX_NETWORKS networks, every 23rd node of none"""
+    lab = np.random.default_rng(case.seed * 13 + d + case.n).integers(0, MATRIX_NETWORKS, case.n)
+    lab[d::23] = -1
+    return lab
+
+
+@functools.lru_cache(maxsize=None)
+def matrix_reference(case):
+    """per graph of the case: DisconnectRef of the 15 pairs of gnm.lesion.pair_sets(matrix_labels) (names: the pairs)"""
+    from gnm.lesion import pair_sets
+    out = []
+    for d, g in enumerate(graphs_of(case)):
+        a, b, pairs = pair_sets(matrix_labels(case, d), MATRIX_NETWORKS)
+        b64, b32, d64, d32, want = disconnect_reference_of(state_of(case), spec_of(case), g, a, b, case.npool, case.eps)
+        out.append(DisconnectRef(a, b, [tuple(p) for p in pairs.tolist()], want, b64, b32, d64, d32))
+    return tuple(out)
+
+
+def row_bit_word(n, r):
+    """the word of a keep mask rb_row_bit reads for row r: ((r >> 3) & 1) * HPW + (r >> 6)"""
+    return ((r >> 3) & 1) * half_words(n) + (r >> 6)
+
+
+def cut_keep(a, b):
+    """the keep matrix of the cut: entry (r, c) is False where row r is in A and column c in B, or r in B and c in A"""
+    return (~a[:, None] | ~b[None, :]) & (~b[:, None] | ~a[None, :])
+
+
+def keep_forward64(state, args, graph, keep, uncut_degree=False):
+    """test_disconnect_host.cut_forward64 for any per-row keep matrix [n, n] (entry (r, c): row r keeps column c), or a
+    batch [K, n, n] of them, in fp64 numpy on the SOURCE graph: the masked adjacency, its degree -- or, uncut_degree, the
+    degree of the unmasked row -- every row kept, the readout over all n nodes.  [C] or [K, C] logits.  With
+    cut_keep(A, B) it is cut_forward64 (pinned by the host test); with another matrix it is a wrong formulation for the
+    host test to tell apart."""
+    L, m, learn_eps, gpool, npool = args
+    p = {k: np.asarray(v, dtype=np.float64) for k, v in state.items() if np.asarray(v).dtype.kind == "f"}
+    n = len(graph.g)
+    keep = np.asarray(keep, dtype=bool)
+    single = keep.ndim == 2
+    keep = keep.reshape(-1, n, n)
+    em = np.asarray(graph.edge_mat).astype(np.int64).reshape(2, -1)
+    adj = np.bincount(em[0] * n + em[1], minlength=n * n).reshape(n, n).astype(np.float64)
+    Am = adj[None] * keep
+    deg = (np.broadcast_to(adj, Am.shape) if uncut_degree else Am).sum(2) + (0 if learn_eps else 1)      # [K, n]
+
+    def bn(x, name):
+        return (x - p[name + ".running_mean"]) / np.sqrt(p[name + ".running_var"] + 1e-5) * p[name + ".weight"] \
+            + p[name + ".bias"]
+
+    h = np.broadcast_to(np.asarray(graph.node_features, dtype=np.float64), (keep.shape[0], n, graph.node_features.shape[1]))
+    score = 0.0
+    scale = float(np.float32(1.0 / n)) if gpool == "average" else 1.0
+    with np.errstate(all="ignore"):
+        for l in range(L):
+            pooled = Am @ h
+            if not learn_eps:
+                pooled = pooled + h
+            if npool == "average":
+                pooled = pooled / deg[:, :, None]
+            if learn_eps:
+                pooled = pooled + (1 + p["eps"][l]) * h
+            x = pooled
+            for k in range(m):
+                wn = f"mlps.{l}.linear" if m == 1 else f"mlps.{l}.linears.{k}"
+                x = x @ p[wn + ".weight"].T + p[wn + ".bias"]
+                x = np.maximum(bn(x, f"batch_norms.{l}" if k == m - 1 else f"mlps.{l}.batch_norms.{k}"), 0)
+            h = x
+            score = score + (h.sum(1) * scale) @ p[f"linears_prediction.{l}.weight"].T + p[f"linears_prediction.{l}.bias"]
+    return score[0] if single else score
+
+
+MUTANTS = ("masks swapped", "one-sided cut", "row bits of the high words lost", "column bits of the high words lost",
+           "row membership from the other half", "degree of the uncut row")
+
+
+def _rows_lost(a, b, high):
+    """rows of the high words are taken to be in neither set; the column masks are whole"""
+    ar, br = a & ~high, b & ~high
+    return (~ar[:, None] | ~b[None, :]) & (~br[:, None] | ~a[None, :])
+
+
+def disconnect_mutants(a, b, n):
+    """wrong formulations of the cut of (A, B) on an n-node graph, for the host test only: name -> (keep matrix [n, n],
+    uncut_degree) for keep_forward64.  "High words": word index r >> 6 of a half row from 2 on (n <= 256, HPW = 4: the
+    second half of the one 128-bit load) or from 4 on (n > 256, HPW = 8: the second load)."""
+    a, b = np.asarray(a, dtype=bool), np.asarray(b, dtype=bool)
+    idx = np.arange(n)
+    high = (idx >> 6) >= (2 if n <= 256 else 4)
+    right = cut_keep(a, b)
+    other = idx ^ 8                                   # a keep mask is zero at columns >= n: such a row reads "in the set"
+    ao = np.where(other < n, a[np.minimum(other, n - 1)], True)
+    bo = np.where(other < n, b[np.minimum(other, n - 1)], True)
+    return {
+        "masks swapped": ((~a[:, None] | ~a[None, :]) & (~b[:, None] | ~b[None, :]), False),   # rows of A lose A
+        "one-sided cut": (~a[:, None] | ~b[None, :], False),                                    # rows of B keep A
+        "row bits of the high words lost": (_rows_lost(a, b, high), False),
+        "column bits of the high words lost": (right | high[None, :], False),
+        "row membership from the other half": ((~ao[:, None] | ~b[None, :]) & (~bo[:, None] | ~a[None, :]), False),
+        "degree of the uncut row": (right, True),
+    }
