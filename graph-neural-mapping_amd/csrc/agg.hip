@@ -86,6 +86,61 @@ __device__ __forceinline__ void acc4(float4& a, const float4 v) {
 __device__ __forceinline__ void acc4(float4& a, const f32x4 v) {
     a.x += v[0]; a.y += v[1]; a.z += v[2]; a.w += v[3];
 }
+// float4 arithmetic, component by component in x, y, z, w order (fast contraction fuses a * b + c after inlining: the
+// helpers keep every expression's operation order, they do not reassociate)
+__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ void scale4(float4& a, float s) { a.x *= s; a.y *= s; a.z *= s; a.w *= s; }
+__device__ __forceinline__ void div4(float4& a, float d) { a.x /= d; a.y /= d; a.z /= d; a.w /= d; }
+__device__ __forceinline__ void fma4(float4& a, float s, const float4 b) {       // a += s * b
+    a.x += s * b.x; a.y += s * b.y; a.z += s * b.z; a.w += s * b.w;
+}
+__device__ __forceinline__ float4 bn_relu4(const float4 z, const float4 sc, const float4 sh) {
+    return make_float4(gnm_relu(z.x * sc.x + sh.x), gnm_relu(z.y * sc.y + sh.y), gnm_relu(z.z * sc.z + sh.z),
+                       gnm_relu(z.w * sc.w + sh.w));
+}
+// mine + theirs[l ^ 8] (the DPP row_ror:8 step of the transposing combines)
+__device__ __forceinline__ float4 add_ror8(const float4 mine, const float4 theirs) {
+    return make_float4(mine.x + ror8(theirs.x), mine.y + ror8(theirs.y), mine.z + ror8(theirs.z), mine.w + ror8(theirs.w));
+}
+// fp64 dot product of two 16-byte chunks, products in fp64 (the d-eps term of phase A)
+__device__ __forceinline__ double dot4d(const float4 a, const float4 b) {
+    return (double)a.x * b.x + (double)a.y * b.y + (double)a.z * b.z + (double)a.w * b.w;
+}
+
+// Four floats at src, columns cc .. cc + 3 of a row that is F wide: columns past F read as 0 / are not written.
+// `vec`: the caller knows all four exist and src is 16-byte aligned.
+__device__ __forceinline__ float4 load4_guarded(const float* src, int cc, int F) {
+    float4 v;
+    v.x = (cc + 0 < F) ? src[0] : 0.f;
+    v.y = (cc + 1 < F) ? src[1] : 0.f;
+    v.z = (cc + 2 < F) ? src[2] : 0.f;
+    v.w = (cc + 3 < F) ? src[3] : 0.f;
+    return v;
+}
+__device__ __forceinline__ float4 load4(const float* src, bool vec, int cc, int F) {
+    if (vec) return *reinterpret_cast<const float4*>(src);
+    return load4_guarded(src, cc, F);
+}
+__device__ __forceinline__ void store4_guarded(float* dst, const float4 v, int cc, int F) {
+    if (cc + 0 < F) dst[0] = v.x;
+    if (cc + 1 < F) dst[1] = v.y;
+    if (cc + 2 < F) dst[2] = v.z;
+    if (cc + 3 < F) dst[3] = v.w;
+}
+// NT: the full-width store is the streaming flavour (see gnm_agg16_kernel's epilogue for why)
+template <bool NT>
+__device__ __forceinline__ void store4(float* dst, const float4 v, bool vec, int cc, int F) {
+    if (vec) {
+        if constexpr (NT) {
+            const f32x4 t4 = {v.x, v.y, v.z, v.w};
+            __builtin_nontemporal_store(t4, reinterpret_cast<f32x4*>(dst));
+        } else {
+            *reinterpret_cast<float4*>(dst) = v;
+        }
+    } else {
+        store4_guarded(dst, v, cc, F);
+    }
+}
 
 // LDS is addressed through 32-bit address-space-3 pointers built from integers, so
 // that "row base (DPP broadcast) + lane chunk + LDS base" is ONE v_add_u32_dpp
@@ -102,7 +157,232 @@ typedef __attribute__((address_space(3))) unsigned short* lds_u16p;
 __device__ __forceinline__ unsigned lds_read_u16(unsigned addr) { return *(lds_u16p)(uintptr_t)addr; }
 __device__ __forceinline__ void lds_write_u16(unsigned addr, unsigned v) { *(lds_u16p)(uintptr_t)addr = (unsigned short)v; }
 
-#define GNM_STEP16(S) acc4(acc, lds_read16(row_bcast16<S>(valb) + subb));
+// In-kernel timeline (tools/agg_timeline.py; -DGNM_AGG16_TUNING builds only): lane 0 of every wave drops s_memtime
+// stamps at phase / group boundaries, where no LDS read is in flight anyway (s_memtime returns through lgkmcnt)
+#ifdef GNM_AGG16_TUNING
+#define GNM_STAMP(k)                                                                                          \
+    if (p.stamps && (threadIdx.x & 63) == 0)                                                                  \
+        p.stamps[((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 64 + (k)] = __builtin_amdgcn_s_memtime();
+#else
+#define GNM_STAMP(k)
+#endif
+
+// ---- LDS layouts: byte offsets into the dynamic LDS block and its size.  A kernel evaluates its layout with the
+// graph's own row count, the host (launchers, gnm_agg_slice_width, the fit check of gnm_agg_fwd_bnrelu) with the
+// batch's largest; no other place computes an LDS offset or size. ------------------------------------------------
+__host__ __device__ inline size_t agg_align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// The reductions at the end of the STATS kernels reuse the tile's first bytes: [kAggDepsSlots] doubles of d-eps wave
+// sums, then [waves][2][cols] doubles of column statistics.  A batch of very small graphs (n_max < 17 at 64 columns)
+// has a tile smaller than that, so the launchers raise the allocation to this floor (found by tests/test_gpu_aggm.py,
+// graphs of 3 nodes: the sums lost every contribution written past the allocation).
+static constexpr int kAggDepsSlots = 64;
+__host__ __device__ inline size_t agg_reduce_lds(int threads, int cols) {
+    return (size_t)(kAggDepsSlots + (threads / 64) * 2 * cols) * 8;
+}
+
+// gnm_agg16_kernel: [rows + 1] tile rows of 256 B (the last one zeros) | the ticket word, in a (rows + 2)-word area |
+// (prologue only) the readout shares, one float4 per thread of up to 1024
+struct Agg16Lds {
+    size_t ticket, rsum, total;
+};
+__host__ __device__ inline Agg16Lds agg16_lds(int rows, bool prologue) {
+    Agg16Lds l;
+    l.ticket = (size_t)(rows + 1) * 256;
+    l.rsum = agg_align16(l.ticket + (size_t)(rows + 2) * 4);
+    l.total = l.ticket + (size_t)(rows + 2) * 4 + 16;
+    if (prologue) l.total += 16 + (size_t)1024 * 16;
+    return l;
+}
+
+// gnm_agg_kernel<LPR, MODE>: [rows + ZR] tile rows of 16 LPR bytes (the last ZR zeros; ZR = 2 for LPR == 8: one of
+// each parity), then either
+//   ids_in_lds == 1 (LPR <= 4): the graph's nnz column ids, shifted by the source's misalignment (at most 7 ids) and
+//                               copied in 16-byte pieces (96 bytes cover both), or
+//   the staged row offsets [rows + 1] with the group ticket of LPR == 8 behind them at [rows + 1]
+//   | ids_in_lds == 2 (LPR == 8): the waves' id scratch, 16 x 1 KB | MODE 1: the readout shares [16 waves][8] float4.
+static constexpr unsigned kAggIdScratch = 1024;     // bytes of id scratch per wave: 8 rows x 64 positions x 2 bytes
+struct AggTileLds {
+    size_t rp, ticket, ids, scr, rsum, total;
+};
+__host__ __device__ inline AggTileLds agg_tile_lds(int lpr, int rows, int mode, int ids_in_lds, int nnz) {
+    AggTileLds l;
+    const size_t tile = (size_t)(rows + (lpr == 8 ? 2 : 1)) * (lpr * 16);
+    l.rp = tile;
+    l.ticket = tile + (size_t)(rows + 1) * 4;
+    l.ids = agg_align16(tile);
+    l.scr = agg_align16(tile + (size_t)(rows + 2) * 4 + 16);
+    l.rsum = l.scr + (ids_in_lds == 2 ? 16 * kAggIdScratch : 0);
+    if (ids_in_lds == 1) l.total = tile + (size_t)nnz * 2 + 96;
+    else if (mode == 1) l.total = l.rsum + 16 * 8 * 16;
+    else if (ids_in_lds == 2) l.total = l.rsum;
+    else l.total = tile + (size_t)(rows + 2) * 4 + 16;
+    return l;
+}
+// What gnm_agg_slice_width budgets for a slice of fs floats: the LPR == 8 form (two zero rows, staged row offsets)
+// at every width, a little more than the other widths need.
+__host__ inline size_t agg_slice_budget(int fs, int rows) {
+    return (size_t)(rows + 2) * fs * 4 + (size_t)(rows + 2) * 4 + 16;
+}
+
+// What a workgroup derives from its block index: one graph x one slice of FS floats.
+struct AggBlock {
+    int b, row0, n, col0;      // graph, its first row and row count, first column of the slice
+    const int32_t* rp;         // the graph's rowptr / column id / degree rowptr blocks
+    const uint16_t* cl;
+    const int32_t* drp;
+    bool vec_in, vec_h;        // x / hfwd rows are 16-byte addressable
+    bool prescale;             // "average" backward: the tile holds x / deg
+};
+__device__ __forceinline__ AggBlock agg_block(const AggArgs& p, int FS) {
+    AggBlock k;
+    k.b = blockIdx.x / p.nslices;
+    const int sl = blockIdx.x - k.b * p.nslices;
+    k.row0 = p.node_off[k.b];
+    k.n = p.node_off[k.b + 1] - k.row0;
+    k.col0 = sl * FS;
+    k.rp = p.rowptr + p.b_rp_off[k.b];
+    k.cl = p.col + p.b_col_off[k.b];
+    k.drp = p.deg_rowptr + p.b_deg_off[k.b];
+    k.vec_in = ((p.ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.x) & 15) == 0);
+    k.vec_h = p.hfwd && ((p.ldh & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.hfwd) & 15) == 0);
+    k.prescale = p.backward && p.average;
+    return k;
+}
+__device__ __forceinline__ float agg_self_b(const AggArgs& p) { return p.self_loop ? 0.f : (p.eps ? 1.f + *p.eps : 1.f); }
+__device__ __forceinline__ bool agg_vec_out(const AggArgs& p) {
+    return ((p.ldy & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.y) & 15) == 0);
+}
+
+// Phase A, one 16-byte tile element i of an LPR-chunk row on the generic path (any width, any alignment): load,
+// d-eps dot against hfwd, 1/deg pre-scale.  The unrolled fast paths of the kernels are separate schedules.
+template <int LPR>
+__device__ __forceinline__ float4 phase_a_element(const AggArgs& p, const AggBlock& k, int i, bool dot_a, double& dot) {
+    const int r = i / LPR;
+    const int c = i - r * LPR;
+    const int cc = k.col0 + 4 * c;
+    float4 v = load4(p.x + (size_t)(k.row0 + r) * p.ldx + cc, k.vec_in && cc + 3 < p.F, cc, p.F);
+    if (dot_a) {
+        const float4 h = load4(p.hfwd + (size_t)(k.row0 + r) * p.ldh + cc, k.vec_h && cc + 3 < p.F, cc, p.F);
+        dot += dot4d(v, h);
+    }
+    if (k.prescale) div4(v, (float)(k.drp[r + 1] - k.drp[r] + p.self_loop));
+    return v;
+}
+
+// The row epilogue of gnm_agg_kernel's three plain paths (staged, 16-row groups, wave-cooperative), y[v] = post *
+// (sum + selfA * pre x[v]) + selfB * x[v] of the header, for row v, 16-byte chunk `sub` of the slice: `tot` the
+// gathered sum, `self` the row's own tile value (pre x[v]), `deg` the row's neighbour count.  The caller loads `self`
+// when its schedule wants it.  The two kernels with a streaming store and STATS terms (the 8-row groups,
+// gnm_agg16_kernel) keep these lines inline: through a shared form with hooks their products fused differently.
+__device__ __forceinline__ void agg_row_out(const AggArgs& p, const AggBlock& k, float4 tot, const float4 self, int v,
+                                            int sub, int deg, float selfB, bool vec_out) {
+    if (p.self_loop) acc4(tot, self);
+    if (!p.backward && p.average) div4(tot, (float)(deg + p.self_loop));   // 0/0 -> NaN as in the reference
+    const int cc = k.col0 + 4 * sub;
+    if (!p.self_loop) {
+        float4 sb = self;
+        if (k.prescale)   // the tile holds dp/deg; the (1+eps) term needs dp itself
+            sb = load4_guarded(p.x + (size_t)(k.row0 + v) * p.ldx + cc, cc, p.F);
+        fma4(tot, selfB, sb);
+    }
+    store4<false>(p.y + (size_t)(k.row0 + v) * p.ldy + cc, tot, vec_out && cc + 3 < p.F, cc, p.F);
+}
+
+// ---- fused BatchNorm-backward statistics of the layer below (STATS kernels), for the lane's 16-byte chunk `sub` of
+// the slice that starts at column col0 --------------------------------------------------------------------------
+// per-column constants; s_pb / s_ub stay as the caller set them (zero) where the term is absent
+__device__ __forceinline__ void stats_load_consts(const AggArgs& p, int b, int n, int col0, int sub, float4& lsc,
+                                                  float4& lsh, float4& lmu, float4& s_pb, float4& s_ub) {
+    lsc = *reinterpret_cast<const float4*>(p.s_scale + col0 + 4 * sub);
+    lsh = *reinterpret_cast<const float4*>(p.s_shift + col0 + 4 * sub);
+    lmu = *reinterpret_cast<const float4*>(p.s_mean + col0 + 4 * sub);    // (rstd multiplies the column sums at the end)
+    if (p.s_dpool) {
+        s_pb = *reinterpret_cast<const float4*>(p.s_dpool + (size_t)b * p.ld_dpool + col0 + 4 * sub);
+        if (p.s_avg) scale4(s_pb, 1.0f / (float)n);
+    }
+    if (p.s_dsc1) s_ub = *reinterpret_cast<const float4*>(p.s_U + (size_t)b * p.ld_U + col0 + 4 * sub);
+}
+// d eps += dpooled[v] . h[v], h = relu(bn_lo(Z[v])) recomputed as the forward formed it.  Each pair sum
+// sb.x * hx + sb.y * hy is ONE fused multiply-add, and which product is the fused one is written out: hipcc
+// contracted the inline text of the two kernels differently (FIRST: the 64-wide kernel fused the first product onto
+// the second, the 8-lane kernel the second onto the first) and, left to it again, paired the four products in the
+// vectoriser and fused none.  Each kernel keeps the rounding its d-eps partials always had.
+template <bool FIRST>
+__device__ __forceinline__ double stats_deps_term(const float4 sb, const float4 zrow, const float4 lsc, const float4 lsh) {
+    const float4 h = bn_relu4(zrow, lsc, lsh);
+    if constexpr (FIRST)
+        return (double)__builtin_fmaf(sb.x, h.x, sb.y * h.y) + (double)__builtin_fmaf(sb.z, h.z, sb.w * h.w);
+    else
+        return (double)__builtin_fmaf(sb.y, h.y, sb.x * h.x) + (double)__builtin_fmaf(sb.w, h.w, sb.z * h.z);
+}
+// row `row` of the batch: total gradient at this layer output = aggregation backward + readout + discriminator terms,
+// then the ReLU mask of the layer below and the two running column sums
+__device__ __forceinline__ void stats_row(const AggArgs& p, float4& tot, const float4 zrow, float dsc_v, int row,
+                                          int col0, int sub, const float4 lsc, const float4 lsh, const float4 lmu,
+                                          const float4 s_pb, const float4 s_ub, float4& ss1, float4& ss2) {
+    tot.x += s_pb.x + dsc_v * s_ub.x; tot.y += s_pb.y + dsc_v * s_ub.y;
+    tot.z += s_pb.z + dsc_v * s_ub.z; tot.w += s_pb.w + dsc_v * s_ub.w;
+    if (p.s_dsc1 && row < p.n_batch) {     // rows perm[g] < B of the shuffled branch (graphcnn.py:242)
+        const int gq = gnm_perm_entry(p.s_inv_perm[row], p.n_batch);
+        const float s2 = p.s_s2sum[gq];
+        const float4 uq = *reinterpret_cast<const float4*>(p.s_U + (size_t)gq * p.ld_U + col0 + 4 * sub);
+        fma4(tot, s2, uq);
+    }
+    if (zrow.x * lsc.x + lsh.x <= 0.f) tot.x = 0.f;
+    if (zrow.y * lsc.y + lsh.y <= 0.f) tot.y = 0.f;
+    if (zrow.z * lsc.z + lsh.z <= 0.f) tot.z = 0.f;
+    if (zrow.w * lsc.w + lsh.w <= 0.f) tot.w = 0.f;
+    acc4(ss1, tot);
+    ss2.x += tot.x * (zrow.x - lmu.x); ss2.y += tot.y * (zrow.y - lmu.y);
+    ss2.z += tot.z * (zrow.z - lmu.z); ss2.w += tot.w * (zrow.w - lmu.w);
+}
+// column sums of a workgroup: the 64 / LPR lane groups of a wave, then the waves, in a fixed order, into
+// s_partial[blk][2][ldp] at columns col0 .. col0 + 4 LPR.  Reuses the tile's first bytes (agg_reduce_lds).
+template <int LPR>
+__device__ __forceinline__ void stats_col_reduce(const AggArgs& p, char* smem, const float4 ss1, const float4 ss2,
+                                                 int tid, int lane, int wave, int nwaves, int sub, int col0,
+                                                 size_t blk, int ldp) {
+    constexpr int W = 4 * LPR;
+    __syncthreads();        // (everyone is done reading the tile)
+    double* sred = reinterpret_cast<double*>(smem) + kAggDepsSlots;      // [nwaves][2][W] (after the d-eps slots)
+    const float v1[4] = {ss1.x, ss1.y, ss1.z, ss1.w}, v2[4] = {ss2.x, ss2.y, ss2.z, ss2.w};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        double d1 = (double)v1[c], d2 = (double)v2[c];
+#pragma unroll
+        for (int off = LPR; off < 64; off <<= 1) {
+            d1 += __shfl_xor(d1, off, 64); d2 += __shfl_xor(d2, off, 64);
+        }
+        if (lane < LPR) {
+            sred[(wave * 2 + 0) * W + 4 * sub + c] = d1;
+            sred[(wave * 2 + 1) * W + 4 * sub + c] = d2;
+        }
+    }
+    __syncthreads();
+    if (tid < 2 * W) {
+        const int which = tid / W, col = tid & (W - 1);
+        double sum = 0.0;
+        for (int w = 0; w < nwaves; ++w) sum += sred[(w * 2 + which) * W + col];
+        if (which) sum *= (double)p.s_rstd[col0 + col];      // sum G (Z - mean) -> sum G xhat
+        p.s_partial[(blk * 2 + which) * ldp + col0 + col] = sum;
+    }
+}
+
+// block reduction of the d-eps dot product (fp64, fixed order) into *out; reuses the tile's first bytes
+__device__ __forceinline__ void deps_block_reduce(double dot, char* smem, double* out, int tid, int lane, int wave,
+                                                  int nwaves) {
+    __syncthreads();    // everyone is done reading the tile
+    double* red = reinterpret_cast<double*>(smem);
+    const double w = wave_sum_d(dot);
+    if (lane == 0) red[wave] = w;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int i = 0; i < nwaves; ++i) s += red[i];
+        *out = s;
+    }
+}
 
 // Column id at (uniform base, per-lane 32-bit index): written as base + zero-extended BYTE offset so the load
 // takes the SGPR-base + 32-bit VGPR-offset form (one v_lshl_add_u32 per load instead of a 64-bit address built
@@ -111,630 +391,361 @@ __device__ __forceinline__ unsigned load_id(const uint16_t* base, unsigned byte_
     return *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(base) + byte_off);
 }
 
-// MODE (32-float slices, LPR == 8, only; round 4 -- what gnm_agg16_kernel does for the 64-wide shape):
-//   1 = forward PROLOGUE: x is the Z of the layer below's last Linear; the tile load applies that layer's outer
-//       BatchNorm + ReLU (p_scale / p_shift), writes the activation (p_hout, optional) and the graph readout (p_gf):
-//       gnm_bn_relu_readout's pass (45 us of 128-wide rows at configs[3]) rides on loads this kernel issues anyway;
-//   2 = backward STATS: the epilogue adds the readout / discriminator terms, applies the ReLU mask of the layer
-//       below and reduces that layer's BatchNorm-backward column sums (s_partial), and takes d eps from the rows it
-//       holds (h recomputed from sZ): gnm_bn_relu_bwd_stats's pass (75 us) and the hfwd read of phase A go away.
-template <int LPR, int MODE = 0>
-__global__ void __launch_bounds__(1024) gnm_agg_kernel(const AggArgs p) {
-    constexpr int FS = LPR * 4;        // floats per LDS row
-    constexpr int SLOTS = 64 / LPR;    // neighbour rows read per wave-instruction
-    constexpr bool PRO = MODE == 1, STATS = MODE == 2;
-    static_assert(MODE == 0 || LPR == 8, "fused forms: 32-float slices only");
-#ifdef GNM_AGG16_TUNING       // in-kernel timeline (tools/agg_timeline.py)
-#define GNM_GSTAMP(k)                                                                                         \
-    if (p.stamps && (threadIdx.x & 63) == 0)                                                                  \
-        p.stamps[((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 64 + (k)] = __builtin_amdgcn_s_memtime();
-#else
-#define GNM_GSTAMP(k)
-#endif
-    GNM_GSTAMP(0)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4* tile = reinterpret_cast<float4*>(smem);
-    const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+// ---- The four phase-B algorithms of gnm_agg_kernel: gather neighbour rows from the LDS tile, finish and store the
+// rows.  `lds`: the kernel's layout (agg_tile_lds). ---------------------------------------------------------------
 
-    const int b = blockIdx.x / p.nslices;
-    const int sl = blockIdx.x - b * p.nslices;
-    const int row0 = p.node_off[b];
-    const int n = p.node_off[b + 1] - row0;
-    const int col0 = sl * FS;
-    const int32_t* rp = p.rowptr + p.b_rp_off[b];
-    const uint16_t* cl = p.col + p.b_col_off[b];
-    const int32_t* drp = p.deg_rowptr + p.b_deg_off[b];
-    const int tid = threadIdx.x;
-    const int nthreads = blockDim.x;
-    const bool vec_in = ((p.ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.x) & 15) == 0);
-    const bool vec_h = p.hfwd && ((p.ldh & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.hfwd) & 15) == 0);
-    const bool prescale = p.backward && p.average;
-
-    // ---- phase A: HBM -> LDS, coalesced; optional 1/deg pre-scale and d-eps dot ----
-    double dot = 0.0;
-    int i0 = tid;
-    // d eps: dot(x, hfwd) on the way in, or -- STATS launches without hfwd -- from the rows the epilogue holds.  The
-    // launcher only starts the fused forms on full-width, 16-byte addressable slices, and a thread keeps the column
-    // chunk tid & (LPR - 1) for all its rows (the workgroup size is a multiple of LPR).
-    const bool dot_a = p.deps_partial && (!STATS || p.hfwd);
-    float4 psc = make_float4(1.f, 1.f, 1.f, 1.f), psh = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 csum = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (PRO) {
-        psc = *reinterpret_cast<const float4*>(p.p_scale + col0 + 4 * (tid & (LPR - 1)));
-        psh = *reinterpret_cast<const float4*>(p.p_shift + col0 + 4 * (tid & (LPR - 1)));
+// ---- phase B, narrow features (FS <= 16 floats): one THREAD per (row, 16-B chunk) ------
+// The rows are so short that the wave-cooperative scheme below spends its time in
+// cross-lane reductions and dependent loads.  Here the graph's column ids are staged in
+// LDS as well (p.ids_in_lds, decided by the launcher), a thread walks its row's ids 8 at a
+// time (8 independent LDS id reads, then 8 row reads) and owns its output chunk outright.
+template <int LPR>
+__device__ __forceinline__ void agg_rows_staged(const AggArgs& p, const AggBlock& k, char* smem, const AggTileLds& lds,
+                                                float selfB, bool vec_out) {
+    const float4* tile = reinterpret_cast<const float4*>(smem);
+    const int n = k.n, col0 = k.col0, tid = threadIdx.x, nthreads = blockDim.x;
+    const int32_t* rp = k.rp;
+    const uint16_t* cl = k.cl;
+    // ids[e] = cl[e], staged with 16-B copies, 4 per thread in flight (64 KB per workgroup): with 4-B
+    // copies only 16 KB were in flight per CU and this copy alone bounded the kernel at ~2 TB/s.
+    // The LDS image is shifted by the source's misalignment so that both sides are 16-B aligned
+    // together; the copy may run up to 7 ids before / 8 ids past the graph's block (the arena keeps
+    // readable slack after the last block, and a block never starts at the buffer's first 16 bytes
+    // unless it is aligned).
+    const int mis = (int)((reinterpret_cast<uintptr_t>(cl) & 15) >> 1);          // ids before alignment
+    uint16_t* ids = reinterpret_cast<uint16_t*>(smem + lds.ids) + mis;
+    const int nnz = p.y ? rp[n] : 0;            // y == null (d-eps only): nothing to gather
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(cl - mis);
+        uint4* dst = reinterpret_cast<uint4*>(ids - mis);
+        const int nq = (nnz + mis + 7) >> 3;
+        int e = tid;
+        for (; e + 3 * nthreads < nq; e += 4 * nthreads) {
+            const uint4 v0 = src[e], v1 = src[e + nthreads], v2 = src[e + 2 * nthreads], v3 = src[e + 3 * nthreads];
+            dst[e] = v0; dst[e + nthreads] = v1; dst[e + 2 * nthreads] = v2; dst[e + 3 * nthreads] = v3;
+        }
+        for (; e < nq; e += nthreads) dst[e] = src[e];
     }
-    auto prologue = [&](int i, float4 w) -> float4 {      // (PRO) the activation of tile element i, written and summed
-        w.x = gnm_relu(w.x * psc.x + psh.x); w.y = gnm_relu(w.y * psc.y + psh.y);
-        w.z = gnm_relu(w.z * psc.z + psh.z); w.w = gnm_relu(w.w * psc.w + psh.w);
-        if (p.p_hout) *reinterpret_cast<float4*>(p.p_hout + (size_t)(row0 + i / LPR) * p.p_ldh + col0 + 4 * (i & (LPR - 1))) = w;
-        csum.x += w.x; csum.y += w.y; csum.z += w.z; csum.w += w.w;
-        return w;
-    };
-    // full-width, 16-byte addressable slices: 8 x 16 B per thread in flight (the loop below issues ONE load per trip,
-    // inside a lane-dependent branch, i.e. one memory round trip per 16 KB of the tile: 16-32 us of a 128 KB tile)
-    if (vec_in && col0 + FS <= p.F && (!dot_a || vec_h)) {       // wave-uniform
-        constexpr int UA = 8;
-        const int total = n * LPR;
-        for (; i0 + (UA - 1) * nthreads < total; i0 += UA * nthreads) {
-            float4 v[UA];
-#pragma unroll
-            for (int u = 0; u < UA; ++u) {
-                const int i = i0 + u * nthreads;
-                const int r = i / LPR, c = i - r * LPR;
-                v[u] = *reinterpret_cast<const float4*>(p.x + (size_t)(row0 + r) * p.ldx + col0 + 4 * c);
-            }
-            if (dot_a) {
-#pragma unroll
-                for (int u = 0; u < UA; ++u) {
-                    const int i = i0 + u * nthreads;
-                    const int r = i / LPR, c = i - r * LPR;
-                    const float4 h = *reinterpret_cast<const float4*>(p.hfwd + (size_t)(row0 + r) * p.ldh + col0 + 4 * c);
-                    dot += (double)v[u].x * h.x + (double)v[u].y * h.y + (double)v[u].z * h.z + (double)v[u].w * h.w;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UA; ++u) {
-                const int i = i0 + u * nthreads;
-                float4 w = v[u];
-                if (prescale) {
-                    const int r = i / LPR;
-                    const float d = (float)(drp[r + 1] - drp[r] + p.self_loop);
-                    w.x /= d; w.y /= d; w.z /= d; w.w /= d;
-                }
-                if constexpr (PRO) w = prologue(i, w);
-                tile[i] = w;
-            }
-        }
-    }
-    for (int i = i0; i < n * LPR; i += nthreads) {
-        const int r = i / LPR;
-        const int c = i - r * LPR;
-        const int cc = col0 + 4 * c;
-        const float* src = p.x + (size_t)(row0 + r) * p.ldx + cc;
-        float4 v;
-        if (vec_in && cc + 3 < p.F) {
-            v = *reinterpret_cast<const float4*>(src);
-        } else {
-            v.x = (cc + 0 < p.F) ? src[0] : 0.f;
-            v.y = (cc + 1 < p.F) ? src[1] : 0.f;
-            v.z = (cc + 2 < p.F) ? src[2] : 0.f;
-            v.w = (cc + 3 < p.F) ? src[3] : 0.f;
-        }
-        if (dot_a) {
-            const float* hs = p.hfwd + (size_t)(row0 + r) * p.ldh + cc;
-            float4 h;
-            if (vec_h && cc + 3 < p.F) {
-                h = *reinterpret_cast<const float4*>(hs);
-            } else {
-                h.x = (cc + 0 < p.F) ? hs[0] : 0.f;
-                h.y = (cc + 1 < p.F) ? hs[1] : 0.f;
-                h.z = (cc + 2 < p.F) ? hs[2] : 0.f;
-                h.w = (cc + 3 < p.F) ? hs[3] : 0.f;
-            }
-            dot += (double)v.x * h.x + (double)v.y * h.y + (double)v.z * h.z + (double)v.w * h.w;
-        }
-        if (prescale) {
-            const float d = (float)(drp[r + 1] - drp[r] + p.self_loop);
-            v.x /= d; v.y /= d; v.z /= d; v.w /= d;
-        }
-        if constexpr (PRO) v = prologue(i, v);
-        tile[i] = v;
-    }
-    constexpr int ZR = LPR == 8 ? 2 : 1;       // zero rows behind the tile (LPR == 8: one of each parity, see phase B)
-    if (tid < ZR * LPR) tile[n * LPR + tid] = make_float4(0.f, 0.f, 0.f, 0.f);  // row n (, n + 1) = zeros (padding slots)
-    // row offsets staged behind the tile (wave-cooperative path only: the narrow path keeps its id block there)
-    int* rp_s = reinterpret_cast<int*>(smem + (size_t)(n + ZR) * (FS * 4));
-    const bool stage_rp = !(LPR <= 4 && p.ids_in_lds);
-    if (stage_rp)
-        for (int i = tid; i <= n; i += nthreads) rp_s[i] = rp[i];
-    if (LPR == 8 && tid == 0) rp_s[n + 1] = nthreads >> 6;      // the group ticket (phase B): every wave's first group is its own number
-    // LDS behind the row offsets (LPR == 8): the waves' id scratch (16 x 1 KB, ids_in_lds == 2), then the prologue's
-    // readout shares ([waves][8] float4)
-    const size_t scr_off = ((size_t)(n + ZR) * (FS * 4) + (size_t)(n + 2) * 4 + 16 + 15) & ~(size_t)15;
-    float4* const rsum = reinterpret_cast<float4*>(smem + scr_off + (p.ids_in_lds == 2 ? 16 * 1024 : 0));
-    if constexpr (PRO) {
-        if (p.p_gf) {      // the 8 lanes of a wave that share a column chunk (lane bits 3-5), then the waves (below)
-#pragma unroll
-            for (int off = 8; off < 64; off <<= 1) {
-                csum.x += __shfl_xor(csum.x, off, 64); csum.y += __shfl_xor(csum.y, off, 64);
-                csum.z += __shfl_xor(csum.z, off, 64); csum.w += __shfl_xor(csum.w, off, 64);
-            }
-            if ((tid & 63) < 8) rsum[(tid >> 6) * 8 + (tid & 7)] = csum;
-        }
-    }
-    GNM_GSTAMP(1)
-    GNM_GSTAMP(2)
     __syncthreads();
-    GNM_GSTAMP(3)
-    if constexpr (PRO) {
-        if (p.p_gf && tid < 8) {      // graph readout of the activation just formed (graphcnn.py:229), in wave order
-            float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int w = 0; w < (nthreads >> 6); ++w) acc4(t, rsum[w * 8 + tid]);
-            if (p.p_gf_avg) {
-                const float inv = 1.f / (float)n;
-                t.x *= inv; t.y *= inv; t.z *= inv; t.w *= inv;
-            }
-            *reinterpret_cast<float4*>(p.p_gf + (size_t)b * p.p_ldgf + col0 + 4 * tid) = t;
-        }
-    }
-
-    // ---- phase B, narrow features (FS <= 16 floats): one THREAD per (row, 16-B chunk) ------
-    // The rows are so short that the wave-cooperative scheme below spends its time in
-    // cross-lane reductions and dependent loads.  Here the graph's column ids are staged in
-    // LDS as well (p.ids_in_lds, decided by the launcher), a thread walks its row's ids 8 at a
-    // time (8 independent LDS id reads, then 8 row reads) and owns its output chunk outright.
-    if constexpr (LPR <= 4) {
-        if (p.ids_in_lds) {
-            // ids[e] = cl[e], staged with 16-B copies, 4 per thread in flight (64 KB per workgroup): with 4-B
-            // copies only 16 KB were in flight per CU and this copy alone bounded the kernel at ~2 TB/s.
-            // The LDS image is shifted by the source's misalignment so that both sides are 16-B aligned
-            // together; the copy may run up to 7 ids before / 8 ids past the graph's block (the arena keeps
-            // readable slack after the last block, and a block never starts at the buffer's first 16 bytes
-            // unless it is aligned).
-            const int mis = (int)((reinterpret_cast<uintptr_t>(cl) & 15) >> 1);          // ids before alignment
-            uint16_t* ids = reinterpret_cast<uint16_t*>(smem + (((size_t)(n + 1) * (FS * 4) + 15) & ~(size_t)15)) + mis;
-            const int nnz = p.y ? rp[n] : 0;            // y == null (d-eps only): nothing to gather
-            {
-                const uint4* src = reinterpret_cast<const uint4*>(cl - mis);
-                uint4* dst = reinterpret_cast<uint4*>(ids - mis);
-                const int nq = (nnz + mis + 7) >> 3;
-                int e = tid;
-                for (; e + 3 * nthreads < nq; e += 4 * nthreads) {
-                    const uint4 v0 = src[e], v1 = src[e + nthreads], v2 = src[e + 2 * nthreads], v3 = src[e + 3 * nthreads];
-                    dst[e] = v0; dst[e + nthreads] = v1; dst[e + 2 * nthreads] = v2; dst[e + 3 * nthreads] = v3;
-                }
-                for (; e < nq; e += nthreads) dst[e] = src[e];
-            }
-            __syncthreads();
-            const float selfB2 = p.self_loop ? 0.f : (p.eps ? 1.f + *p.eps : 1.f);
-            const bool vec_out2 = ((p.ldy & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.y) & 15) == 0);
-            for (int w = tid; p.y && w < n * LPR; w += nthreads) {
-                const int v = w / LPR, sub2 = w - v * LPR;
-                const int beg = rp[v], end = rp[v + 1];
-                float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                int e = beg;
-                for (; e + 8 <= end; e += 8) {
-                    unsigned id[8];
+    for (int w = tid; p.y && w < n * LPR; w += nthreads) {
+        const int v = w / LPR, sub2 = w - v * LPR;
+        const int beg = rp[v], end = rp[v + 1];
+        float4 acc = zero4();
+        int e = beg;
+        for (; e + 8 <= end; e += 8) {
+            unsigned id[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) id[j] = ids[e + j];
+            for (int j = 0; j < 8; ++j) id[j] = ids[e + j];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) acc4(acc, tile[id[j] * LPR + sub2]);
-                }
-                for (; e < end; ++e) acc4(acc, tile[(unsigned)ids[e] * LPR + sub2]);
-                const float4 self = tile[v * LPR + sub2];
-                if (p.self_loop) acc4(acc, self);
-                if (!p.backward && p.average) {
-                    const float d = (float)(end - beg + p.self_loop);
-                    acc.x /= d; acc.y /= d; acc.z /= d; acc.w /= d;
-                }
-                const int cc = col0 + 4 * sub2;
-                if (!p.self_loop) {
-                    float4 sb = self;
-                    if (prescale) {
-                        const float* src = p.x + (size_t)(row0 + v) * p.ldx + cc;
-                        sb.x = (cc + 0 < p.F) ? src[0] : 0.f;
-                        sb.y = (cc + 1 < p.F) ? src[1] : 0.f;
-                        sb.z = (cc + 2 < p.F) ? src[2] : 0.f;
-                        sb.w = (cc + 3 < p.F) ? src[3] : 0.f;
-                    }
-                    acc.x += selfB2 * sb.x; acc.y += selfB2 * sb.y; acc.z += selfB2 * sb.z; acc.w += selfB2 * sb.w;
-                }
-                float* dst = p.y + (size_t)(row0 + v) * p.ldy + cc;
-                if (vec_out2 && cc + 3 < p.F) {
-                    *reinterpret_cast<float4*>(dst) = acc;
-                } else {
-                    if (cc + 0 < p.F) dst[0] = acc.x;
-                    if (cc + 1 < p.F) dst[1] = acc.y;
-                    if (cc + 2 < p.F) dst[2] = acc.z;
-                    if (cc + 3 < p.F) dst[3] = acc.w;
-                }
-            }
-            if (p.deps_partial) {
-                __syncthreads();
-                double* red = reinterpret_cast<double*>(smem);
-                const double ws = wave_sum_d(dot);
-                if ((tid & 63) == 0) red[tid >> 6] = ws;
-                __syncthreads();
-                if (tid == 0) {
-                    double s2 = 0.0;
-                    for (int k = 0; k < (nthreads >> 6); ++k) s2 += red[k];
-                    p.deps_partial[blockIdx.x] = s2;
-                }
-            }
-            return;
+            for (int j = 0; j < 8; ++j) acc4(acc, tile[id[j] * LPR + sub2]);
         }
+        for (; e < end; ++e) acc4(acc, tile[(unsigned)ids[e] * LPR + sub2]);
+        agg_row_out(p, k, acc, tile[v * LPR + sub2], v, sub2, end - beg, selfB, vec_out);
     }
+}
 
-    // ---- phase B: gather neighbour rows from LDS --------------------------------
+// ---- 32-float slices (8 lanes per row, 8 neighbours per wave-instruction): GROUPS OF 8 ROWS per wave ----------
+// Row r of a group is gathered by all 8 lane groups (each takes every 8th neighbour); the 8 x 8 partial sums are
+// then combined by a transposing butterfly -- v_permlane32_swap, v_permlane16_swap, DPP row_ror:8 -- after which lane
+// group k owns the whole sum of row k and all 64 lanes run the epilogue and store 1 KiB.  No ds_bpermute and no
+// per-row global round trip: the 9 row offsets come from LDS as a lane vector fetched one group ahead, the 8 id
+// chunks of a group are requested together.  MODE 2 (STATS) adds its d-eps terms to `dot`.
+template <int MODE>
+__device__ __forceinline__ void agg_rows_group8(const AggArgs& p, const AggBlock& k, char* smem, const AggTileLds& lds,
+                                                float selfB, bool vec_out, double& dot) {
+    constexpr int LPR = 8, FS = 32, SLOTS = 8;
+    constexpr bool STATS = MODE == 2;
+    const float4* tile = reinterpret_cast<const float4*>(smem);
+    const int* rp_s = reinterpret_cast<const int*>(smem + lds.rp);
+    const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    const int b = k.b, row0 = k.row0, n = k.n, col0 = k.col0, tid = threadIdx.x;
+    const uint16_t* cl = k.cl;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nwaves = nthreads >> 6;
+    const int nwaves = blockDim.x >> 6;
+    const int sub = lane & (LPR - 1);          // 16-B chunk of the row this lane owns
+    const int slot = lane / LPR;               // which of the SLOTS concurrent neighbours
+    const unsigned subb = lds_base + (unsigned)sub * 16u;   // LDS byte address of this lane's chunk in row 0
+    const int jlane = sub * SLOTS + slot;      // edge (within a 64-chunk) whose id this lane fetches
+    // Bank conflicts (round 4).  A 128-byte row lies on banks 0-31 or 32-63 by the parity of its index, and the
+    // hardware serves a ds_read_b128 in 16-lane groups that put the neighbours of slots (0, 3), (1, 2), (4, 7),
+    // (5, 6) on the same cycle: equal parity there = a 2-way conflict (a third of this kernel's LDS cycles in
+    // round 3's PMC).  The arena orders every CSR row so that slots 0, 1, 4, 5 get even ids and slots 2, 3, 6, 7
+    // odd ones while the row has both (host.cpp gnm_csr_parity_order); padding slots read the zero row of the
+    // parity their slot wants (rows n and n + 1 are both zero).
+    const unsigned zero_row_pad = (unsigned)(n + ((n ^ (slot >> 1)) & 1)) * (FS * 4);
+    const int ngroups = p.y ? (n + 7) >> 3 : 0;
+    const unsigned jl2 = 2u * (unsigned)jlane;
+    const bool hi8 = (lane & 8) != 0;
+    // Round 4: groups are handed out by an LDS ticket (a wave's first group is its own number, the counter starts
+    // at nwaves) -- the static deal left the median wave idle for 17 % of the workgroup's life behind the waves
+    // whose rows happened to have more than 32 neighbours (in-kernel timeline, profiles/r04_c4_timeline.md) -- and
+    // the NEXT group's row bounds and first id chunks are requested in the middle of the current one (one exposed
+    // L2 round trip per group before).  A row's own sum does not depend on which wave takes it.
+    int* const ticket = reinterpret_cast<int*>(smem + lds.ticket);
+    // wave-private id scratch behind the row offsets (8 rows x 64 positions x 2 bytes per wave), when the launcher
+    // found room for it (ids_in_lds == 2)
+    const bool stage8 = p.ids_in_lds == 2;
+    const unsigned scr0 = lds_base + (unsigned)lds.scr + (unsigned)wave * kAggIdScratch;
+    // scratch row layout [slot][step]: the 8 ids a slot reads over the steps of a row are 16 contiguous bytes, so
+    // steps 0-3 (4-7) come with ONE ds_read_b64 each -- eight 2-byte reads per row cost half as many LDS cycles
+    // as the row gather itself (the kernel became LDS-pipe bound once the DPP moves were gone)
+    const unsigned scr_w = scr0 + 2u * (unsigned)((jlane & 7) * 8 + (jlane >> 3)), scr_r = scr0 + 16u * (unsigned)slot;
+    const unsigned zero_id = (unsigned)(n + ((n ^ (slot >> 1)) & 1));
+    int g = wave;
+    int rpv = 0;
+    unsigned raw[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) raw[r] = 0u;
+    if (g < ngroups) {
+        rpv = rp_s[min(8 * g + (lane & 15), n)];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) raw[r] = load_id(cl, 2u * (unsigned)__builtin_amdgcn_readlane(rpv, r) + jl2);
+    }
+    // STATS: per-lane column sums of the rows this lane group ends up owning, and the per-column constants of the
+    // layer below (chunk `sub` of this slice).  The deal of groups is STATIC there (wave, wave + W, ...): the sums
+    // are accumulated per wave, and with tickets their order -- hence their last bits -- would change from launch
+    // to launch (every reduction of this library has a fixed order).
+    float4 ss1 = zero4(), ss2 = ss1, s_pb = ss1, s_ub = ss1;
+    float4 lsc = ss1, lsh = ss1, lmu = ss1;
+    if constexpr (STATS) stats_load_consts(p, b, n, col0, sub, lsc, lsh, lmu, s_pb, s_ub);
+    while (g < ngroups) {                                       // wave-uniform
+        int gn = g + nwaves;
+        if constexpr (!STATS) {
+            gn = 0;
+            if (lane == 0) gn = atomicAdd(ticket, 1);            // (read after the first four rows)
+        }
+        int bnd[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) bnd[i] = __builtin_amdgcn_readlane(rpv, i);
+        const int v = 8 * g + slot;
+        const float4 self = tile[min(v, n) * LPR + sub];       // ahead of the gather (row n = zeros)
+        float4 zrow = make_float4(0.f, 0.f, 0.f, 0.f);
+        float dsc_v = 0.f;
+        if constexpr (STATS) {     // requested ahead of the gather, consumed in the epilogue
+            const int vc = row0 + min(v, n - 1);
+            zrow = *reinterpret_cast<const float4*>(p.sZ + (size_t)vc * p.ldsz + col0 + 4 * sub);
+            if (p.s_dsc1) dsc_v = p.s_dsc1[vc];
+        }
+        float4 acc[8];
+        int nrpv = 0;
+        agg_u32x2 idn = {0u, 0u};
+        if (stage8) {
+            // ids through a wave-private LDS scratch (round 4): a lane's id of row r goes to scratch[r][position]
+            // (padding positions: the zero row of the slot's parity), and step S of slot k reads position 8 S + k
+            // back with an immediate offset -- one 2-byte LDS read and one shift-add per step instead of two
+            // bank-masked DPP moves, a zero fill and an add (the kernel is VALU-issue bound: ~35 VALU per row).
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int cnt = min(64, bnd[r + 1] - bnd[r]);
+                lds_write_u16(scr_w + 128u * r, (jlane < cnt) ? raw[r] : zero_id);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            idn = lds_read_u32x2(scr_r);
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if (r == 4) {                                       // the next group's bounds: an LDS read under rows 4-7
+                gn = __builtin_amdgcn_readfirstlane(gn);
+                nrpv = rp_s[min(8 * gn + (lane & 15), n)];      // (exhausted ticket: every bound = rp[n], reads the slack)
+            }
+            const int beg = bnd[r], end = bnd[r + 1];
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+            int e0 = beg;
+            if (stage8) {
+                // (every position of the scratch row holds a valid id -- padding = a zero row -- so the first four
+                //  steps need no guard, and the ids of row r + 1 are requested before row r's rows are waited for:
+                //  one exposed LDS round trip per row instead of two)
+                const unsigned rb = scr_r + 128u * r;
+                const unsigned i0 = idn.x & 0xFFFFu, i1 = idn.x >> 16, i2 = idn.y & 0xFFFFu, i3 = idn.y >> 16;
+                if (r < 7) idn = lds_read_u32x2(rb + 128u);
+                {
+                    const f32x4 t0 = lds_read16((i0 << 7) + subb), t1 = lds_read16((i1 << 7) + subb),
+                                t2 = lds_read16((i2 << 7) + subb), t3 = lds_read16((i3 << 7) + subb);
+                    acc4(a, (t0 + t1) + (t2 + t3));
+                }
+                if (end - beg > 32) {                          // wave-uniform
+                    const agg_u32x2 jj = lds_read_u32x2(rb + 8u);
+                    const unsigned j0 = jj.x & 0xFFFFu, j1 = jj.x >> 16, j2 = jj.y & 0xFFFFu, j3 = jj.y >> 16;
+                    const f32x4 t0 = lds_read16((j0 << 7) + subb), t1 = lds_read16((j1 << 7) + subb),
+                                t2 = lds_read16((j2 << 7) + subb), t3 = lds_read16((j3 << 7) + subb);
+                    acc4(a, (t0 + t1) + (t2 + t3));
+                }
+                e0 = beg + 64;                                  // (rows of more than 64 neighbours: the chunks below)
+            }
+            for (; e0 < end; e0 += 64) {
+                const int cnt = min(64, end - e0);
+                const unsigned rw = (e0 == beg) ? raw[r] : load_id(cl, 2u * (unsigned)e0 + jl2);
+                const unsigned valb = (jlane < cnt) ? rw * (FS * 4) : zero_row_pad;
+                {
+                    const f32x4 t0 = lds_read16(bcast8<0>(valb) + subb), t1 = lds_read16(bcast8<1>(valb) + subb),
+                                t2 = lds_read16(bcast8<2>(valb) + subb), t3 = lds_read16(bcast8<3>(valb) + subb);
+                    acc4(a, (t0 + t1) + (t2 + t3));
+                }
+                if (cnt > 32) {                                // wave-uniform: steps 4..7 hold something
+                    const f32x4 t0 = lds_read16(bcast8<4>(valb) + subb), t1 = lds_read16(bcast8<5>(valb) + subb),
+                                t2 = lds_read16(bcast8<6>(valb) + subb), t3 = lds_read16(bcast8<7>(valb) + subb);
+                    acc4(a, (t0 + t1) + (t2 + t3));
+                }
+            }
+            acc[r] = a;
+        }
+        // the next group's first id chunks: in flight under the combine, the epilogue and the stores
+#pragma unroll
+        for (int r = 0; r < 8; ++r) raw[r] = load_id(cl, 2u * (unsigned)__builtin_amdgcn_readlane(nrpv, r) + jl2);
+        // transposing combine: lane bit 5 picks rows {0-3 | 4-7}, bit 4 {r | r+2}, bit 3 {r | r+1}
+        const float4 b0 = swap_add32(acc[0], acc[4]), b1 = swap_add32(acc[1], acc[5]);
+        const float4 b2 = swap_add32(acc[2], acc[6]), b3 = swap_add32(acc[3], acc[7]);
+        const float4 c0 = swap_add16(b0, b2), c1 = swap_add16(b1, b3);
+        const float4 mine = hi8 ? c1 : c0, theirs = hi8 ? c0 : c1;
+        float4 tot = add_ror8(mine, theirs);
+        if (v < n) {
+            const int beg = bnd_of(rpv, slot), end = bnd_of(rpv, slot + 1);
+            if (p.self_loop) acc4(tot, self);
+            if (!p.backward && p.average) div4(tot, (float)(end - beg + p.self_loop));   // 0/0 -> NaN as in the reference
+            const int cc = col0 + 4 * sub;
+            if (!p.self_loop) {
+                float4 sb = self;
+                if (k.prescale)   // the tile holds dp/deg; the (1+eps) term needs dp itself
+                    sb = load4_guarded(p.x + (size_t)(row0 + v) * p.ldx + cc, cc, p.F);
+                fma4(tot, selfB, sb);
+                if constexpr (STATS) {
+                    if (p.deps_partial && !p.hfwd) dot += stats_deps_term<false>(sb, zrow, lsc, lsh);
+                }
+            }
+            if constexpr (STATS) stats_row(p, tot, zrow, dsc_v, row0 + v, col0, sub, lsc, lsh, lmu, s_pb, s_ub, ss1, ss2);
+            // the full-width test is wave-uniform: ONE 16-byte store per lane (see agg16)
+            store4<true>(p.y + (size_t)(row0 + v) * p.ldy + cc, tot, vec_out && col0 + FS <= p.F, cc, p.F);
+        }
+        rpv = nrpv;
+        g = gn;
+    }
+    GNM_STAMP(63)
+    if constexpr (STATS) stats_col_reduce<8>(p, smem, ss1, ss2, tid, lane, wave, nwaves, sub, col0, (size_t)b, p.F);
+}
+
+// ---- 8-float rows (the input layer, F0 <= 8): 2 lanes per neighbour row, 32 neighbours per wave-instruction,
+// GROUPS OF 16 ROWS per wave.  Lane bit 2 is the 16-B chunk; the other five bits number the 32 neighbour slots,
+// so both lanes of a slot load the same column id themselves (no cross-lane traffic at all), and the 16 x 32
+// partial sums are transposed and added over lane bits 5, 4, 3 (permlane swaps, DPP row_ror:8) and 1, 0
+// (DPP quad_perm): lanes {bit5, bit4, bit3, bit1} = k end up with row k.
+__device__ __forceinline__ void agg_rows_group16(const AggArgs& p, const AggBlock& k, char* smem, const AggTileLds& lds,
+                                                float selfB, bool vec_out) {
+    const float4* tile = reinterpret_cast<const float4*>(smem);
+    const int* rp_s = reinterpret_cast<const int*>(smem + lds.rp);
+    const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    const int n = k.n, col0 = k.col0;
+    const uint16_t* cl = k.cl;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nwaves = blockDim.x >> 6;
+    const int ngroups = p.y ? (n + 15) >> 4 : 0;
+    const int q2 = (lane >> 2) & 1;                                   // chunk of the 32-B row
+    const unsigned p5 = (unsigned)(((lane >> 3) << 2) | (lane & 3));   // neighbour slot 0..31
+    const unsigned sub2b = lds_base + (unsigned)q2 * 16u;
+    const unsigned zero2 = sub2b + (unsigned)n * 32u;
+    const bool b3 = (lane & 8) != 0, b1 = (lane & 2) != 0;
+    const int krow = ((lane >> 3) << 1) | ((lane >> 1) & 1);          // row of the group this lane ends up owning
+    int g = wave;
+    int rpv = 0, nrpv = 0;
+    if (g < ngroups) rpv = rp_s[min(16 * g + (lane & 31), n)];
+    unsigned nr0 = 0, nr1 = 0, nr2 = 0, nr3 = 0;                        // ids of the NEXT row (4 chunks of 32)
+    if (g < ngroups) {
+        const unsigned o = 2u * ((unsigned)__builtin_amdgcn_readlane(rpv, 0) + p5);
+        nr0 = load_id(cl, o); nr1 = load_id(cl, o + 64u); nr2 = load_id(cl, o + 128u); nr3 = load_id(cl, o + 192u);
+    }
+    for (; g < ngroups; g += nwaves) {
+        const bool more = g + nwaves < ngroups;
+        if (more) nrpv = rp_s[min(16 * (g + nwaves) + (lane & 31), n)];
+        const int v = 16 * g + krow;
+        const float4 self = tile[min(v, n) * 2 + q2];
+        float4 acc[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int beg = __builtin_amdgcn_readlane(rpv, r), end = __builtin_amdgcn_readlane(rpv, r + 1);
+            const unsigned r0 = nr0, r1 = nr1, r2 = nr2, r3 = nr3;
+            // the next row's ids (row r + 1 of this group, or row 0 of this wave's next group), unconditionally
+            {
+                const int nb = (r < 15) ? end : __builtin_amdgcn_readlane(nrpv, 0);
+                if (r < 15 || more) {                              // wave-uniform
+                    const unsigned o = 2u * ((unsigned)nb + p5);
+                    nr0 = load_id(cl, o); nr1 = load_id(cl, o + 64u); nr2 = load_id(cl, o + 128u); nr3 = load_id(cl, o + 192u);
+                }
+            }
+            const int cnt = end - beg;
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (cnt > 0) {
+                const unsigned a0 = ((int)p5 < cnt) ? (r0 << 5) + sub2b : zero2;
+                const unsigned a1 = ((int)p5 + 32 < cnt) ? (r1 << 5) + sub2b : zero2;
+                if (cnt > 64) {
+                    const unsigned a2 = ((int)p5 + 64 < cnt) ? (r2 << 5) + sub2b : zero2;
+                    const unsigned a3 = ((int)p5 + 96 < cnt) ? (r3 << 5) + sub2b : zero2;
+                    const f32x4 t0 = lds_read16(a0), t1 = lds_read16(a1), t2 = lds_read16(a2), t3 = lds_read16(a3);
+                    acc4(a, (t0 + t1) + (t2 + t3));
+                    for (int e0 = beg + 128; e0 < end; e0 += 32) {       // degree > 128: fetched in place
+                        const unsigned rw = load_id(cl, 2u * ((unsigned)e0 + p5));
+                        const unsigned ax = ((int)p5 < end - e0) ? (rw << 5) + sub2b : zero2;
+                        acc4(a, lds_read16(ax));
+                    }
+                } else {
+                    const f32x4 t0 = lds_read16(a0), t1 = lds_read16(a1);
+                    acc4(a, t0 + t1);
+                }
+            }
+            acc[r] = a;
+        }
+        // transposing combine over lane bits 5, 4, 3, 1, then the plain sum over bit 0
+        float4 b8[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b8[j] = swap_add32(acc[j], acc[j + 8]);
+        float4 c4[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c4[j] = swap_add16(b8[j], b8[j + 4]);
+        float4 d2[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float4 mine = b3 ? c4[j + 2] : c4[j], theirs = b3 ? c4[j] : c4[j + 2];
+            d2[j] = add_ror8(mine, theirs);
+        }
+        const float4 mine = b1 ? d2[1] : d2[0], theirs = b1 ? d2[0] : d2[1];
+        float4 tot;
+        tot.x = mine.x + qxor2(theirs.x); tot.y = mine.y + qxor2(theirs.y);
+        tot.z = mine.z + qxor2(theirs.z); tot.w = mine.w + qxor2(theirs.w);
+        tot.x += qxor1(tot.x); tot.y += qxor1(tot.y); tot.z += qxor1(tot.z); tot.w += qxor1(tot.w);
+        int degk = 0;
+        if (!p.backward && p.average) degk = bnd_of(rpv, krow + 1) - bnd_of(rpv, krow);
+        if (v < n && (lane & 1) == 0)
+            agg_row_out(p, k, tot, self, v, q2, degk, selfB, vec_out);
+        rpv = nrpv;
+    }
+}
+
+// ---- the wave-cooperative fallback (128-float slices; 16-float slices whose ids are not staged): one wave per
+// destination row, LPR lanes per neighbour row, 64 / LPR neighbours per wave-instruction.
+// y == null: only the d-eps dot product of phase A is wanted.
+// Nothing on the per-row path is a dependent global round trip: the row bounds come from LDS two rows ahead,
+// the row's first 64 column ids are requested one row ahead (unconditional loads: the arena keeps readable
+// slack behind the last block), and the ids of a chunk reach the lane groups by a BATCH of ds_bpermute issued
+// before the reads.
+template <int LPR>
+__device__ __forceinline__ void agg_rows_wave(const AggArgs& p, const AggBlock& k, char* smem, const AggTileLds& lds,
+                                                float selfB, bool vec_out) {
+    constexpr int FS = LPR * 4, SLOTS = 64 / LPR;
+    const float4* tile = reinterpret_cast<const float4*>(smem);
+    const int* rp_s = reinterpret_cast<const int*>(smem + lds.rp);
+    const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    const int n = k.n, col0 = k.col0;
+    const uint16_t* cl = k.cl;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nwaves = blockDim.x >> 6;
     const int sub = lane & (LPR - 1);          // 16-B chunk of the row this lane owns
     const int slot = lane / LPR;               // which of the SLOTS concurrent neighbours
     const unsigned subb = lds_base + (unsigned)sub * 16u;   // LDS byte address of this lane's chunk in row 0
     const int jlane = sub * SLOTS + slot;      // edge (within a 64-chunk) whose id this lane fetches
     const unsigned zero_row_b = (unsigned)n * (FS * 4);
-    const float selfB = p.self_loop ? 0.f : (p.eps ? 1.f + *p.eps : 1.f);
-    const bool vec_out = ((p.ldy & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.y) & 15) == 0);
-
-    // ---- 32-float slices (8 lanes per row, 8 neighbours per wave-instruction): GROUPS OF 8 ROWS per wave ----------
-    // Row r of a group is gathered by all 8 lane groups (each takes every 8th neighbour); the 8 x 8 partial sums are
-    // then combined by a transposing butterfly -- v_permlane32_swap, v_permlane16_swap, DPP row_ror:8 -- after which lane
-    // group k owns the whole sum of row k and all 64 lanes run the epilogue and store 1 KiB.  No ds_bpermute and no
-    // per-row global round trip: the 9 row offsets come from LDS as a lane vector fetched one group ahead, the 8 id
-    // chunks of a group are requested together.
-    if constexpr (LPR == 8) {
-        // Bank conflicts (round 4).  A 128-byte row lies on banks 0-31 or 32-63 by the parity of its index, and the
-        // hardware serves a ds_read_b128 in 16-lane groups that put the neighbours of slots (0, 3), (1, 2), (4, 7),
-        // (5, 6) on the same cycle: equal parity there = a 2-way conflict (a third of this kernel's LDS cycles in
-        // round 3's PMC).  The arena orders every CSR row so that slots 0, 1, 4, 5 get even ids and slots 2, 3, 6, 7
-        // odd ones while the row has both (host.cpp gnm_csr_parity_order); padding slots read the zero row of the
-        // parity their slot wants (rows n and n + 1 are both zero).
-        const unsigned zero_row_pad = (unsigned)(n + ((n ^ (slot >> 1)) & 1)) * (FS * 4);
-        const int ngroups = p.y ? (n + 7) >> 3 : 0;
-        const unsigned jl2 = 2u * (unsigned)jlane;
-        const bool hi8 = (lane & 8) != 0;
-        // Round 4: groups are handed out by an LDS ticket (a wave's first group is its own number, the counter starts
-        // at nwaves) -- the static deal left the median wave idle for 17 % of the workgroup's life behind the waves
-        // whose rows happened to have more than 32 neighbours (in-kernel timeline, profiles/r04_c4_timeline.md) -- and
-        // the NEXT group's row bounds and first id chunks are requested in the middle of the current one (one exposed
-        // L2 round trip per group before).  A row's own sum does not depend on which wave takes it.
-        int* const ticket = rp_s + n + 1;
-        // wave-private id scratch behind the row offsets (8 rows x 64 positions x 2 bytes per wave), when the launcher
-        // found room for it (ids_in_lds == 2)
-        const bool stage8 = p.ids_in_lds == 2;
-        const unsigned scr0 = lds_base + (unsigned)scr_off + (unsigned)wave * 1024u;
-        // scratch row layout [slot][step]: the 8 ids a slot reads over the steps of a row are 16 contiguous bytes, so
-        // steps 0-3 (4-7) come with ONE ds_read_b64 each -- eight 2-byte reads per row cost half as many LDS cycles
-        // as the row gather itself (the kernel became LDS-pipe bound once the DPP moves were gone)
-        const unsigned scr_w = scr0 + 2u * (unsigned)((jlane & 7) * 8 + (jlane >> 3)), scr_r = scr0 + 16u * (unsigned)slot;
-        const unsigned zero_id = (unsigned)(n + ((n ^ (slot >> 1)) & 1));
-        int g = wave;
-        int rpv = 0;
-        unsigned raw[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) raw[r] = 0u;
-        if (g < ngroups) {
-            rpv = rp_s[min(8 * g + (lane & 15), n)];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) raw[r] = load_id(cl, 2u * (unsigned)__builtin_amdgcn_readlane(rpv, r) + jl2);
-        }
-        // STATS: per-lane column sums of the rows this lane group ends up owning, and the per-column constants of the
-        // layer below (chunk `sub` of this slice).  The deal of groups is STATIC there (wave, wave + W, ...): the sums
-        // are accumulated per wave, and with tickets their order -- hence their last bits -- would change from launch
-        // to launch (every reduction of this library has a fixed order).
-        float4 ss1 = make_float4(0.f, 0.f, 0.f, 0.f), ss2 = ss1, s_pb = ss1, s_ub = ss1;
-        float4 lsc = ss1, lsh = ss1, lmu = ss1;
-        if constexpr (STATS) {
-            lsc = *reinterpret_cast<const float4*>(p.s_scale + col0 + 4 * sub);
-            lsh = *reinterpret_cast<const float4*>(p.s_shift + col0 + 4 * sub);
-            lmu = *reinterpret_cast<const float4*>(p.s_mean + col0 + 4 * sub);    // (rstd multiplies the column sums at the end)
-            if (p.s_dpool) {
-                s_pb = *reinterpret_cast<const float4*>(p.s_dpool + (size_t)b * p.ld_dpool + col0 + 4 * sub);
-                if (p.s_avg) {
-                    const float w = 1.0f / (float)n;
-                    s_pb.x *= w; s_pb.y *= w; s_pb.z *= w; s_pb.w *= w;
-                }
-            }
-            if (p.s_dsc1) s_ub = *reinterpret_cast<const float4*>(p.s_U + (size_t)b * p.ld_U + col0 + 4 * sub);
-        }
-        while (g < ngroups) {                                       // wave-uniform
-            int gn = g + nwaves;
-            if constexpr (!STATS) {
-                gn = 0;
-                if (lane == 0) gn = atomicAdd(ticket, 1);            // (read after the first four rows)
-            }
-            int bnd[9];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) bnd[i] = __builtin_amdgcn_readlane(rpv, i);
-            const int v = 8 * g + slot;
-            const float4 self = tile[min(v, n) * LPR + sub];       // ahead of the gather (row n = zeros)
-            float4 zrow = make_float4(0.f, 0.f, 0.f, 0.f);
-            float dsc_v = 0.f;
-            if constexpr (STATS) {     // requested ahead of the gather, consumed in the epilogue
-                const int vc = row0 + min(v, n - 1);
-                zrow = *reinterpret_cast<const float4*>(p.sZ + (size_t)vc * p.ldsz + col0 + 4 * sub);
-                if (p.s_dsc1) dsc_v = p.s_dsc1[vc];
-            }
-            float4 acc[8];
-            int nrpv = 0;
-            agg_u32x2 idn = {0u, 0u};
-            if (stage8) {
-                // ids through a wave-private LDS scratch (round 4): a lane's id of row r goes to scratch[r][position]
-                // (padding positions: the zero row of the slot's parity), and step S of slot k reads position 8 S + k
-                // back with an immediate offset -- one 2-byte LDS read and one shift-add per step instead of two
-                // bank-masked DPP moves, a zero fill and an add (the kernel is VALU-issue bound: ~35 VALU per row).
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int cnt = min(64, bnd[r + 1] - bnd[r]);
-                    lds_write_u16(scr_w + 128u * r, (jlane < cnt) ? raw[r] : zero_id);
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                idn = lds_read_u32x2(scr_r);
-            }
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                if (r == 4) {                                       // the next group's bounds: an LDS read under rows 4-7
-                    gn = __builtin_amdgcn_readfirstlane(gn);
-                    nrpv = rp_s[min(8 * gn + (lane & 15), n)];      // (exhausted ticket: every bound = rp[n], reads the slack)
-                }
-                const int beg = bnd[r], end = bnd[r + 1];
-                float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-                int e0 = beg;
-                if (stage8) {
-                    // (every position of the scratch row holds a valid id -- padding = a zero row -- so the first four
-                    //  steps need no guard, and the ids of row r + 1 are requested before row r's rows are waited for:
-                    //  one exposed LDS round trip per row instead of two)
-                    const unsigned rb = scr_r + 128u * r;
-                    const unsigned i0 = idn.x & 0xFFFFu, i1 = idn.x >> 16, i2 = idn.y & 0xFFFFu, i3 = idn.y >> 16;
-                    if (r < 7) idn = lds_read_u32x2(rb + 128u);
-                    {
-                        const f32x4 t0 = lds_read16((i0 << 7) + subb), t1 = lds_read16((i1 << 7) + subb),
-                                    t2 = lds_read16((i2 << 7) + subb), t3 = lds_read16((i3 << 7) + subb);
-                        acc4(a, (t0 + t1) + (t2 + t3));
-                    }
-                    if (end - beg > 32) {                          // wave-uniform
-                        const agg_u32x2 jj = lds_read_u32x2(rb + 8u);
-                        const unsigned j0 = jj.x & 0xFFFFu, j1 = jj.x >> 16, j2 = jj.y & 0xFFFFu, j3 = jj.y >> 16;
-                        const f32x4 t0 = lds_read16((j0 << 7) + subb), t1 = lds_read16((j1 << 7) + subb),
-                                    t2 = lds_read16((j2 << 7) + subb), t3 = lds_read16((j3 << 7) + subb);
-                        acc4(a, (t0 + t1) + (t2 + t3));
-                    }
-                    e0 = beg + 64;                                  // (rows of more than 64 neighbours: the chunks below)
-                }
-                for (; e0 < end; e0 += 64) {
-                    const int cnt = min(64, end - e0);
-                    const unsigned rw = (e0 == beg) ? raw[r] : load_id(cl, 2u * (unsigned)e0 + jl2);
-                    const unsigned valb = (jlane < cnt) ? rw * (FS * 4) : zero_row_pad;
-                    {
-                        const f32x4 t0 = lds_read16(bcast8<0>(valb) + subb), t1 = lds_read16(bcast8<1>(valb) + subb),
-                                    t2 = lds_read16(bcast8<2>(valb) + subb), t3 = lds_read16(bcast8<3>(valb) + subb);
-                        acc4(a, (t0 + t1) + (t2 + t3));
-                    }
-                    if (cnt > 32) {                                // wave-uniform: steps 4..7 hold something
-                        const f32x4 t0 = lds_read16(bcast8<4>(valb) + subb), t1 = lds_read16(bcast8<5>(valb) + subb),
-                                    t2 = lds_read16(bcast8<6>(valb) + subb), t3 = lds_read16(bcast8<7>(valb) + subb);
-                        acc4(a, (t0 + t1) + (t2 + t3));
-                    }
-                }
-                acc[r] = a;
-            }
-            // the next group's first id chunks: in flight under the combine, the epilogue and the stores
-#pragma unroll
-            for (int r = 0; r < 8; ++r) raw[r] = load_id(cl, 2u * (unsigned)__builtin_amdgcn_readlane(nrpv, r) + jl2);
-            // transposing combine: lane bit 5 picks rows {0-3 | 4-7}, bit 4 {r | r+2}, bit 3 {r | r+1}
-            const float4 b0 = swap_add32(acc[0], acc[4]), b1 = swap_add32(acc[1], acc[5]);
-            const float4 b2 = swap_add32(acc[2], acc[6]), b3 = swap_add32(acc[3], acc[7]);
-            const float4 c0 = swap_add16(b0, b2), c1 = swap_add16(b1, b3);
-            const float4 mine = hi8 ? c1 : c0, theirs = hi8 ? c0 : c1;
-            float4 tot;
-            tot.x = mine.x + ror8(theirs.x); tot.y = mine.y + ror8(theirs.y);
-            tot.z = mine.z + ror8(theirs.z); tot.w = mine.w + ror8(theirs.w);
-            if (v < n) {
-                const int beg = bnd_of(rpv, slot), end = bnd_of(rpv, slot + 1);
-                if (p.self_loop) acc4(tot, self);
-                if (!p.backward && p.average) {
-                    const float d = (float)(end - beg + p.self_loop);   // 0/0 -> NaN as in the reference
-                    tot.x /= d; tot.y /= d; tot.z /= d; tot.w /= d;
-                }
-                const int cc = col0 + 4 * sub;
-                if (!p.self_loop) {
-                    float4 sb = self;
-                    if (prescale) {   // the tile holds dp/deg; the (1+eps) term needs dp itself
-                        const float* src = p.x + (size_t)(row0 + v) * p.ldx + cc;
-                        sb.x = (cc + 0 < p.F) ? src[0] : 0.f;
-                        sb.y = (cc + 1 < p.F) ? src[1] : 0.f;
-                        sb.z = (cc + 2 < p.F) ? src[2] : 0.f;
-                        sb.w = (cc + 3 < p.F) ? src[3] : 0.f;
-                    }
-                    tot.x += selfB * sb.x; tot.y += selfB * sb.y; tot.z += selfB * sb.z; tot.w += selfB * sb.w;
-                    if constexpr (STATS) {
-                        if (p.deps_partial && !p.hfwd) {
-                            // d eps += dpooled[v] . h[v], h = relu(bn_lo(Z[v])) recomputed as the forward formed it
-                            const float hx = gnm_relu(zrow.x * lsc.x + lsh.x), hy = gnm_relu(zrow.y * lsc.y + lsh.y);
-                            const float hz = gnm_relu(zrow.z * lsc.z + lsh.z), hw = gnm_relu(zrow.w * lsc.w + lsh.w);
-                            dot += (double)(sb.x * hx + sb.y * hy) + (double)(sb.z * hz + sb.w * hw);
-                        }
-                    }
-                }
-                if constexpr (STATS) {
-                    // total gradient at this layer output = aggregation backward + readout + discriminator terms
-                    tot.x += s_pb.x + dsc_v * s_ub.x; tot.y += s_pb.y + dsc_v * s_ub.y;
-                    tot.z += s_pb.z + dsc_v * s_ub.z; tot.w += s_pb.w + dsc_v * s_ub.w;
-                    if (p.s_dsc1 && row0 + v < p.n_batch) {     // rows perm[g] < B of the shuffled branch (graphcnn.py:242)
-                        const int gq = gnm_perm_entry(p.s_inv_perm[row0 + v], p.n_batch);
-                        const float s2 = p.s_s2sum[gq];
-                        const float4 uq = *reinterpret_cast<const float4*>(p.s_U + (size_t)gq * p.ld_U + col0 + 4 * sub);
-                        tot.x += s2 * uq.x; tot.y += s2 * uq.y; tot.z += s2 * uq.z; tot.w += s2 * uq.w;
-                    }
-                    if (zrow.x * lsc.x + lsh.x <= 0.f) tot.x = 0.f;
-                    if (zrow.y * lsc.y + lsh.y <= 0.f) tot.y = 0.f;
-                    if (zrow.z * lsc.z + lsh.z <= 0.f) tot.z = 0.f;
-                    if (zrow.w * lsc.w + lsh.w <= 0.f) tot.w = 0.f;
-                    ss1.x += tot.x; ss1.y += tot.y; ss1.z += tot.z; ss1.w += tot.w;
-                    ss2.x += tot.x * (zrow.x - lmu.x); ss2.y += tot.y * (zrow.y - lmu.y);
-                    ss2.z += tot.z * (zrow.z - lmu.z); ss2.w += tot.w * (zrow.w - lmu.w);
-                }
-                float* dst = p.y + (size_t)(row0 + v) * p.ldy + cc;
-                if (vec_out && col0 + FS <= p.F) {          // wave-uniform: ONE 16-byte store per lane (see agg16)
-                    const f32x4 t4 = {tot.x, tot.y, tot.z, tot.w};
-                    __builtin_nontemporal_store(t4, reinterpret_cast<f32x4*>(dst));
-                } else {
-                    if (cc + 0 < p.F) dst[0] = tot.x;
-                    if (cc + 1 < p.F) dst[1] = tot.y;
-                    if (cc + 2 < p.F) dst[2] = tot.z;
-                    if (cc + 3 < p.F) dst[3] = tot.w;
-                }
-            }
-            rpv = nrpv;
-            g = gn;
-        }
-        GNM_GSTAMP(63)
-        if constexpr (STATS) {     // column sums: the 8 lane groups of a wave, then the waves, in a fixed order
-            __syncthreads();        // (everyone is done reading the tile: its first bytes are reused)
-            double* sred = reinterpret_cast<double*>(smem) + 64;      // [nwaves][2][32] (after the d-eps slots)
-            const float v1[4] = {ss1.x, ss1.y, ss1.z, ss1.w}, v2[4] = {ss2.x, ss2.y, ss2.z, ss2.w};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                double d1 = (double)v1[c], d2 = (double)v2[c];
-#pragma unroll
-                for (int off = 8; off < 64; off <<= 1) {
-                    d1 += __shfl_xor(d1, off, 64); d2 += __shfl_xor(d2, off, 64);
-                }
-                if (lane < 8) {
-                    sred[(wave * 2 + 0) * 32 + 4 * sub + c] = d1;
-                    sred[(wave * 2 + 1) * 32 + 4 * sub + c] = d2;
-                }
-            }
-            __syncthreads();
-            if (tid < 64) {
-                const int which = tid >> 5, col = tid & 31;
-                double sum = 0.0;
-                for (int w = 0; w < nwaves; ++w) sum += sred[(w * 2 + which) * 32 + col];
-                if (which) sum *= (double)p.s_rstd[col0 + col];      // sum G (Z - mean) -> sum G xhat
-                p.s_partial[((size_t)b * 2 + which) * p.F + col0 + col] = sum;
-            }
-        }
-    } else if constexpr (LPR == 2) {
-        // ---- 8-float rows (the input layer, F0 <= 8): 2 lanes per neighbour row, 32 neighbours per wave-instruction,
-        // GROUPS OF 16 ROWS per wave.  Lane bit 2 is the 16-B chunk; the other five bits number the 32 neighbour slots,
-        // so both lanes of a slot load the same column id themselves (no cross-lane traffic at all), and the 16 x 32
-        // partial sums are transposed and added over lane bits 5, 4, 3 (permlane swaps, DPP row_ror:8) and 1, 0
-        // (DPP quad_perm): lanes {bit5, bit4, bit3, bit1} = k end up with row k.
-        const int ngroups = p.y ? (n + 15) >> 4 : 0;
-        const int q2 = (lane >> 2) & 1;                                   // chunk of the 32-B row
-        const unsigned p5 = (unsigned)(((lane >> 3) << 2) | (lane & 3));   // neighbour slot 0..31
-        const unsigned sub2b = lds_base + (unsigned)q2 * 16u;
-        const unsigned zero2 = sub2b + (unsigned)n * 32u;
-        const bool b3 = (lane & 8) != 0, b1 = (lane & 2) != 0;
-        const int krow = ((lane >> 3) << 1) | ((lane >> 1) & 1);          // row of the group this lane ends up owning
-        int g = wave;
-        int rpv = 0, nrpv = 0;
-        if (g < ngroups) rpv = rp_s[min(16 * g + (lane & 31), n)];
-        unsigned nr0 = 0, nr1 = 0, nr2 = 0, nr3 = 0;                        // ids of the NEXT row (4 chunks of 32)
-        if (g < ngroups) {
-            const unsigned o = 2u * ((unsigned)__builtin_amdgcn_readlane(rpv, 0) + p5);
-            nr0 = load_id(cl, o); nr1 = load_id(cl, o + 64u); nr2 = load_id(cl, o + 128u); nr3 = load_id(cl, o + 192u);
-        }
-        for (; g < ngroups; g += nwaves) {
-            const bool more = g + nwaves < ngroups;
-            if (more) nrpv = rp_s[min(16 * (g + nwaves) + (lane & 31), n)];
-            const int v = 16 * g + krow;
-            const float4 self = tile[min(v, n) * 2 + q2];
-            float4 acc[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int beg = __builtin_amdgcn_readlane(rpv, r), end = __builtin_amdgcn_readlane(rpv, r + 1);
-                const unsigned r0 = nr0, r1 = nr1, r2 = nr2, r3 = nr3;
-                // the next row's ids (row r + 1 of this group, or row 0 of this wave's next group), unconditionally
-                {
-                    const int nb = (r < 15) ? end : __builtin_amdgcn_readlane(nrpv, 0);
-                    if (r < 15 || more) {                              // wave-uniform
-                        const unsigned o = 2u * ((unsigned)nb + p5);
-                        nr0 = load_id(cl, o); nr1 = load_id(cl, o + 64u); nr2 = load_id(cl, o + 128u); nr3 = load_id(cl, o + 192u);
-                    }
-                }
-                const int cnt = end - beg;
-                float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (cnt > 0) {
-                    const unsigned a0 = ((int)p5 < cnt) ? (r0 << 5) + sub2b : zero2;
-                    const unsigned a1 = ((int)p5 + 32 < cnt) ? (r1 << 5) + sub2b : zero2;
-                    if (cnt > 64) {
-                        const unsigned a2 = ((int)p5 + 64 < cnt) ? (r2 << 5) + sub2b : zero2;
-                        const unsigned a3 = ((int)p5 + 96 < cnt) ? (r3 << 5) + sub2b : zero2;
-                        const f32x4 t0 = lds_read16(a0), t1 = lds_read16(a1), t2 = lds_read16(a2), t3 = lds_read16(a3);
-                        acc4(a, (t0 + t1) + (t2 + t3));
-                        for (int e0 = beg + 128; e0 < end; e0 += 32) {       // degree > 128: fetched in place
-                            const unsigned rw = load_id(cl, 2u * ((unsigned)e0 + p5));
-                            const unsigned ax = ((int)p5 < end - e0) ? (rw << 5) + sub2b : zero2;
-                            acc4(a, lds_read16(ax));
-                        }
-                    } else {
-                        const f32x4 t0 = lds_read16(a0), t1 = lds_read16(a1);
-                        acc4(a, t0 + t1);
-                    }
-                }
-                acc[r] = a;
-            }
-            // transposing combine over lane bits 5, 4, 3, 1, then the plain sum over bit 0
-            float4 b8[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) b8[j] = swap_add32(acc[j], acc[j + 8]);
-            float4 c4[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) c4[j] = swap_add16(b8[j], b8[j + 4]);
-            float4 d2[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float4 mine = b3 ? c4[j + 2] : c4[j], theirs = b3 ? c4[j] : c4[j + 2];
-                d2[j].x = mine.x + ror8(theirs.x); d2[j].y = mine.y + ror8(theirs.y);
-                d2[j].z = mine.z + ror8(theirs.z); d2[j].w = mine.w + ror8(theirs.w);
-            }
-            const float4 mine = b1 ? d2[1] : d2[0], theirs = b1 ? d2[0] : d2[1];
-            float4 tot;
-            tot.x = mine.x + qxor2(theirs.x); tot.y = mine.y + qxor2(theirs.y);
-            tot.z = mine.z + qxor2(theirs.z); tot.w = mine.w + qxor2(theirs.w);
-            tot.x += qxor1(tot.x); tot.y += qxor1(tot.y); tot.z += qxor1(tot.z); tot.w += qxor1(tot.w);
-            int degk = 0;
-            if (!p.backward && p.average) degk = bnd_of(rpv, krow + 1) - bnd_of(rpv, krow);
-            if (v < n && (lane & 1) == 0) {
-                if (p.self_loop) acc4(tot, self);
-                if (!p.backward && p.average) {
-                    const float d = (float)(degk + p.self_loop);   // 0/0 -> NaN as in the reference
-                    tot.x /= d; tot.y /= d; tot.z /= d; tot.w /= d;
-                }
-                const int cc = col0 + 4 * q2;
-                if (!p.self_loop) {
-                    float4 sb = self;
-                    if (prescale) {   // the tile holds dp/deg; the (1+eps) term needs dp itself
-                        const float* src = p.x + (size_t)(row0 + v) * p.ldx + cc;
-                        sb.x = (cc + 0 < p.F) ? src[0] : 0.f;
-                        sb.y = (cc + 1 < p.F) ? src[1] : 0.f;
-                        sb.z = (cc + 2 < p.F) ? src[2] : 0.f;
-                        sb.w = (cc + 3 < p.F) ? src[3] : 0.f;
-                    }
-                    tot.x += selfB * sb.x; tot.y += selfB * sb.y; tot.z += selfB * sb.z; tot.w += selfB * sb.w;
-                }
-                float* dst = p.y + (size_t)(row0 + v) * p.ldy + cc;
-                if (vec_out && cc + 3 < p.F) {
-                    *reinterpret_cast<float4*>(dst) = tot;
-                } else {
-                    if (cc + 0 < p.F) dst[0] = tot.x;
-                    if (cc + 1 < p.F) dst[1] = tot.y;
-                    if (cc + 2 < p.F) dst[2] = tot.z;
-                    if (cc + 3 < p.F) dst[3] = tot.w;
-                }
-            }
-            rpv = nrpv;
-        }
-    } else {
-    // y == null: only the d-eps dot product of phase A is wanted.
-    // Nothing on the per-row path is a dependent global round trip: the row bounds come from LDS two rows ahead,
-    // the row's first 64 column ids are requested one row ahead (unconditional loads: the arena keeps readable
-    // slack behind the last block), and the ids of a chunk reach the lane groups either by DPP (8-lane groups: two
-    // bank-masked row_newbcast moves, no LDS round trip) or by a BATCH of ds_bpermute issued before the reads.
     const unsigned jl2 = 2u * (unsigned)jlane;
     int v = p.y ? wave : n;
     int nb = 0, ne = 0, nnb = 0, nne = 0;
@@ -756,30 +767,16 @@ __global__ void __launch_bounds__(1024) gnm_agg_kernel(const AggArgs p) {
             if (e0 != beg) raw = load_id(cl, 2u * (unsigned)e0 + jl2);             // degree > 64: fetched in place
             const unsigned valb = (jlane < cnt) ? raw * (FS * 4) : zero_row_b;
             const int steps = (cnt + SLOTS - 1) / SLOTS;   // wave-uniform, <= LPR
-            if constexpr (LPR == 8) {
-                // padding slots read the zero row: blocks of 4 run unguarded, 4 reads in flight each
-                {
-                    const f32x4 t0 = lds_read16(bcast8<0>(valb) + subb), t1 = lds_read16(bcast8<1>(valb) + subb),
-                                t2 = lds_read16(bcast8<2>(valb) + subb), t3 = lds_read16(bcast8<3>(valb) + subb);
-                    acc4(acc, (t0 + t1) + (t2 + t3));
-                }
-                if (steps > 4) {
-                    const f32x4 t0 = lds_read16(bcast8<4>(valb) + subb), t1 = lds_read16(bcast8<5>(valb) + subb),
-                                t2 = lds_read16(bcast8<6>(valb) + subb), t3 = lds_read16(bcast8<7>(valb) + subb);
-                    acc4(acc, (t0 + t1) + (t2 + t3));
-                }
-            } else {
-                const int gbase = lane & ~(LPR - 1);
-                int s = 0;
-                for (; s + 4 <= steps; s += 4) {
-                    const unsigned a0 = (unsigned)__shfl((int)valb, gbase + s, 64), a1 = (unsigned)__shfl((int)valb, gbase + s + 1, 64),
-                                   a2 = (unsigned)__shfl((int)valb, gbase + s + 2, 64), a3 = (unsigned)__shfl((int)valb, gbase + s + 3, 64);
-                    const f32x4 t0 = lds_read16(a0 + subb), t1 = lds_read16(a1 + subb), t2 = lds_read16(a2 + subb),
-                                t3 = lds_read16(a3 + subb);
-                    acc4(acc, (t0 + t1) + (t2 + t3));
-                }
-                for (; s < steps; ++s) acc4(acc, lds_read16((unsigned)__shfl((int)valb, gbase + s, 64) + subb));
+            const int gbase = lane & ~(LPR - 1);
+            int s = 0;
+            for (; s + 4 <= steps; s += 4) {
+                const unsigned a0 = (unsigned)__shfl((int)valb, gbase + s, 64), a1 = (unsigned)__shfl((int)valb, gbase + s + 1, 64),
+                               a2 = (unsigned)__shfl((int)valb, gbase + s + 2, 64), a3 = (unsigned)__shfl((int)valb, gbase + s + 3, 64);
+                const f32x4 t0 = lds_read16(a0 + subb), t1 = lds_read16(a1 + subb), t2 = lds_read16(a2 + subb),
+                            t3 = lds_read16(a3 + subb);
+                acc4(acc, (t0 + t1) + (t2 + t3));
             }
+            for (; s < steps; ++s) acc4(acc, lds_read16((unsigned)__shfl((int)valb, gbase + s, 64) + subb));
         }
         // combine the SLOTS partial sums of this destination row
 #pragma unroll
@@ -789,51 +786,141 @@ __global__ void __launch_bounds__(1024) gnm_agg_kernel(const AggArgs p) {
             acc.z += __shfl_xor(acc.z, off, 64);
             acc.w += __shfl_xor(acc.w, off, 64);
         }
-        if (lane < LPR) {
-            const float4 self = tile[v * LPR + sub];
-            if (p.self_loop) acc4(acc, self);
-            if (!p.backward && p.average) {
-                const float d = (float)(end - beg + p.self_loop);   // 0/0 -> NaN as in the reference
-                acc.x /= d; acc.y /= d; acc.z /= d; acc.w /= d;
+        if (lane < LPR)
+            agg_row_out(p, k, acc, tile[v * LPR + sub], v, sub, end - beg, selfB, vec_out);
+    }
+}
+
+// MODE (32-float slices, LPR == 8, only; round 4 -- what gnm_agg16_kernel does for the 64-wide shape):
+//   1 = forward PROLOGUE: x is the Z of the layer below's last Linear; the tile load applies that layer's outer
+//       BatchNorm + ReLU (p_scale / p_shift), writes the activation (p_hout, optional) and the graph readout (p_gf):
+//       gnm_bn_relu_readout's pass (45 us of 128-wide rows at configs[3]) rides on loads this kernel issues anyway;
+//   2 = backward STATS: the epilogue adds the readout / discriminator terms, applies the ReLU mask of the layer
+//       below and reduces that layer's BatchNorm-backward column sums (s_partial), and takes d eps from the rows it
+//       holds (h recomputed from sZ): gnm_bn_relu_bwd_stats's pass (75 us) and the hfwd read of phase A go away.
+template <int LPR, int MODE = 0>
+__global__ void __launch_bounds__(1024) gnm_agg_kernel(const AggArgs p) {
+    constexpr int FS = LPR * 4;        // floats per LDS row
+    constexpr bool PRO = MODE == 1, STATS = MODE == 2;
+    static_assert(MODE == 0 || LPR == 8, "fused forms: 32-float slices only");
+    GNM_STAMP(0)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float4* tile = reinterpret_cast<float4*>(smem);
+
+    const AggBlock k = agg_block(p, FS);
+    const int b = k.b, row0 = k.row0, n = k.n, col0 = k.col0;
+    const int tid = threadIdx.x;
+    const int nthreads = blockDim.x;
+    const AggTileLds lds = agg_tile_lds(LPR, n, MODE, p.ids_in_lds, 0);
+
+    // ---- phase A: HBM -> LDS, coalesced; optional 1/deg pre-scale and d-eps dot ----
+    double dot = 0.0;
+    int i0 = tid;
+    // d eps: dot(x, hfwd) on the way in, or -- STATS launches without hfwd -- from the rows the epilogue holds.  The
+    // launcher only starts the fused forms on full-width, 16-byte addressable slices, and a thread keeps the column
+    // chunk tid & (LPR - 1) for all its rows (the workgroup size is a multiple of LPR).
+    const bool dot_a = p.deps_partial && (!STATS || p.hfwd);
+    float4 psc = make_float4(1.f, 1.f, 1.f, 1.f), psh = zero4();
+    float4 csum = zero4();
+    if constexpr (PRO) {
+        psc = *reinterpret_cast<const float4*>(p.p_scale + col0 + 4 * (tid & (LPR - 1)));
+        psh = *reinterpret_cast<const float4*>(p.p_shift + col0 + 4 * (tid & (LPR - 1)));
+    }
+    auto prologue = [&](int i, float4 w) -> float4 {      // (PRO) the activation of tile element i, written and summed
+        w = bn_relu4(w, psc, psh);
+        if (p.p_hout) *reinterpret_cast<float4*>(p.p_hout + (size_t)(row0 + i / LPR) * p.p_ldh + col0 + 4 * (i & (LPR - 1))) = w;
+        acc4(csum, w);
+        return w;
+    };
+    // full-width, 16-byte addressable slices: 8 x 16 B per thread in flight (the loop below issues ONE load per trip,
+    // inside a lane-dependent branch, i.e. one memory round trip per 16 KB of the tile: 16-32 us of a 128 KB tile)
+    if (k.vec_in && col0 + FS <= p.F && (!dot_a || k.vec_h)) {       // wave-uniform
+        constexpr int UA = 8;
+        const int total = n * LPR;
+        for (; i0 + (UA - 1) * nthreads < total; i0 += UA * nthreads) {
+            float4 v[UA];
+#pragma unroll
+            for (int u = 0; u < UA; ++u) {
+                const int i = i0 + u * nthreads;
+                const int r = i / LPR, c = i - r * LPR;
+                v[u] = *reinterpret_cast<const float4*>(p.x + (size_t)(row0 + r) * p.ldx + col0 + 4 * c);
             }
-            const int cc = col0 + 4 * sub;
-            if (!p.self_loop) {
-                float4 sb = self;
-                if (prescale) {   // the tile holds dp/deg; the (1+eps) term needs dp itself
-                    const float* src = p.x + (size_t)(row0 + v) * p.ldx + cc;
-                    sb.x = (cc + 0 < p.F) ? src[0] : 0.f;
-                    sb.y = (cc + 1 < p.F) ? src[1] : 0.f;
-                    sb.z = (cc + 2 < p.F) ? src[2] : 0.f;
-                    sb.w = (cc + 3 < p.F) ? src[3] : 0.f;
+            if (dot_a) {
+#pragma unroll
+                for (int u = 0; u < UA; ++u) {
+                    const int i = i0 + u * nthreads;
+                    const int r = i / LPR, c = i - r * LPR;
+                    const float4 h = *reinterpret_cast<const float4*>(p.hfwd + (size_t)(row0 + r) * p.ldh + col0 + 4 * c);
+                    dot += dot4d(v[u], h);
                 }
-                acc.x += selfB * sb.x; acc.y += selfB * sb.y; acc.z += selfB * sb.z; acc.w += selfB * sb.w;
             }
-            float* dst = p.y + (size_t)(row0 + v) * p.ldy + cc;
-            if (vec_out && cc + 3 < p.F) {
-                *reinterpret_cast<float4*>(dst) = acc;
-            } else {
-                if (cc + 0 < p.F) dst[0] = acc.x;
-                if (cc + 1 < p.F) dst[1] = acc.y;
-                if (cc + 2 < p.F) dst[2] = acc.z;
-                if (cc + 3 < p.F) dst[3] = acc.w;
+#pragma unroll
+            for (int u = 0; u < UA; ++u) {
+                const int i = i0 + u * nthreads;
+                float4 w = v[u];
+                if (k.prescale) {
+                    const int r = i / LPR;
+                    div4(w, (float)(k.drp[r + 1] - k.drp[r] + p.self_loop));
+                }
+                if constexpr (PRO) w = prologue(i, w);
+                tile[i] = w;
             }
         }
     }
-
-    }   // LPR != 8
-
-    if (p.deps_partial) {   // block reduction of the d-eps dot product (fp64, fixed order)
-        __syncthreads();    // everyone is done reading the tile; reuse its first bytes
-        double* red = reinterpret_cast<double*>(smem);
-        const double w = wave_sum_d(dot);
-        if (lane == 0) red[wave] = w;
-        __syncthreads();
-        if (tid == 0) {
-            double s = 0.0;
-            for (int i = 0; i < nwaves; ++i) s += red[i];
-            p.deps_partial[blockIdx.x] = s;
+    for (int i = i0; i < n * LPR; i += nthreads) {
+        float4 v = phase_a_element<LPR>(p, k, i, dot_a, dot);
+        if constexpr (PRO) v = prologue(i, v);
+        tile[i] = v;
+    }
+    constexpr int ZR = LPR == 8 ? 2 : 1;       // zero rows behind the tile (LPR == 8: one of each parity, see phase B)
+    if (tid < ZR * LPR) tile[n * LPR + tid] = zero4();  // row n (, n + 1) = zeros (padding slots)
+    // row offsets staged behind the tile (wave-cooperative path only: the narrow path keeps its id block there)
+    int* rp_s = reinterpret_cast<int*>(smem + lds.rp);
+    const bool stage_rp = !(LPR <= 4 && p.ids_in_lds);
+    if (stage_rp)
+        for (int i = tid; i <= n; i += nthreads) rp_s[i] = k.rp[i];
+    // the group ticket (phase B): every wave's first group is its own number
+    if (LPR == 8 && tid == 0) *reinterpret_cast<int*>(smem + lds.ticket) = nthreads >> 6;
+    float4* const rsum = reinterpret_cast<float4*>(smem + lds.rsum);
+    if constexpr (PRO) {
+        if (p.p_gf) {      // the 8 lanes of a wave that share a column chunk (lane bits 3-5), then the waves (below)
+#pragma unroll
+            for (int off = 8; off < 64; off <<= 1) {
+                csum.x += __shfl_xor(csum.x, off, 64); csum.y += __shfl_xor(csum.y, off, 64);
+                csum.z += __shfl_xor(csum.z, off, 64); csum.w += __shfl_xor(csum.w, off, 64);
+            }
+            if ((tid & 63) < 8) rsum[(tid >> 6) * 8 + (tid & 7)] = csum;
         }
     }
+    GNM_STAMP(1)
+    GNM_STAMP(2)
+    __syncthreads();
+    GNM_STAMP(3)
+    if constexpr (PRO) {
+        if (p.p_gf && tid < 8) {      // graph readout of the activation just formed (graphcnn.py:229), in wave order
+            float4 t = zero4();
+            for (int w = 0; w < (nthreads >> 6); ++w) acc4(t, rsum[w * 8 + tid]);
+            if (p.p_gf_avg) scale4(t, 1.f / (float)n);
+            *reinterpret_cast<float4*>(p.p_gf + (size_t)b * p.p_ldgf + col0 + 4 * tid) = t;
+        }
+    }
+
+    // ---- phase B: gather neighbour rows from LDS --------------------------------
+    const float selfB = agg_self_b(p);
+    const bool vec_out = agg_vec_out(p);
+    if constexpr (LPR == 8) {
+        agg_rows_group8<MODE>(p, k, smem, lds, selfB, vec_out, dot);
+    } else if constexpr (LPR <= 4) {
+        if (p.ids_in_lds) agg_rows_staged<LPR>(p, k, smem, lds, selfB, vec_out);
+        else if constexpr (LPR == 2) agg_rows_group16(p, k, smem, lds, selfB, vec_out);
+        else agg_rows_wave<LPR>(p, k, smem, lds, selfB, vec_out);
+    } else {
+        agg_rows_wave<LPR>(p, k, smem, lds, selfB, vec_out);
+    }
+
+    if (p.deps_partial)
+        deps_block_reduce(dot, smem, p.deps_partial + blockIdx.x, tid, tid & 63, __builtin_amdgcn_readfirstlane(tid >> 6),
+                          nthreads >> 6);
 }
 
 
@@ -964,28 +1051,14 @@ __global__ void __launch_bounds__(1024) gnm_agg_kernel(const AggArgs p) {
     }
 
 
-__device__ __forceinline__ float4 sel4(bool c, const float4 a, const float4 b) {
-    return make_float4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
-}
-__device__ __forceinline__ float4 shfl_xor4(const float4 v, int m) {
-    return make_float4(__shfl_xor(v.x, m, 64), __shfl_xor(v.y, m, 64), __shfl_xor(v.z, m, 64),
-                       __shfl_xor(v.w, m, 64));
-}
-
 template <bool STATS>
 __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
     constexpr int LPR = 16;
     constexpr int FS = 64;
 #ifdef GNM_AGG16_TUNING       // tools/bench_agg.py ablations (GNM_AGG16_DEBUG); compiled out of the product kernel
     const int dbg = p.debug;
-    // in-kernel timeline (tools/agg_timeline.py): lane 0 of every wave drops s_memtime stamps at phase / group
-    // boundaries, where no LDS read is in flight anyway (s_memtime returns through lgkmcnt)
-#define GNM_STAMP(k)                                                                                          \
-    if (p.stamps && (threadIdx.x & 63) == 0)                                                                  \
-        p.stamps[((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 64 + (k)] = __builtin_amdgcn_s_memtime();
 #else
     constexpr int dbg = 0;
-#define GNM_STAMP(k)
 #endif
     GNM_STAMP(0)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1005,6 +1078,7 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
     const bool vec_in = ((p.ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.x) & 15) == 0);
     const bool vec_h = p.hfwd && ((p.ldh & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.hfwd) & 15) == 0);
     const bool prescale = p.backward && p.average;
+    const Agg16Lds lds = agg16_lds(n, p.p_scale != nullptr);
     const int nwaves = nthreads >> 6;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1035,7 +1109,7 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
     const int trows = tbase + (wave < textra ? 1 : 0);
     // tickets >= gtot: nothing left.  DYN: tickets number the groups of the graph; static: the groups of this wave
     const int gtot = !p.y ? 0 : (DYN ? n4 + tail_rows : nfull + (trem > 0 ? 1 : 0));
-    int* const ticket = reinterpret_cast<int*>(smem + (size_t)(n + 1) * (FS * 4));     // LDS word behind the tile
+    int* const ticket = reinterpret_cast<int*>(smem + lds.ticket);     // LDS word behind the tile
     // bounds of group t as a lane vector: lane i (0..4) = rowptr[first row + min(i, rows of the group)], read
     // straight from global memory (a 1.6 KB array, L2-resident); an exhausted ticket yields an empty group at row 0
     auto group_first = [&](int t) -> int {
@@ -1079,7 +1153,7 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
             idx[r] = load_pair(beg, 1);
         }
     };
-    const float selfB = p.self_loop ? 0.f : (p.eps ? 1.f + *p.eps : 1.f);
+    const float selfB = agg_self_b(p);
 
     // ---- phase A ---------------------------------------------------------------
     double dot = 0.0;
@@ -1093,16 +1167,15 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
     // forward prologue (non-STATS launches of gnm_agg_fwd_bnrelu only; nthreads is a multiple of 16, so a
     // thread keeps the column chunk tid & 15 for all its rows)
     const bool pro = !STATS && p.p_scale != nullptr;
-    float4 psc = make_float4(1.f, 1.f, 1.f, 1.f), psh = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 csum = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 psc = make_float4(1.f, 1.f, 1.f, 1.f), psh = zero4();
+    float4 csum = zero4();
     if (pro) {
         psc = *reinterpret_cast<const float4*>(p.p_scale + 4 * (tid & 15));
         psh = *reinterpret_cast<const float4*>(p.p_shift + 4 * (tid & 15));
         auto emit = [&](int i, float4 w) {
-            w.x = gnm_relu(w.x * psc.x + psh.x); w.y = gnm_relu(w.y * psc.y + psh.y);
-            w.z = gnm_relu(w.z * psc.z + psh.z); w.w = gnm_relu(w.w * psc.w + psh.w);
+            w = bn_relu4(w, psc, psh);
             if (p.p_hout) *reinterpret_cast<float4*>(p.p_hout + (size_t)(row0 + (i >> 4)) * p.p_ldh + 4 * (i & 15)) = w;
-            csum.x += w.x; csum.y += w.y; csum.z += w.z; csum.w += w.w;
+            acc4(csum, w);
             tile[i] = w;
         };
         if (base + (UNR - 1) * nthreads < total) {      // first batch, peeled: the id ring is requested behind its loads
@@ -1146,8 +1219,7 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
             base = total;
         }
         // readout partials: [nthreads] float4 behind the row offsets (the 64 threads of a column chunk)
-        float4* rsum = reinterpret_cast<float4*>(smem + (((size_t)(n + 1) * (FS * 4) + (size_t)(n + 2) * 4 + 15) & ~(size_t)15));
-        rsum[tid] = csum;
+        reinterpret_cast<float4*>(smem + lds.rsum)[tid] = csum;
     } else {
     // branch-free main part: UNR x 16 B (+ UNR x 16 B of hfwd) per thread in flight; the id ring is requested
     // behind the loads of the first batch
@@ -1170,9 +1242,7 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
         if (with_ring) issue_ring();
         if (dot_a) {
 #pragma unroll
-            for (int u = 0; u < UNR; ++u)
-                dot += (double)v[u].x * hh[u].x + (double)v[u].y * hh[u].y + (double)v[u].z * hh[u].z +
-                       (double)v[u].w * hh[u].w;
+            for (int u = 0; u < UNR; ++u) dot += dot4d(v[u], hh[u]);
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
@@ -1180,8 +1250,7 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
             float4 w = v[u];
             if (prescale) {
                 const int r = i >> 4;
-                const float d = (float)(drp[r + 1] - drp[r] + p.self_loop);
-                w.x /= d; w.y /= d; w.z /= d; w.w /= d;
+                div4(w, (float)(drp[r + 1] - drp[r] + p.self_loop));
             }
             tile[i] = w;
         }
@@ -1228,24 +1297,13 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
     }
     }
     // fused BatchNorm-backward statistics of the layer below (STATS): per-lane column chunk `sub` (requested in
-    // front of the drain below, like everything else the group loop finds already in registers)
-    float4 ss1 = make_float4(0.f, 0.f, 0.f, 0.f), ss2 = ss1, s_pb = ss1, s_ub = ss1;
+    // front of the drain below, like everything else the group loop finds already in registers).  The STATS launch is
+    // one 64-wide slice: column offset 0.
+    float4 ss1 = zero4(), ss2 = ss1, s_pb = ss1, s_ub = ss1;
     float4 lsc = ss1, lsh = ss1, lmu = ss1;
-    if constexpr (STATS) {
-        lsc = *reinterpret_cast<const float4*>(p.s_scale + 4 * sub);
-        lsh = *reinterpret_cast<const float4*>(p.s_shift + 4 * sub);
-        lmu = *reinterpret_cast<const float4*>(p.s_mean + 4 * sub);      // (rstd multiplies the column sums at the end)
-        if (p.s_dpool) {
-            s_pb = *reinterpret_cast<const float4*>(p.s_dpool + (size_t)b * p.ld_dpool + 4 * sub);
-            if (p.s_avg) {
-                const float w = 1.0f / (float)n;
-                s_pb.x *= w; s_pb.y *= w; s_pb.z *= w; s_pb.w *= w;
-            }
-        }
-        if (p.s_dsc1) s_ub = *reinterpret_cast<const float4*>(p.s_U + (size_t)b * p.ld_U + 4 * sub);
-    }
+    if constexpr (STATS) stats_load_consts(p, b, n, 0, sub, lsc, lsh, lmu, s_pb, s_ub);
 
-    if (tid < LPR) tile[n * LPR + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tid < LPR) tile[n * LPR + tid] = zero4();
     // Drain this wave's vector-memory queue HERE, once per graph, in front of the barrier (where all but the last
     // wave wait anyway): the group loop below then starts from a known-empty queue and its waits come out as the
     // exact counted vmcnt(3) per row.  Without it the compiler merges the several phase-A paths into "something may
@@ -1258,13 +1316,10 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
     GNM_STAMP(3)
     if (pro && p.p_gf && tid < LPR) {
         // graph readout of the activation just formed (graphcnn.py:229), partials combined in thread order
-        const float4* rsum = reinterpret_cast<const float4*>(smem + (((size_t)(n + 1) * (FS * 4) + (size_t)(n + 2) * 4 + 15) & ~(size_t)15));
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int k = tid; k < nthreads; k += LPR) acc4(t, rsum[k]);
-        if (p.p_gf_avg) {
-            const float inv = 1.f / (float)n;
-            t.x *= inv; t.y *= inv; t.z *= inv; t.w *= inv;
-        }
+        const float4* rsum = reinterpret_cast<const float4*>(smem + lds.rsum);
+        float4 t = zero4();
+        for (int j = tid; j < nthreads; j += LPR) acc4(t, rsum[j]);
+        if (p.p_gf_avg) scale4(t, 1.f / (float)n);
         *reinterpret_cast<float4*>(p.p_gf + (size_t)b * p.p_ldgf + 4 * tid) = t;
     }
 
@@ -1307,7 +1362,7 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
         const float4 self = tile[min(v, n) * LPR + sub];
         // "average" backward: the tile holds x / deg, the (1 + eps) self term needs x itself -- requested here,
         // ahead of the gather (a load issued in the epilogue is waited for at once, which drains the whole queue)
-        float4 xself = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 xself = zero4();
         if (prescale && !p.self_loop) {                                  // wave-uniform
             const int cc = col0 + 4 * sub;
             const float* src = p.x + (size_t)(row0 + min(v, n - 1)) * p.ldx + cc;
@@ -1404,57 +1459,27 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
         if (dbg & 2) {
             if (tot.x == 12345.678f) p.y[0] = tot.y + tot.z + tot.w + self.x;   // keep values live
         } else if (q < grows) {
+            // (these lines stay inline: through a shared epilogue helper the selfB product of the STATS instance no
+            //  longer fused with its add -- the final add of the combine was sunk in between -- and G changed in the
+            //  last bit)
             if (p.self_loop) acc4(tot, self);
-            if (need_deg) {
-                const float d = (float)(degv + p.self_loop);   // 0/0 -> NaN as in the reference
-                tot.x /= d; tot.y /= d; tot.z /= d; tot.w /= d;
-            }
+            if (need_deg) div4(tot, (float)(degv + p.self_loop));   // 0/0 -> NaN as in the reference
             const int cc = col0 + 4 * sub;
             if (!p.self_loop) {
                 const float4 sb = prescale ? xself : self;
-                tot.x += selfB * sb.x; tot.y += selfB * sb.y; tot.z += selfB * sb.z; tot.w += selfB * sb.w;
+                fma4(tot, selfB, sb);
                 if constexpr (STATS) {
-                    if (p.deps_partial && !p.hfwd) {
-                        // d eps += dpooled[v] . h[v], h = relu(bn_lo(Z[v])) recomputed as the forward formed it
-                        const float hx = gnm_relu(zrow.x * lsc.x + lsh.x), hy = gnm_relu(zrow.y * lsc.y + lsh.y);
-                        const float hz = gnm_relu(zrow.z * lsc.z + lsh.z), hw = gnm_relu(zrow.w * lsc.w + lsh.w);
-                        dot += (double)(sb.x * hx + sb.y * hy) + (double)(sb.z * hz + sb.w * hw);
-                    }
+                    if (p.deps_partial && !p.hfwd) dot += stats_deps_term<true>(sb, zrow, lsc, lsh);
                 }
             }
-            if constexpr (STATS) {
-                // total gradient at this layer output = aggregation backward + readout + discriminator terms
-                tot.x += s_pb.x + dsc_v * s_ub.x; tot.y += s_pb.y + dsc_v * s_ub.y;
-                tot.z += s_pb.z + dsc_v * s_ub.z; tot.w += s_pb.w + dsc_v * s_ub.w;
-                if (p.s_dsc1 && row0 + v < p.n_batch) {     // rows perm[g] < B of the shuffled branch (graphcnn.py:242)
-                    const int gq = gnm_perm_entry(p.s_inv_perm[row0 + v], p.n_batch);
-                    const float s2 = p.s_s2sum[gq];
-                    const float4 uq = *reinterpret_cast<const float4*>(p.s_U + (size_t)gq * p.ld_U + 4 * sub);
-                    tot.x += s2 * uq.x; tot.y += s2 * uq.y; tot.z += s2 * uq.z; tot.w += s2 * uq.w;
-                }
-                if (zrow.x * lsc.x + lsh.x <= 0.f) tot.x = 0.f;
-                if (zrow.y * lsc.y + lsh.y <= 0.f) tot.y = 0.f;
-                if (zrow.z * lsc.z + lsh.z <= 0.f) tot.z = 0.f;
-                if (zrow.w * lsc.w + lsh.w <= 0.f) tot.w = 0.f;
-                ss1.x += tot.x; ss1.y += tot.y; ss1.z += tot.z; ss1.w += tot.w;
-                ss2.x += tot.x * (zrow.x - lmu.x); ss2.y += tot.y * (zrow.y - lmu.y);
-                ss2.z += tot.z * (zrow.z - lmu.z); ss2.w += tot.w * (zrow.w - lmu.w);
-            }
+            if constexpr (STATS) stats_row(p, tot, zrow, dsc_v, row0 + v, 0, sub, lsc, lsh, lmu, s_pb, s_ub, ss1, ss2);
             GNM_STAMP(7 + 5 * min(kk, 10))
-            float* dst = p.y + (size_t)(row0 + v) * p.ldy + cc;
-            if (vec_full) {     // wave-uniform: ONE 16-byte store per lane (a per-lane condition here was
-                                // if-converted into a 12-byte + a 4-byte masked store on every launch)
-                // (a plain float4 store here is merged by the optimiser with the scalar stores of the other
-                //  branch into a 12-byte + a 4-byte store; the streaming flavour cannot be: ONE
-                //  global_store_dwordx4 nt.  The row is written once and next read by another kernel.)
-                const f32x4 t4 = {tot.x, tot.y, tot.z, tot.w};
-                __builtin_nontemporal_store(t4, reinterpret_cast<f32x4*>(dst));
-            } else {
-                if (cc + 0 < p.F) dst[0] = tot.x;
-                if (cc + 1 < p.F) dst[1] = tot.y;
-                if (cc + 2 < p.F) dst[2] = tot.z;
-                if (cc + 3 < p.F) dst[3] = tot.w;
-            }
+            // vec_full is wave-uniform, so this is ONE 16-byte store per lane (a per-lane condition here was
+            // if-converted into a 12-byte + a 4-byte masked store on every launch), and it is the streaming flavour
+            // (a plain float4 store here is merged by the optimiser with the scalar stores of the other branch into
+            // a 12-byte + a 4-byte store; the streaming flavour cannot be: ONE global_store_dwordx4 nt.  The row is
+            // written once and next read by another kernel.)
+            store4<true>(p.y + (size_t)(row0 + v) * p.ldy + cc, tot, vec_full, cc, p.F);
         }
         GNM_STAMP(8 + 5 * min(kk, 10))
         // advance the pipeline
@@ -1465,42 +1490,11 @@ __global__ void __launch_bounds__(1024) gnm_agg16_kernel(const AggArgs p) {
     GNM_STAMP(63)
 
     if constexpr (STATS) {     // column sums: the 4 quarters of a wave, then the waves, in a fixed order
-        __syncthreads();
-        double* sred = reinterpret_cast<double*>(smem) + 64;      // [nwaves][2][64] (after the d-eps slots)
-        const float v1[4] = {ss1.x, ss1.y, ss1.z, ss1.w}, v2[4] = {ss2.x, ss2.y, ss2.z, ss2.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            double d1 = (double)v1[c], d2 = (double)v2[c];
-            d1 += __shfl_xor(d1, 16, 64); d2 += __shfl_xor(d2, 16, 64);
-            d1 += __shfl_xor(d1, 32, 64); d2 += __shfl_xor(d2, 32, 64);
-            if (lane < 16) {
-                sred[(wave * 2 + 0) * 64 + 4 * sub + c] = d1;
-                sred[(wave * 2 + 1) * 64 + 4 * sub + c] = d2;
-            }
-        }
-        __syncthreads();
-        if (tid < 128) {
-            const int which = tid >> 6, col = tid & 63;
-            double sum = 0.0;
-            for (int w = 0; w < nwaves; ++w) sum += sred[(w * 2 + which) * 64 + col];
-            if (which) sum *= (double)p.s_rstd[col];      // sum G (Z - mean) -> sum G xhat
-            p.s_partial[((size_t)blockIdx.x * 2 + which) * 64 + col] = sum;
-        }
+        stats_col_reduce<16>(p, smem, ss1, ss2, tid, lane, wave, nwaves, sub, 0, (size_t)blockIdx.x, 64);
         __syncthreads();
     }
 
-    if (p.deps_partial) {
-        __syncthreads();
-        double* red = reinterpret_cast<double*>(smem);
-        const double w = wave_sum_d(dot);
-        if (lane == 0) red[wave] = w;
-        __syncthreads();
-        if (tid == 0) {
-            double s = 0.0;
-            for (int i = 0; i < nwaves; ++i) s += red[i];
-            p.deps_partial[blockIdx.x] = s;
-        }
-    }
+    if (p.deps_partial) deps_block_reduce(dot, smem, p.deps_partial + blockIdx.x, tid, lane, wave, nwaves);
 }
 
 #ifdef GNM_AGG16_TUNING
@@ -1508,28 +1502,30 @@ static unsigned long long* g_agg16_stamps = nullptr;
 extern "C" void gnm_debug_set_stamps(void* p) { g_agg16_stamps = reinterpret_cast<unsigned long long*>(p); }
 #endif
 
-static int launch_agg16(const AggArgs& a0, int B, int n_max, hipStream_t stream) {
-    AggArgs a = a0;
+// What both launchers do with the finished layout size: the timeline buffer of tuning builds, and the workgroup size
+// -- one workgroup per CU when the tile is large (16 waves to keep the LDS pipe busy); smaller tiles share a CU, so
+// fewer waves per workgroup.
+static int agg_stamps_and_threads(AggArgs& a, size_t lds) {
 #ifdef GNM_AGG16_TUNING
     a.stamps = g_agg16_stamps;
 #else
     a.stamps = nullptr;
 #endif
-    size_t lds = (size_t)(n_max + 1) * 256 + (size_t)(n_max + 2) * 4 + 16;
-    if (a.p_scale) lds += 16 + (size_t)1024 * 16;     // forward prologue: readout partials of up to 1024 threads
+    if (lds <= 20 * 1024) return 256;
+    if (lds <= 48 * 1024) return 512;
+    return 1024;
+}
+
+static int launch_agg16(const AggArgs& a0, int B, int n_max, hipStream_t stream) {
+    AggArgs a = a0;
+    size_t lds = agg16_lds(n_max, a.p_scale != nullptr).total;
     GNM_ALLOW_FULL_LDS(&gnm_agg16_kernel<false>);
     GNM_ALLOW_FULL_LDS(&gnm_agg16_kernel<true>);
-    int threads = 1024;
-    if (lds <= 20 * 1024) threads = 256;
-    else if (lds <= 48 * 1024) threads = 512;
+    int threads = agg_stamps_and_threads(a, lds);
     static const int env_threads = gnm_env_int("GNM_AGG16_THREADS", 0);   // tuning knob for tools/bench_agg.py
     if (env_threads >= 64 && env_threads <= 1024 && (env_threads & 63) == 0) threads = env_threads;
     if (reinterpret_cast<uintptr_t>(a.col) & 3) return GNM_ERR_UNSUPPORTED;     // column ids are fetched as aligned pairs
-    // the reductions at the end of the kernel reuse the tile's LDS: [64] d-eps slots + [waves][2][64] doubles of column
-    // statistics.  A batch of very small graphs (n_max < 17) has a tile smaller than that (found by
-    // tests/test_gpu_aggm.py, graphs of 3 nodes: the sums lost every contribution written past the allocation)
-    const size_t red = (size_t)(64 + (threads / 64) * 128) * 8;
-    if (lds < red) lds = red;
+    lds = std::max(lds, agg_reduce_lds(threads, 64));
     if (a.sZ)
         hipLaunchKernelGGL(gnm_agg16_kernel<true>, dim3(B * a.nslices), dim3(threads), lds, stream, a);
     else
@@ -1541,40 +1537,21 @@ static int launch_agg16(const AggArgs& a0, int B, int n_max, hipStream_t stream)
 template <int LPR>
 static int launch_agg(const AggArgs& a0, int B, int n_max, hipStream_t stream) {
     AggArgs a = a0;
-#ifdef GNM_AGG16_TUNING
-    a.stamps = g_agg16_stamps;
-#else
-    a.stamps = nullptr;
-#endif
-    size_t lds = (size_t)(n_max + (LPR == 8 ? 2 : 1)) * LPR * 16;      // + the zero row(s)
     const int max_nnz = a.ids_in_lds;             // on entry: largest nnz of the batch (0 = unknown)
-    a.ids_in_lds = 0;
     const int mode = LPR == 8 ? (a.sZ ? 2 : (a.p_scale ? 1 : 0)) : 0;      // fused forms (gnm_agg_kernel's MODE)
     if (LPR != 8 && (a.sZ || a.p_scale)) return GNM_ERR_UNSUPPORTED;
-    const size_t extra = mode == 1 ? 16 * 8 * 16 : 0;                      // prologue: [16 waves][8] float4 of readout shares
-    if (LPR == 4 && max_nnz > 0 && lds + (size_t)max_nnz * 2 + 96 <= (size_t)kLdsBudget - 1024) {
-        a.ids_in_lds = 1;
-        lds += (size_t)max_nnz * 2 + 96;          // + alignment shift and 16-B rounding of the staged id block
-    } else {
-        lds += (size_t)(n_max + 2) * 4 + 16;       // staged row offsets (gnm_agg_slice_width budgets for them)
-        if (LPR == 8) {                             // + the waves' id scratch (16 x 1 KB), where it fits next to the tile
-            const size_t with_scr = ((lds + 15) & ~(size_t)15) + 16 * 1024;
-            if (with_scr + extra <= (size_t)kLdsBudget - 1024 && lds > 48 * 1024) {   // (1024-thread launches only: 16 waves)
-                lds = with_scr;
-                a.ids_in_lds = 2;
-            }
-        }
-    }
-    if (extra) {
-        lds = ((lds + 15) & ~(size_t)15) + extra;
-        if (lds > (size_t)kLdsBudget - 1024) return GNM_ERR_UNSUPPORTED;
-    }
+    const size_t room = (size_t)kLdsBudget - 1024;
+    // ids_in_lds: 1 = the graph's ids next to a 16-float tile, where they fit; 2 = the waves' id scratch of the 8-lane
+    // kernel, where it fits next to a tile of more than 48 KB (1024-thread launches only: 16 waves)
+    a.ids_in_lds = 0;
+    if (LPR == 4 && max_nnz > 0 && agg_tile_lds(LPR, n_max, mode, 1, max_nnz).total <= room) a.ids_in_lds = 1;
+    else if (LPR == 8 && agg_tile_lds(LPR, n_max, mode, 2, 0).total <= room &&
+             agg_tile_lds(LPR, n_max, 0, 0, 0).total > 48 * 1024)
+        a.ids_in_lds = 2;
+    size_t lds = agg_tile_lds(LPR, n_max, mode, a.ids_in_lds, max_nnz).total;
+    if (lds > room && mode == 1) return GNM_ERR_UNSUPPORTED;       // no room for the prologue's readout shares
     GNM_ALLOW_FULL_LDS(&gnm_agg_kernel<LPR>);
-    // one workgroup per CU when the tile is large (16 waves to keep the LDS pipe busy);
-    // smaller tiles share a CU, so use fewer waves per workgroup.
-    int threads = 1024;
-    if (lds <= 20 * 1024) threads = 256;
-    else if (lds <= 48 * 1024) threads = 512;
+    int threads = agg_stamps_and_threads(a, lds);
     if (a.ids_in_lds) {                            // one thread per (row, chunk): enough threads for a whole graph
         threads = ((n_max * LPR + 63) / 64) * 64;
         if (threads > 1024) threads = 1024;
@@ -1582,9 +1559,7 @@ static int launch_agg(const AggArgs& a0, int B, int n_max, hipStream_t stream) {
     }
     if constexpr (LPR == 8) {
         if (mode) {
-            // the STATS reductions at the end reuse the tile's first bytes: [64] d-eps slots + [waves][2][32] doubles
-            const size_t red = (size_t)(64 + (threads / 64) * 64) * 8;
-            if (lds < red) lds = red;
+            lds = std::max(lds, agg_reduce_lds(threads, 32));
             if (mode == 1) {
                 GNM_ALLOW_FULL_LDS((&gnm_agg_kernel<8, 1>));
                 hipLaunchKernelGGL((gnm_agg_kernel<8, 1>), dim3(B * a.nslices), dim3(threads), lds, stream, a);
@@ -1620,7 +1595,7 @@ __global__ void __launch_bounds__(256) gnm_agg_global_kernel(const AggArgs p, in
     const int32_t* drp = p.deg_rowptr + p.b_deg_off[b];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool prescale = p.backward && p.average;
-    const float selfB = p.self_loop ? 0.f : (p.eps ? 1.f + *p.eps : 1.f);
+    const float selfB = agg_self_b(p);
     double dot = 0.0;
     for (int v = ch * kAggGRows + wave; v < min(n, (ch + 1) * kAggGRows); v += 4) {
         const int e0 = rp[v], e1 = rp[v + 1];
@@ -1673,8 +1648,17 @@ extern "C" int gnm_agg_slice_width(int F, int n_max) {
     int fs = 8;
     static const int env_cap = gnm_env_int("GNM_AGG_SLICE_MAX", 128);   // tuning knob: widest slice tried
     while (fs < F && fs < 128 && fs < env_cap) fs <<= 1;
-    while (fs >= 8 && (size_t)(n_max + 2) * fs * 4 + (size_t)(n_max + 2) * 4 + 16 > (size_t)kLdsBudget - 1024) fs >>= 1;
+    while (fs >= 8 && agg_slice_budget(fs, n_max) > (size_t)kLdsBudget - 1024) fs >>= 1;
     return fs >= 8 ? fs : 0;
+}
+
+// The shapes the two fused entries take: 64 = one 64-wide slice (gnm_agg16_kernel), 32 = 32-float slices of a width
+// that is a multiple of 32 (gnm_agg_kernel<8, MODE>: hidden_dim 128 on graphs too large for a wider slice,
+// configs[3]), 0 = neither.
+static int agg_fused_shape(int F, int n_max) {
+    const int fs = gnm_agg_slice_width(F, n_max);
+    if (F == 64 && fs == 64) return 64;
+    return fs == 32 && (F & 31) == 0 ? 32 : 0;
 }
 
 extern "C" int gnm_agg(const int32_t* rowptr, const uint16_t* col, const int64_t* b_rp_off,
@@ -1719,11 +1703,8 @@ extern "C" int gnm_agg_bwd_stats(const int32_t* rowptr, const uint16_t* col, con
                                  int ld_U, const int32_t* inv_perm, const float* s2sum, double* s_partial,
                                  void* stream) {
     if (B <= 0) return GNM_OK;
-    // two shapes: one 64-wide slice (gnm_agg16_kernel), or 32-float slices of a width that is a multiple of 32
-    // (gnm_agg_kernel<8, 2>: hidden_dim 128 on graphs too large for a wider slice, configs[3])
-    const int fs = gnm_agg_slice_width(F, n_max);
-    const bool wide64 = F == 64 && fs == 64, sliced32 = fs == 32 && (F & 31) == 0;
-    if ((!wide64 && !sliced32) || !y || !sZ || !s_partial) return GNM_ERR_UNSUPPORTED;
+    const int shape = agg_fused_shape(F, n_max);
+    if (!shape || !y || !sZ || !s_partial) return GNM_ERR_UNSUPPORTED;
     if ((ldsz & 3) || (ldy & 3) || (ldx & 3) || (dpool && (ld_dpool & 3)) || (dsc1 && (ld_U & 3))) return GNM_ERR_UNSUPPORTED;
     if (reinterpret_cast<uintptr_t>(x) & 15) return GNM_ERR_UNSUPPORTED;
     const uintptr_t al = reinterpret_cast<uintptr_t>(sZ) | reinterpret_cast<uintptr_t>(s_scale) |
@@ -1739,7 +1720,7 @@ extern "C" int gnm_agg_bwd_stats(const int32_t* rowptr, const uint16_t* col, con
     a.s_dpool = dpool; a.s_dsc1 = dsc1; a.s_U = U; a.s_inv_perm = inv_perm; a.s_s2sum = s2sum;
     a.s_partial = s_partial; a.ldsz = ldsz; a.ld_dpool = ld_dpool; a.ld_U = ld_U; a.s_avg = graph_avg;
     a.n_batch = B;
-    if (sliced32) {
+    if (shape == 32) {
         a.nslices = F / 32;
         a.ids_in_lds = nnz_max > 0 ? nnz_max : 0;
         return launch_agg<8>(a, B, n_max, reinterpret_cast<hipStream_t>(stream));
@@ -1757,12 +1738,9 @@ extern "C" int gnm_agg_fwd_bnrelu(const int32_t* rowptr, const uint16_t* col, co
                                   int ldh, float* gf, int ldgf, int graph_avg, float* y, int ldy, int F,
                                   const float* eps, int average, int self_loop, void* stream) {
     if (B <= 0) return GNM_OK;
-    // two shapes, as gnm_agg_bwd_stats: one 64-wide slice, or 32-float slices of a multiple of 32 (gnm_agg_kernel<8, 1>)
-    const int fs = gnm_agg_slice_width(F, n_max);
-    const bool wide64 = F == 64 && fs == 64, sliced32 = fs == 32 && (F & 31) == 0;
-    if ((!wide64 && !sliced32) || !y || !z || !scale || !shift) return GNM_ERR_UNSUPPORTED;
-    if (wide64 && (size_t)(n_max + 1) * 256 + (size_t)(n_max + 2) * 4 + 32 + (size_t)1024 * 16 > (size_t)kLdsBudget - 1024)
-        return GNM_ERR_UNSUPPORTED;
+    const int shape = agg_fused_shape(F, n_max);
+    if (!shape || !y || !z || !scale || !shift) return GNM_ERR_UNSUPPORTED;
+    if (shape == 64 && agg16_lds(n_max, true).total > (size_t)kLdsBudget - 1024) return GNM_ERR_UNSUPPORTED;
     if ((ldz & 3) || (hout && (ldh & 3)) || (ldy & 3) || (gf && (ldgf & 3))) return GNM_ERR_UNSUPPORTED;
     const uintptr_t al = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(scale) |
                          reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(hout) |
@@ -1772,7 +1750,7 @@ extern "C" int gnm_agg_fwd_bnrelu(const int32_t* rowptr, const uint16_t* col, co
                          self_loop, 0, nullptr, 0, nullptr);
     a.p_scale = scale; a.p_shift = shift; a.p_hout = hout; a.p_gf = gf; a.p_ldh = ldh; a.p_ldgf = ldgf;
     a.p_gf_avg = graph_avg;
-    if (sliced32) {
+    if (shape == 32) {
         a.nslices = F / 32;
         a.ids_in_lds = nnz_max > 0 ? nnz_max : 0;
         return launch_agg<8>(a, B, n_max, reinterpret_cast<hipStream_t>(stream));      // (declines when LDS has no room for the shares)

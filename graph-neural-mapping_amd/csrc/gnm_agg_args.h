@@ -21,17 +21,19 @@ struct AggArgs {
     int F;                     // valid feature width
     int nslices;
     int average, self_loop, backward;
-    // optional fusion (agg16, backward, one slice): y is the gradient arriving at relu(bn(sZ)) of the layer
-    // below -- add the readout / discriminator terms, apply that ReLU mask, write G and reduce the
+    // optional fusion (backward; one 64-wide slice or 32-float slices): y is the gradient arriving at relu(bn(sZ))
+    // of the layer below -- add the readout / discriminator terms, apply that ReLU mask, write G and reduce the
     // BatchNorm-backward sums (replaces gnm_bn_relu_bwd_stats for that BatchNorm)
     const float* sZ; const float* s_scale; const float* s_shift; const float* s_mean; const float* s_rstd;
     const float* s_dpool; const float* s_dsc1; const float* s_U; const int32_t* s_inv_perm; const float* s_s2sum;
-    double* s_partial;         // [B][2][64]
+    double* s_partial;         // [B][2][F]
     int ldsz, ld_dpool, ld_U, s_avg, n_batch;
-    int ids_in_lds;            // narrow slices: the graph's column ids are staged in LDS (max_nnz given)
+    // on entry to the launcher: the batch's largest nnz (0 = unknown).  In the kernel: 1 = the graph's column ids are
+    // staged in LDS (16-float slices), 2 = the waves have an id scratch in LDS (32-float slices), 0 = neither
+    int ids_in_lds;
     int debug;                 // tuning only (GNM_AGG16_DEBUG): 1 no id loads, 2 no epilogue/store, 4 no combine
     unsigned long long* stamps;   // tuning only: per-wave s_memtime stamps, [workgroup][16 waves][64] (gnm_debug_set_stamps)
-    // forward prologue (agg16 only): the input is Z of the previous layer's last Linear; the tile load applies that
+    // forward prologue (one 64-wide slice or 32-float slices): the input is Z of the previous layer's last Linear; the tile load applies that
     // layer's outer BatchNorm + ReLU, writes the activation h (p_hout) and its graph readout (p_gf) on the way
     const float* p_scale; const float* p_shift;
     float* p_hout; float* p_gf;

@@ -52,26 +52,34 @@ def dense_adj(batch_graphs):
 
 
 AGG_CASES = [
-    # (sizes, density, F, symmetric)
-    ([40, 40, 40], 0.3, 64, True),        # headline shape class: LPR 16
-    ([37, 5, 64, 1, 23], 0.4, 64, True),  # ragged sizes incl. a single-node graph
-    ([50, 50], 0.0, 64, True),            # no edges at all
-    ([200, 200], 1.0, 64, True),          # complete graphs: degree 199 -> third id chunk fetched in place
-    ([30, 31], 0.3, 7, True),             # layer-0 width: LPR 2, scalar loads
-    ([30, 31], 0.3, 5, True),
-    ([64, 64], 0.2, 32, True),            # LPR 8
-    ([48, 48], 0.3, 16, True),            # LPR 4
-    ([300, 300], 0.05, 128, True),        # LPR 32
-    ([1000, 1000], 0.02, 128, True),      # config-4 class: tile does not fit -> 4 feature slices of 32
-    ([400, 400], 0.3, 400, True),         # one-hot width of the reference's default input: 7 slices of 64
-    ([45, 45, 45], 0.3, 64, False),       # asymmetric
-    ([45, 45, 45], 0.3, 20, False),       # asymmetric, partial slice, unaligned rows
+    # (sizes, density, F, symmetric, nnz_max): nnz_max None = the batch's own, 0 = the launcher's "unknown"
+    ([40, 40, 40], 0.3, 64, True, None),        # headline shape class: LPR 16
+    ([37, 5, 64, 1, 23], 0.4, 64, True, None),  # ragged sizes incl. a single-node graph
+    ([50, 50], 0.0, 64, True, None),            # no edges at all
+    ([200, 200], 1.0, 64, True, None),          # complete graphs: degree 199 -> the second 128-id window
+    ([30, 31], 0.3, 7, True, None),             # layer-0 width: LPR 2, scalar loads
+    ([30, 31], 0.3, 5, True, None),
+    ([64, 64], 0.2, 32, True, None),            # LPR 8
+    ([48, 48], 0.3, 16, True, None),            # LPR 4, ids staged in LDS
+    ([300, 300], 0.05, 128, True, None),        # LPR 32
+    ([1000, 1000], 0.02, 128, True, None),      # config-4 class: tile does not fit -> 4 feature slices of 32
+    ([400, 400], 0.3, 400, True, None),         # one-hot width of the reference's default input: 7 slices of 64
+    ([45, 45, 45], 0.3, 64, False, None),       # asymmetric
+    ([45, 45, 45], 0.3, 20, False, None),       # asymmetric, partial slice, unaligned rows
+    # branches of agg.hip that none of the cases above reaches (appended, so the ids above stay what they were)
+    ([150, 140], 1.0, 7, True, None),           # LPR 2, degree 149: four id reads per row, then ids fetched in place
+    ([300, 280], 1.0, 64, True, None),          # LPR 16, degree 299 > 256: ids fetched in place behind both windows
+    ([100, 90], 1.0, 32, True, None),           # LPR 8 without id scratch, rows of more than 64 neighbours
+    ([700, 650], 0.15, 32, True, None),         # LPR 8 with the waves' id scratch (tile > 48 KB), mean degree ~100
+    ([100, 90], 1.0, 128, True, None),          # LPR 32, second 64-id chunk of a row
+    ([48, 48], 0.3, 16, True, 0),               # LPR 4, nnz_max unknown: the wave-cooperative path, no staged ids
 ]
+AGG_IDS = ["sizes%d-%s-%s-%s%s" % (i, c[1], c[2], c[3], "" if c[4] is None else "-nnz%d" % c[4]) for i, c in enumerate(AGG_CASES)]
 
 
-@pytest.mark.parametrize("sizes,density,F,symmetric", AGG_CASES)
+@pytest.mark.parametrize("sizes,density,F,symmetric,nnz_max", AGG_CASES, ids=AGG_IDS)
 @pytest.mark.parametrize("average,learn_eps", [(0, 1), (1, 1), (0, 0), (1, 0)])
-def test_agg_forward_backward(sizes, density, F, symmetric, average, learn_eps):
+def test_agg_forward_backward(sizes, density, F, symmetric, nnz_max, average, learn_eps):
     from gnm import core
     from gnm.arena import GraphArena
     rng = np.random.default_rng(hash((tuple(sizes), F)) % 2**31)
@@ -79,6 +87,8 @@ def test_agg_forward_backward(sizes, density, F, symmetric, average, learn_eps):
     ar = GraphArena(DEV)
     batch = ar.batch(graphs)
     batch.dense = False              # this test is about the CSR gather kernels (the matrix-core path: test_gpu_aggm.py)
+    if nnz_max is not None:
+        batch.nnz_max = nnz_max
     assert batch.symmetric == (symmetric or density == 0.0)
     A = dense_adj(graphs)
     N = batch.N
