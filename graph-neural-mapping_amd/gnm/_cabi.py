@@ -94,6 +94,9 @@ SIGNATURES = {
     "gnm_disconnect_scratch_floats": (_ll, [_ll, _ll, _i, _i, _i]),
     "gnm_disconnect": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _ll, _ll, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i,
                             _i, _f, _p, _p, _p, _p, _ll, _p]),
+    "gnm_coalition_pack": (_i, [_p, _ll, _p, _p, _p, _i, _i, _p, _i, _i, _ll, _i, _p, _p, _p]),
+    "gnm_shapley_exact": (_i, [_p, _ll, _i, _ll, _i, _p, _p, _p, _p, _p]),
+    "gnm_shapley_permutation": (_i, [_p, _ll, _i, _ll, _i, _i, _p, _p, _p, _p]),
     "gnm_integrated_gradients_scratch_floats": (_ll, [_ll, _i, _i]),
     "gnm_intgrad_z0": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _i, _p]),
     "gnm_integrated_gradients": (_i, [_p, _p, _p, _p, _p, _i, _i, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p,

@@ -1129,6 +1129,177 @@ def disconnect_hip(spec, batch, X, P, classes, in_a, in_b, vgraph, out=None):
     return out
 
 
+def _runs_under(f, budget):
+    """_runs_within for a cost that is a difference of a non-decreasing prefix array: items 0 .. len(f) - 2 as runs
+    (i0, i1), each the longest of at least one item with f[i1] - f[i0] <= budget -- one bisection per run"""
+    i0, count = 0, len(f) - 1
+    while i0 < count:
+        i1 = max(i0 + 1, int(np.searchsorted(f, f[i0] + budget, side="right")) - 1)
+        yield i0, i1
+        i0 = i1
+
+
+def shapley_hip(spec, batch, X, P, classes, labels, vgraph, ids, K, ranks=None, out=None):
+    """The eval-mode class scores of the coalitions of a node labelling (csrc/shapley.hip gnm_coalition_pack in front
+    of the unchanged gnm_lesion): out[ci, q] = c_logit[classes[ci]] of graph vgraph[q] of the batch without its labelled
+    nodes whose group is absent from coalition ids[q].  labels: a host int array [B, >= n_max], row b the labels of
+    graph b in -1 .. K - 1 (-1: background, never removed; entries past a graph's n are ignored); vgraph: V host ints
+    in [0, B); ids: V host ints.  ranks None, the bitset form (K <= 32): bit p of an id says group p is present.
+    ranks a host int [M, K] array of inverse permutations, the prefix form (K <= 416): id = m (K + 1) + j keeps the
+    groups p with ranks[m, p] < j.
+
+    lesion_hip's chunk loop (whole virtual graphs under LESION_SCRATCH_BYTES, the chunk's scratch bounded through the
+    batch's largest graph) with three differences: a virtual graph costs 4 bytes of description (its id; the labels go
+    up once per batch) instead of a removed row; the kept counts gnm_lesion checks are computed here from the group
+    sizes, so nothing is read back; and a coalition that keeps no node at all is left out of the launch and scored
+    sum_l linears_prediction[l].bias[c], added in fp32 in layer order -- the head's score of a zero pooled vector.
+    The shapes lesion_decline takes.  Returns a float32 [len(classes), V] tensor (`out` when given)."""
+    d = _launch_dims(spec, batch, X, P)
+    dev, L, m, N, B, H, Cn, F0, X = d.dev, d.L, d.m, d.N, d.B, d.H, d.Cn, d.F0, d.X
+    nm, K = int(batch.n_max), int(K)
+    vgraph = np.ascontiguousarray(vgraph, dtype=np.int32)
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    labels = np.asarray(labels)
+    Vt = int(vgraph.shape[0])
+    if labels.ndim != 2 or labels.shape[0] != B or labels.shape[1] < nm or labels.dtype.kind not in "iu":
+        raise GnmError("labels must be an int [%d, >= %d] array, got %s %s" % (B, nm, labels.dtype, list(labels.shape)))
+    if ids.shape != (Vt,):
+        raise GnmError("ids must be [%d], got %s" % (Vt, list(ids.shape)))
+    if Vt and (vgraph.min() < 0 or vgraph.max() >= B):
+        raise GnmError("vgraph entries must be graphs of the batch, 0 .. %d" % (B - 1))
+    offs = np.asarray(batch.node_off_host, dtype=np.int64)
+    ns = np.diff(offs)
+    lab = labels[:, :nm].astype(np.int64)
+    inside = np.arange(nm)[None, :] < ns[:, None]
+    if (lab[inside] < -1).any() or (lab[inside] >= K).any():
+        raise GnmError("labels must lie in -1 .. %d" % (K - 1))
+    if ranks is None:
+        if not 1 <= K <= 32:
+            raise GnmError("the bitset form takes 1 .. 32 groups, got %d" % K)
+        top = 1 << K
+    else:
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64)
+        if not 1 <= K <= 416 or ranks.ndim != 2 or ranks.shape[1] != K or ranks.shape[0] < 1:
+            raise GnmError("the prefix form takes ranks [M >= 1, K] with 1 <= K <= 416, got K = %d and %s"
+                           % (K, list(ranks.shape)))
+        if not (np.sort(ranks, axis=1) == np.arange(K)[None, :]).all():
+            raise GnmError("every row of ranks must be a permutation of 0 .. %d" % (K - 1))
+        top = ranks.shape[0] * (K + 1)
+    if Vt and (ids.min() < 0 or ids.max() >= top):
+        raise GnmError("coalition ids must lie in 0 .. %d" % (top - 1))
+    # the kept counts from the group sizes: background + the sizes of the groups present
+    sizes = np.stack([np.bincount(lab[b][inside[b] & (lab[b] >= 0)], minlength=K) for b in range(B)]).astype(np.int64)
+    kept_all = ((lab < 0) & inside).sum(1)[vgraph]
+    if ranks is None:
+        for p in np.nonzero(sizes.any(0))[0]:
+            kept_all = kept_all + ((ids >> int(p)) & 1) * sizes[vgraph, p]
+    else:
+        order = np.argsort(ranks, axis=1)                                 # order[m, j]: the player at position j
+        csum = np.concatenate([np.zeros((B, ranks.shape[0], 1), dtype=np.int64),
+                               np.cumsum(sizes[:, order], axis=2)], axis=2)       # [B, M, K + 1]
+        kept_all = kept_all + csum[vgraph, ids // (K + 1), ids % (K + 1)]
+    out = _out_array(out, (len(classes), Vt), dev)
+    cls = (C.c_int * len(classes))(*[int(c) for c in classes])
+    run = np.nonzero(kept_all > 0)[0]
+    Vr = int(run.shape[0])
+    vg_r, ids_r = vgraph[run], ids[run].astype(np.int32)
+    kept_r = np.ascontiguousarray(kept_all[run], dtype=np.int32)
+    vn = ns[vg_r].astype(np.int32)                          # node count of each virtual graph that runs
+    cum = np.concatenate([[0], np.cumsum(vn, dtype=np.int64)])      # activation rows before it
+    # gnm_lesion_scratch_floats with the chunk's largest graph bounded by the batch's: a prefix array
+    cost = 2 * cum * H + L * np.arange(Vr + 1, dtype=np.int64) * ((nm + 31) // 32) * H
+    with torch.no_grad(), _stream_scope(dev):
+        res = out if Vr == Vt else torch.empty((len(classes), Vr), dtype=torch.float32, device=dev)
+        up = batch.arena._upload
+        if Vr:
+            table = _eval_table(spec, P, dev)
+            XW = _first_linear_product(X, P, m, N, F0, H)
+            lab16 = np.full((B, nm), -1, dtype=np.int16)
+            lab16[inside] = lab[inside]
+            lab_d = up(torch.as_tensor(lab16))              # once per batch
+            ranks_d = up(torch.as_tensor(ranks.astype(np.int16))) if ranks is not None else None
+        for q0, q1 in _runs_under(cost, LESION_SCRATCH_BYTES // 4):
+            V, nc = q1 - q0, np.ascontiguousarray(vn[q0:q1])
+            n_max, rows = int(nc.max()), int(cum[q1] - cum[q0])
+            mstride = int(lib.gnm_lesion_mask_words(n_max))
+            vg = up(torch.as_tensor(vg_r[q0:q1]))
+            idd = up(torch.as_tensor(ids_r[q0:q1]))
+            vrow_off = up(torch.as_tensor(cum[q0:q1] - cum[q0]))
+            masks = torch.empty((V, mstride), dtype=torch.int32, device=dev)
+            kept = torch.empty(V, dtype=torch.int32, device=dev)
+            check(lib.gnm_coalition_pack(lab_d.data_ptr(), lab_d.stride(0), vg.data_ptr(), idd.data_ptr(),
+                                         ranks_d.data_ptr() if ranks is not None else None,
+                                         ranks.shape[0] if ranks is not None else 0, K, batch.node_off.data_ptr(), B,
+                                         n_max, V, mstride, masks.data_ptr(), kept.data_ptr(), _stream()),
+                  "gnm_coalition_pack")
+            kept_host = np.ascontiguousarray(kept_r[q0:q1])
+            scratch = torch.empty(int(lib.gnm_lesion_scratch_floats(rows, V, n_max, H, L)), dtype=torch.float32,
+                                  device=dev)
+            dst = res[:, q0:q1]
+            with _timed("shapley_hip", B=B, N=V, H=H, L=L):
+                check(lib.gnm_lesion(batch.arena.bits.buf.data_ptr(), batch.bits_off.data_ptr(),
+                                     batch.node_off.data_ptr(), vg.data_ptr(), vrow_off.data_ptr(), masks.data_ptr(),
+                                     mstride, kept.data_ptr(), kept_host.ctypes.data, nc.ctypes.data, B, n_max, V,
+                                     rows, XW.data_ptr(), XW.stride(0), H, L, m, Cn, cls, len(classes),
+                                     int(spec.n_avg), int(not spec.learn_eps), int(spec.g_avg), BN_EPS,
+                                     table.data_ptr(), d.eps, scratch.data_ptr(), dst.data_ptr(), res.stride(0),
+                                     _stream()), "gnm_lesion")
+        if Vr != Vt:
+            # the coalitions that keep no node: the head's score of a zero pooled vector at every layer
+            ci = torch.as_tensor([int(c) for c in classes], device=dev)
+            empty = torch.zeros(len(classes), dtype=torch.float32, device=dev)
+            for l in range(L):
+                empty = empty + P["linears_prediction.%d.bias" % l].detach()[ci]
+            out[:] = empty[:, None]
+            if Vr:
+                out[:, up(torch.as_tensor(run))] = res
+    return out
+
+
+def shapley_exact_hip(values, K, interactions=False):
+    """Exact Shapley values from all 2^K coalition scores (csrc/shapley.hip gnm_shapley_exact): values float32
+    [n_classes, G, 2^K] on the device -> phi fp64 [n_classes, G, K] and, with interactions, inter fp64
+    [n_classes, G, K, K] (else None).  The weights come from gnm/shapley.py (math.comb, fp64)."""
+    from .shapley import interaction_weights, shapley_weights
+    dev = launch_device(values)
+    if values.dim() != 3 or values.dtype != torch.float32 or values.shape[2] != 1 << K:
+        raise GnmError("values must be float32 [n_classes, G, 2^%d], got %s %s" % (K, values.dtype, list(values.shape)))
+    values = values.contiguous()
+    Cc, G = int(values.shape[0]), int(values.shape[1])
+    w = np.ascontiguousarray(shapley_weights(K))
+    u = np.ascontiguousarray(interaction_weights(K)) if interactions and K > 1 else None
+    with torch.no_grad(), _stream_scope(dev):
+        phi = torch.empty((Cc, G, K), dtype=torch.float64, device=dev)
+        inter = torch.empty((Cc, G, K, K), dtype=torch.float64, device=dev) if interactions else None
+        check(lib.gnm_shapley_exact(values.data_ptr(), G << K, Cc, G, K, w.ctypes.data,
+                                    u.ctypes.data if u is not None else None, phi.data_ptr(),
+                                    inter.data_ptr() if interactions else None, _stream()), "gnm_shapley_exact")
+    return phi, inter
+
+
+def shapley_permutation_hip(values, ranks):
+    """Sampled Shapley values from the prefix scores of M permutations (csrc/shapley.hip gnm_shapley_permutation):
+    values float32 [n_classes, G, M, K + 1] on the device, ranks a host int [M, K] array of inverse permutations ->
+    (mean, stderr) fp64 [n_classes, G, K]."""
+    dev = launch_device(values)
+    ranks = np.ascontiguousarray(ranks, dtype=np.int64)
+    if ranks.ndim != 2 or ranks.shape[0] < 1 or not (np.sort(ranks, axis=1) == np.arange(ranks.shape[1])[None, :]).all():
+        raise GnmError("every row of ranks must be a permutation of 0 .. K - 1")
+    M, K = ranks.shape
+    if values.dim() != 4 or values.dtype != torch.float32 or tuple(values.shape[2:]) != (M, K + 1):
+        raise GnmError("values must be float32 [n_classes, G, %d, %d], got %s %s"
+                       % (M, K + 1, values.dtype, list(values.shape)))
+    values = values.contiguous()
+    Cc, G = int(values.shape[0]), int(values.shape[1])
+    with torch.no_grad(), _stream_scope(dev):
+        ranks_d = torch.as_tensor(ranks.astype(np.int16)).to(dev)
+        mean = torch.empty((Cc, G, K), dtype=torch.float64, device=dev)
+        err = torch.empty((Cc, G, K), dtype=torch.float64, device=dev)
+        check(lib.gnm_shapley_permutation(values.data_ptr(), G * M * (K + 1), Cc, G, M, K, ranks_d.data_ptr(),
+                                          mean.data_ptr(), err.data_ptr(), _stream()), "gnm_shapley_permutation")
+    return mean, err
+
+
 # integrated_gradients_hip's device arrays per chunk of source graphs stay under this many bytes: the virtual batch's
 # forward keeps every Linear's z and every layer's aggregation, (m L + L - 1) K N H floats, next to 4 K N H of scratch.
 # K = 32, 8 graphs of 400 nodes, H = 64, m = 2, L = 5: 0.26 GB of z, 0.47 GB in all.

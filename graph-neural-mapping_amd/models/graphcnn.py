@@ -36,7 +36,8 @@ from gnm.arena import GraphArena  # noqa: E402
 from gnm.core import (DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, disconnect_decline,  # noqa: E402
                       disconnect_hip, edge_saliency_hip, eval_forward_fused, eval_fused_ok, integrated_gradients_hip,
                       launch_device, lesion_decline, lesion_hip, occlusion_decline, occlusion_hip, saliency_decline,
-                      saliency_hip, saliency_maps_hip)
+                      saliency_hip, saliency_maps_hip, shapley_exact_hip, shapley_hip, shapley_permutation_hip)
+from gnm import shapley as shapley_host  # noqa: E402
 from gnm.intgrad import quadrature  # noqa: E402
 from gnm.lesion import curve_area, default_fractions, masks_from_ranking, pair_sets  # noqa: E402
 
@@ -854,6 +855,130 @@ class GIN_InfoMaxReg(nn.Module):
             return mat
         delta = square(delta)
         return (delta, base, square(scores)) if return_scores else delta
+
+    def shapley(self, graphs, cls, labels, method="exact", permutations=None, seed=0, interactions=False, batch_size=8,
+                return_scores=False):
+        """Shapley values of the ROI networks of a labelling: the average loss of the class score when a network is
+        lesioned, over all orders of removal -- the figures that, unlike one lesion() per network, add up and do not
+        depend on which other networks are still present.
+
+        labels: as disconnection_matrix() -- ONE int [n] vector for all graphs (which then all have n nodes) or a list
+        of per-graph [n_g] vectors; entry r is the group of node r in 0 .. K - 1, or -1 for BACKGROUND, a node of no
+        group that is never removed; K is the largest id over all graphs + 1.  The players are the K groups.  For a
+        coalition S of them, v_c(g, S) = score_c(G_g without every labelled node whose group is not in S): lesion()'s
+        contract on that set (rows and edges removed, the readout over the kept nodes, the reduced graph's own degrees,
+        0/0 NaN), so v(N) is the kernel's score of the whole graph.  A coalition that keeps no node at all (no
+        background, every group of S empty in the graph) is not run: its value is sum_l linears_prediction[l].bias[c],
+        added in fp32 in layer order, the head's score of a zero pooled vector -- the reference's own value under graph
+        "sum" pooling, a stated deviation under "average" (0/0 there).
+
+        method="exact" (K <= 16): all 2^K coalitions per graph.  Returns phi, an fp64 device tensor [len(graphs), K] for
+        an int `cls` and [len(cls), len(graphs), K] for a sequence,
+            phi[c, g, i] = sum over S in N \\ {i} of (v(S + i) - v(S)) / (K C(K - 1, |S|)),
+        with sum_i phi_i = v(N) - v(empty).  interactions=True returns (phi, inter), inter [.., K, K] fp64 the Shapley
+        interaction index sum over S in N \\ {i, j} of (v(S+ij) - v(S+i) - v(S+j) + v(S)) / ((K - 1) C(K - 2, |S|)):
+        symmetric, zero diagonal -- the principled counterpart of disconnection_matrix().  return_scores=True appends
+        values, float32 [.., len(graphs), 2^K]: entry id is the coalition whose bit p says group p is present, bitwise
+        lesion()'s score of that set.
+
+        method="permutation": sampled Shapley values for larger K, up to one player per node (labels = arange(n) gives
+        per-ROI values).  permutations: an int M -- M rows np.random.default_rng(seed).permutation(K), the numpy global
+        RNG untouched -- or an explicit int [M, K] array of permutations; the same rows serve every graph.  Each row
+        contributes v(its prefix through i) - v(its prefix before i) to player i.  Returns (phi, stderr): the fp64 mean
+        over the M rows and std(ddof=1) / sqrt(M) (NaN at M = 1).  v(empty) and v(N) are scored once per graph.
+        interactions=True raises; return_scores=True appends values [.., len(graphs), M, K + 1], entry (m, j) the score
+        with the first j players of row m present.
+
+        No copy of a graph and no mask is built on the host: a coalition is 4 bytes (csrc/shapley.hip
+        gnm_coalition_pack writes lesion()'s keep masks on the device), the forward is lesion()'s kernels unchanged, and
+        the scores are combined on the device in fp64 from the fp32 scores -- differences first, fixed summation
+        orders, no atomics (gnm_shapley_exact / gnm_shapley_permutation; gnm/shapley.py restates them in numpy).  The
+        results are bitwise the same run to run, for any batch_size, any chunking (gnm/core.py LESION_SCRATCH_BYTES)
+        and any set of classes.  A group with no node in a graph has phi exactly 0.0 there (and a zero inter row)
+        wherever the graph's scores are finite.
+
+        NaN: every coalition enters every player's sum, so ONE NaN coalition score makes that graph's phi and inter
+        NaN for that class (and no other graph's).  Under neighbour "average" with learned eps this is common: any
+        coalition that leaves a kept node without a kept neighbour scores NaN, as the reference's 0/0 row does on the
+        explicit copy -- a few background nodes joined to every node avoid it.  A graph with a non-finite feature gets
+        all-NaN results and its batch-mates run as a clean batch, as in lesion().
+
+        The shapes lesion() takes; any other batch raises ValueError naming the condition, as do K > 16 under "exact"
+        (use method="permutation"), labels of the wrong length or dtype or below -1, a labelling that names no group, a
+        shared labelling over graphs of different node counts, and rows that are not permutations of 0 .. K - 1.  No
+        parameter .grad, BatchNorm buffer or numpy RNG state is touched, and the train / eval mode is restored."""
+        single, classes = self._interpret_args("shapley", graphs, cls, batch_size)
+        if method not in ("exact", "permutation"):
+            raise ValueError("shapley: method must be 'exact' or 'permutation', not %r" % (method,))
+        as_np = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)     # noqa: E731
+        ns = [len(g.g) for g in graphs]
+        shared = torch.is_tensor(labels) or isinstance(labels, np.ndarray) or (
+            isinstance(labels, (list, tuple)) and len(labels) > 0 and np.ndim(labels[0]) == 0)
+        if shared and any(k != ns[0] for k in ns):
+            raise ValueError("shapley: a shared [n] labelling needs graphs of one node count")
+        if not shared and (not isinstance(labels, (list, tuple)) or len(labels) != len(graphs)):
+            raise ValueError("shapley: labels must be one [n] vector or a list of one [n_g] vector per graph")
+        try:
+            per = [shapley_host.check_labels(as_np(labels), ns[0])] * len(graphs) if shared else \
+                [shapley_host.check_labels(as_np(v), n) for v, n in zip(labels, ns)]
+        except ValueError as e:
+            raise ValueError("shapley: %s" % e) from None
+        K = max([int(v.max()) + 1 for v in per if v.size] + [0])
+        if K < 1:
+            raise ValueError("shapley: the labels name no group")
+        if method == "exact":
+            if permutations is not None:
+                raise ValueError("shapley: permutations belong to method='permutation'")
+            if K > shapley_host.EXACT_MAX_PLAYERS:
+                raise ValueError("shapley: method='exact' scores 2^K coalitions per graph and takes at most %d groups, "
+                                 "got %d; use method='permutation'" % (shapley_host.EXACT_MAX_PLAYERS, K))
+            ranks, ids, where = None, np.arange(1 << K, dtype=np.int64), None
+        else:
+            if interactions:
+                raise ValueError("shapley: interactions need method='exact'")
+            if K > shapley_host.PREFIX_MAX_PLAYERS:
+                raise ValueError("shapley: at most %d groups, got %d" % (shapley_host.PREFIX_MAX_PLAYERS, K))
+            if permutations is None:
+                raise ValueError("shapley: method='permutation' needs permutations, an int M or an int [M, K] array")
+            try:
+                if isinstance(permutations, (int, np.integer)):
+                    perms = shapley_host.draw_permutations(int(permutations), K, seed)
+                else:
+                    perms = shapley_host.check_permutations(as_np(permutations), K)
+            except ValueError as e:
+                raise ValueError("shapley: %s" % e) from None
+            ranks, M = shapley_host.ranks_of(perms), perms.shape[0]
+            # the coalitions that run, per graph: every prefix of row 0, and the proper prefixes of the other rows
+            # (j = 0 and j = K are v(empty) and v(N) whatever the row); where[m, j]: entry (m, j)'s place among them
+            mj = [(0, j) for j in range(K + 1)] + [(m, j) for m in range(1, M) for j in range(1, K)]
+            ids = np.array([m * (K + 1) + j for m, j in mj], dtype=np.int64)
+            where = np.zeros((M, K + 1), dtype=np.int64)
+            where[:, K] = K
+            for k, (m, j) in enumerate(mj):
+                where[m, j] = k
+        cnt = int(ids.shape[0])
+
+        def run_batch(chunk, batch, P, i0):
+            def run(b, Xb, which):
+                """the coalitions of graphs `which` of the chunk, which are the graphs of batch b, in order"""
+                rows = np.full((len(which), int(b.n_max)), -1, dtype=np.int64)
+                for k, j in enumerate(which):
+                    rows[k, :ns[i0 + j]] = per[i0 + j]
+                vgraph = np.repeat(np.arange(len(which), dtype=np.int32), cnt)
+                return shapley_hip(self._spec, b, Xb, P, classes, rows, vgraph, np.tile(ids, len(which)), K, ranks)
+            return self._sets_batch("shapley", lesion_decline, chunk, batch, P, classes, [cnt] * batch.B, run)
+        _, _, values = self._set_scores(graphs, False, classes, batch_size, [cnt] * len(graphs), True, run_batch)
+        if method == "exact":
+            phi, inter = shapley_exact_hip(values, K, interactions)
+            res = (phi, inter) if interactions else (phi,)
+        else:
+            values = values[:, :, torch.as_tensor(where, device=values.device)]          # [C, G, M, K + 1]
+            res = shapley_permutation_hip(values, ranks)
+        if return_scores:
+            res = res + (values,)
+        if single:
+            res = tuple(r[0] for r in res)
+        return res[0] if len(res) == 1 else res
 
     def integrated_gradients(self, graphs, cls, steps=32, baseline=None, method="midpoint", batch_size=8,
                              return_scores=False):

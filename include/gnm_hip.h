@@ -467,6 +467,47 @@ int gnm_disconnect(const uint32_t* adj_bits, const int64_t* b_bits_off, const in
                    int average, int self_loop, int graph_avg, float bn_eps, const long long* table, const float* eps,
                    float* scratch, float* out, long long ldo, void* stream);
 
+/* ---- Shapley values of ROI networks (csrc/shapley.hip) -------------------------------------------------------------
+ * The players are the K groups of a node labelling; the value of a coalition is gnm_lesion's score of the graph without
+ * the labelled nodes of every group outside it.  gnm_coalition_pack describes the virtual graphs to gnm_lesion from 4
+ * bytes each; gnm_shapley_exact / gnm_shapley_permutation combine the fp32 scores in fp64.
+ *
+ * gnm_coalition_pack: masks [V][mstride] and kept [V] exactly as gnm_lesion_pack writes them (same layout, stride, zero
+ * words and zero bits at columns >= n) -- bitwise its output for the equivalent "removed" array.  labels: int16 [B, ldl]
+ * on the DEVICE, row b the labels of source graph b of the batch (entries at columns >= n are ignored; a negative label
+ * is background, never removed; a label >= K is treated as background too); vgraph [V], ids [V] int32 on the DEVICE.
+ * ranks == NULL, the BITSET form, 1 <= K <= 32: node r of virtual graph q is kept iff its label l is background or bit
+ * l of ids[q] is set.  ranks != NULL, the PREFIX form, 1 <= K <= 416, M >= 1: ranks int16 [M][K] on the DEVICE, row m
+ * the position of each player in permutation m; ids[q] = m (K + 1) + j, 0 <= j <= K, names the first j players of
+ * permutation m: node r is kept iff its label l is background or ranks[m][l] < j.  16 lanes per virtual graph, one
+ * word per lane, plain vector stores.  Return codes as gnm_lesion_pack (BAD_ARG: ldl < n_max, mstride too small or > 16,
+ * a NULL array; UNSUPPORTED: n_max outside 1..416), and BAD_ARG for K outside the form's range or M < 1.
+ *
+ * gnm_shapley_exact: scores [n_classes][lds] fp32 on the DEVICE, entry g 2^K + id the score of the coalition of graph g
+ * whose bit p says group p is present (lds >= G 2^K) -> phi [n_classes][G][K] fp64,
+ * phi_i = sum over S in N \ {i} of w_host[|S|] (v(S + i) - v(S)), and, with inter != NULL, inter [n_classes][G][K][K]
+ * fp64, inter_ij = sum over S in N \ {i, j} of u_host[|S|] ((v(S + ij) - v(S + i)) - (v(S + j) - v(S))), both triangles
+ * and a zero diagonal.  w_host [K], u_host [K - 1]: fp64 weight tables on the HOST (passed to the kernels by value;
+ * u_host may be NULL when inter is, or at K = 1).  One 256-thread workgroup per (class, graph, player) and per
+ * (class, graph, pair i < j); thread t takes the compact subset indices t, t + 256, ... in ascending order, the fp64
+ * difference of the fp32 scores times the weight (no contraction), then a fixed-order LDS tree.  No atomics: bitwise
+ * reproducible; a NaN score makes that (class, graph)'s results NaN and no other's.  UNSUPPORTED: K outside 1..16;
+ * BAD_ARG: lds too small, a NULL array.
+ *
+ * gnm_shapley_permutation: scores [n_classes][lds] fp32 on the DEVICE, entry (g M + m) (K + 1) + j the score of graph g
+ * with the first j players of permutation m present (lds >= G M (K + 1)); ranks as above (the HOST validates that each
+ * row is a permutation of 0 .. K - 1) -> mean, err [n_classes][G][K] fp64: the mean over m of
+ * v[m][ranks[m][i] + 1] - v[m][ranks[m][i]] and its standard error sqrt(sum (d - mean)^2 / (M - 1)) / sqrt(M) (two
+ * passes; NaN at M = 1).  One thread per (class, graph, player), sequential over m.  UNSUPPORTED: K outside 1..416;
+ * BAD_ARG: M < 1, lds too small, a NULL array. */
+int gnm_coalition_pack(const int16_t* labels, long long ldl, const int32_t* vgraph, const int32_t* ids,
+                       const int16_t* ranks, int M, int K, const int32_t* node_off, int B, int n_max, long long V,
+                       int mstride, uint32_t* masks, int32_t* kept, void* stream);
+int gnm_shapley_exact(const float* scores, long long lds, int n_classes, long long G, int K, const double* w_host,
+                      const double* u_host, double* phi, double* inter, void* stream);
+int gnm_shapley_permutation(const float* scores, long long lds, int n_classes, long long G, int M, int K,
+                            const int16_t* ranks, double* mean, double* err, void* stream);
+
 /* ---- Eval-mode integrated gradients (csrc/intgrad.hip over csrc/saliency.hip's layer launches) ----------------------
  * attr[node_off[g] + r, :] = (X - x')[g, r, :] * sum_k w_k d score[cls] / d X (x' + alpha_k (X_g - x'))[r, :] for every
  * graph g of a batch, x' the baseline (zeros, or one [n_base, F0] block every graph shares), (alpha_k, w_k), k < K, a
