@@ -12,8 +12,16 @@
 //   gnm_timeseries_normalize  R_ij = (C_ij / s_i) / s_j, s = sqrt(diag), for both triangles from the upper one, then
 //                             np.clip(R, -1, 1) with NaN kept (np.corrcoef); n = 1 is numpy's c / c.
 //
-// Every sum has a fixed order inside one workgroup (no atomics, no split of T across workgroups), so a subject's
-// results do not depend on the other subjects of the launch.
+// Sliding windows of the same packed series, described and never copied: window w is the `window` rows from row
+// w_beg[w] on (any order, overlapping freely).
+//
+//   gnm_dynfc_means           the means kernel on (w_beg[w], window) instead of (t_off[s], t_off[s + 1] - t_off[s]).
+//   gnm_dynfc_corr            finished R of every window in one launch: the Gram's grid and staging, the standard
+//                             deviations from column sums taken while staging, the normalisation from an LDS tile of the
+//                             accumulators; rectangular (np.corrcoef) or tapered (np.cov's aweights form).
+//
+// Every sum has a fixed order inside one workgroup (no atomics, no split of T across workgroups), so a subject's or
+// window's results do not depend on the other subjects or windows of the launch.
 #include "gnm_common.h"
 
 namespace {
@@ -89,16 +97,17 @@ __device__ double np_pairwise_sum(const T* a, long long n, long long stride) {
 }
 
 // ---------------------------------------------------------------------------------------------------- means
-// one thread per (subject, ROI): the reduce numpy runs is 0 + pairwise_sum(column), then true_divide by T
+// one thread per (subject, ROI): the reduce numpy runs is 0 + pairwise_sum(column), then true_divide by T.
+// window = 0: subject s owns rows t_off[s] .. t_off[s + 1]; window > 0: `window` rows from t_off[s] on (t_off = w_beg).
 template <typename T>
 __global__ void __launch_bounds__(kMeanThreads) gnm_ts_means_kernel(const T* __restrict__ x,
-                                                                    const int64_t* __restrict__ t_off, int n, int bps,
-                                                                    double* __restrict__ mean) {
+                                                                    const int64_t* __restrict__ t_off, int window,
+                                                                    int n, int bps, double* __restrict__ mean) {
 #pragma clang fp contract(off)
     const int s = blockIdx.x / bps;
     const int c = (blockIdx.x % bps) * kMeanThreads + threadIdx.x;
     if (c >= n) return;
-    const long long t0 = t_off[s], T_s = t_off[s + 1] - t0;
+    const long long t0 = t_off[s], T_s = window > 0 ? (long long)window : t_off[s + 1] - t0;
     const double sum = 0.0 + np_pairwise_sum(x + t0 * n + c, T_s, (long long)n);
     mean[(size_t)s * n + c] = sum / (double)T_s;
 }
@@ -287,6 +296,213 @@ __global__ void __launch_bounds__(kGramThreads) gnm_ts_normalize_kernel(const do
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- windows
+// Workgroup (window w, block pair bi <= bj): the Gram kernel's grid, staging and MFMA loop over the window's rows, and
+// the normalise kernel's epilogue from an LDS tile of the accumulators instead of a C read back from memory, so each R
+// entry is written once and nothing else is.
+//   * rectangular (kTaper false, np.corrcoef): centre = mean[w] (the means kernel's), C = (Xc^T Xc) * (1 / (window - 1)).
+//   * tapered (kTaper true, np.cov's aweights): centre avg = sum_t w_t x_t / sum_t w_t, C = (Xc^T (w * Xc)) * (1 / fact),
+//     fact = sum w - sum w^2 / sum w; the B side is staged as w_t * xc.  Thread (column, wave) sums the rows
+//     t = wave, wave + 4, .. in ascending t and the four waves' parts are added as (p0 + p1) + (p2 + p3).
+//   * s_i = sqrt(C_ii) of the workgroup's two column blocks: column sums of xc * (w * xc) taken while staging, in the
+//     same per-wave order and the same combine, times the same reciprocal.  The order depends on the column and the
+//     window alone, so every workgroup that serves a column gets the same bits, on the A side or the B side.
+//   * rows past the window and columns past n are staged as exact zeros by select; a value outside the window is
+//     never part of a product.
+// The tile s_c and the small sums alias the staging buffers: the K loop ends on a barrier, after which no wave reads
+// them.
+template <typename T, bool kTaper>
+__global__ void __launch_bounds__(kGramThreads) gnm_dynfc_corr_kernel(const T* __restrict__ x,
+                                                                      const int64_t* __restrict__ w_beg, int window,
+                                                                      const double* __restrict__ mean,
+                                                                      const double* __restrict__ taper, int n, int nb,
+                                                                      int P, double* __restrict__ fc) {
+#pragma clang fp contract(off)
+    constexpr int kSide = 2 * kKt * kLdsRow;            // doubles of one side's two stages
+    constexpr int kTile = kBlk * (kBlk + 1);            // doubles of the accumulator tile
+    static_assert(2 * kSide >= kTile + 2 * 4 * kBlk + 2 * kBlk + 2 * 4, "tile and sums must fit the staging buffers");
+    // one 40 KiB buffer, four workgroups to a CU: the two sides' stages during the K loop; before it (taper) and after
+    // it the tile in front and the small sums behind it, each use fenced from the next by a barrier
+    __shared__ double s_raw[2 * kSide];
+    double (*s_a)[kKt][kLdsRow] = reinterpret_cast<double (*)[kKt][kLdsRow]>(s_raw);
+    double (*s_b)[kKt][kLdsRow] = reinterpret_cast<double (*)[kKt][kLdsRow]>(s_raw + kSide);
+    double (*s_c)[kBlk + 1] = reinterpret_cast<double (*)[kBlk + 1]>(s_raw);
+    double (*s_part)[4][kBlk] = reinterpret_cast<double (*)[4][kBlk]>(s_raw + kTile);   // per-wave parts, column sums
+    double* s_si = s_raw + kTile + 2 * 4 * kBlk;
+    double* s_sj = s_si + kBlk;
+    double (*s_wpart)[4] = reinterpret_cast<double (*)[4]>(s_sj + kBlk);                // parts of sum w and sum w^2
+    const int w = blockIdx.x / P;
+    int bi, bj;
+    ts_block_pair(blockIdx.x % P, nb, bi, bj);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const T* xs = x + (long long)w_beg[w] * n;
+    // staging: thread tid stages column (tid & 63) of rows (tid >> 6) + 4 u, u < kStagePer, of both blocks
+    const int sc = lane, sr = wave;
+    const int ca = bi * kBlk + sc, cb = bj * kBlk + sc;
+    const bool va = ca < n, vb = cb < n;
+    const int ka = va ? ca : 0, kb = vb ? cb : 0;       // a column that exists, for loads whose value is not used
+    double ma, mb, inv;
+    if constexpr (kTaper) {
+        double pa = 0.0, pb = 0.0, q1 = 0.0, q2 = 0.0;
+        for (int t0 = sr; t0 < window; t0 += 4 * kStagePer) {      // kStagePer rows in flight, added in ascending t
+            T ga[kStagePer], gb[kStagePer];
+            double gw[kStagePer];
+#pragma unroll
+            for (int u = 0; u < kStagePer; ++u) {
+                const int tt = t0 + 4 * u < window ? t0 + 4 * u : 0;
+                ga[u] = xs[(long long)tt * n + ka];
+                gb[u] = xs[(long long)tt * n + kb];
+                gw[u] = taper[tt];
+            }
+#pragma unroll
+            for (int u = 0; u < kStagePer; ++u) {
+                if (t0 + 4 * u >= window) break;
+                const double wt = gw[u];
+                if (va) pa += wt * (double)ga[u];
+                if (vb) pb += wt * (double)gb[u];
+                q1 += wt;
+                q2 += wt * wt;
+            }
+        }
+        s_part[0][sr][sc] = pa;
+        s_part[1][sr][sc] = pb;
+        if (sc == 0) {
+            s_wpart[0][sr] = q1;
+            s_wpart[1][sr] = q2;
+        }
+        __syncthreads();
+        const double sw = (s_wpart[0][0] + s_wpart[0][1]) + (s_wpart[0][2] + s_wpart[0][3]);
+        const double sw2 = (s_wpart[1][0] + s_wpart[1][1]) + (s_wpart[1][2] + s_wpart[1][3]);
+        ma = ((s_part[0][0][sc] + s_part[0][1][sc]) + (s_part[0][2][sc] + s_part[0][3][sc])) / sw;
+        mb = ((s_part[1][0][sc] + s_part[1][1][sc]) + (s_part[1][2][sc] + s_part[1][3][sc])) / sw;
+        inv = 1.0 / (sw - sw2 / sw);
+        __syncthreads();                                // s_part is written again below
+    } else {
+        ma = va ? mean[(size_t)w * n + ca] : 0.0;
+        mb = vb ? mean[(size_t)w * n + cb] : 0.0;
+        inv = 1.0 / (double)(window - 1);               // np.cov: c *= np.true_divide(1, T - 1)
+    }
+    // Global loads are fetched raw, kDepth stages ahead and from an address that is always inside the window (row 0 or
+    // column 0 of it where the thread's own lies outside), so nothing waits on them until stage() centres, weights and
+    // stores them: a 50-row window has all its rows in flight at once instead of one round trip per stage.
+    constexpr int kDepth = kTaper ? 2 : 4;              // the taper's weights and products leave registers for two
+    T ga[kDepth][kStagePer], gb[kDepth][kStagePer];
+    double da = 0.0, db = 0.0;                          // this thread's rows of sum_t xc * (w * xc), columns ca and cb
+    auto fetch = [&](int slot, int k0) {
+#pragma unroll
+        for (int u = 0; u < kStagePer; ++u) {
+            const int t = k0 + sr + 4 * u;
+            const int tt = t < window ? t : 0;
+            ga[slot][u] = xs[(long long)tt * n + ka];
+            gb[slot][u] = xs[(long long)tt * n + kb];
+        }
+    };
+    auto stage = [&](int slot, int buf, int k0) {
+#pragma unroll
+        for (int u = 0; u < kStagePer; ++u) {
+            const int t = k0 + sr + 4 * u;
+            const bool in = t < window;
+            const double xa = (in && va) ? (double)ga[slot][u] - ma : 0.0;
+            const double xb = (in && vb) ? (double)gb[slot][u] - mb : 0.0;
+            double wa = xa, wb = xb;
+            if constexpr (kTaper) {
+                const double wt = in ? taper[t] : 0.0;
+                wa = wt * xa;
+                wb = wt * xb;
+            }
+            da += xa * wa;
+            db += xb * wb;
+            s_a[buf][sr + 4 * u][sc] = xa;
+            s_b[buf][sr + 4 * u][sc] = wb;
+        }
+    };
+    // wave w owns rows 32 (w >> 1) .., columns 32 (w & 1) .. of the block; a diagonal block's strictly lower
+    // quadrant is never read (the epilogue reads i <= j), so that wave only stages
+    const int wr = wave >> 1, wc = wave & 1;
+    const bool busy = !(bi == bj && wr > wc);
+    f64x4 acc[2][2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) acc[r][c] = f64x4{0.0, 0.0, 0.0, 0.0};
+    const int nk = (window + kKt - 1) / kKt;
+#pragma unroll
+    for (int j = 0; j < kDepth; ++j)
+        if (j < nk) fetch(j, j * kKt);
+    stage(0, 0, 0);
+    __syncthreads();
+    const int fr = lane & 15, fk = lane >> 4;
+    for (int kc0 = 0; kc0 < nk; kc0 += kDepth) {
+#pragma unroll
+        for (int j = 0; j < kDepth; ++j) {              // stage kc lives in slot kc % kDepth = j and buffer kc & 1
+            const int kc = kc0 + j;
+            if (kc >= nk) break;
+            const int buf = j & 1;
+            if (kc + kDepth < nk) fetch(j, (kc + kDepth) * kKt);        // slot j was staged an iteration ago
+            if (busy) {
+#pragma unroll
+                for (int kk = 0; kk < kKt / 4; ++kk) {
+                    if (kc * kKt + 4 * kk >= window) break;     // the last stage's all-zero row quads: windows are short
+                    const int k = 4 * kk + fk;
+                    double a[2], b[2];
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) a[r] = s_a[buf][k][32 * wr + 16 * r + fr];
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) b[c] = s_b[buf][k][32 * wc + 16 * c + fr];
+#pragma unroll
+                    for (int r = 0; r < 2; ++r)
+#pragma unroll
+                        for (int c = 0; c < 2; ++c)
+                            acc[r][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[r], b[c], acc[r][c], 0, 0, 0);
+                }
+            }
+            if (kc + 1 < nk) stage((j + 1) % kDepth, buf ^ 1, (kc + 1) * kKt);
+            __syncthreads();
+        }
+    }
+    // C of the block into the tile (row = block row, column = block column), the column sums into s_part
+    s_part[0][sr][sc] = da;
+    s_part[1][sr][sc] = db;
+    if (busy) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    s_c[32 * wr + 16 * r + fk + 4 * q][32 * wc + 16 * c + fr] = acc[r][c][q] * inv;
+    }
+    __syncthreads();
+    double* m = fc + (size_t)w * n * n;
+    if (n == 1) {                                       // np.corrcoef of one ROI: cov is a scalar, returned as c / c
+        if (tid == 0) m[0] = s_c[0][0] / s_c[0][0];
+        return;
+    }
+    if (tid < 2 * kBlk) {
+        const int side = tid >> 6, c = tid & 63;
+        const double sum = (s_part[side][0][c] + s_part[side][1][c]) + (s_part[side][2][c] + s_part[side][3][c]);
+        (side ? s_sj : s_si)[c] = sqrt(sum * inv);
+    }
+    __syncthreads();
+    const int i0 = bi * kBlk, j0 = bj * kBlk;
+    // upper block: row i = i0 + r, column j = j0 + c (a diagonal block reads C_ji below its diagonal)
+#pragma unroll 4
+    for (int e = tid; e < kBlk * kBlk; e += kGramThreads) {
+        const int r = e >> 6, c = e & 63, i = i0 + r, j = j0 + c;
+        if (i >= n || j >= n) continue;
+        const double cij = (i <= j) ? s_c[r][c] : s_c[c][r];
+        m[(size_t)i * n + j] = ts_clip((cij / s_si[r]) / s_sj[c]);
+    }
+    if (bi == bj) return;
+    // mirror block: row j = j0 + r, column i = i0 + c: R_ji = (C_ij / s_j) / s_i
+#pragma unroll 4
+    for (int e = tid; e < kBlk * kBlk; e += kGramThreads) {
+        const int r = e >> 6, c = e & 63, j = j0 + r, i = i0 + c;
+        if (i >= n || j >= n) continue;
+        m[(size_t)j * n + i] = ts_clip((s_c[c][r] / s_sj[r]) / s_si[c]);
+    }
+}
+
 int ts_check(int S, int n) {
     if (S < 0 || n < 1) return GNM_ERR_BAD_ARG;
     if (n > kTsMaxN) return GNM_ERR_UNSUPPORTED;
@@ -314,10 +530,65 @@ extern "C" int gnm_timeseries_means(const void* x, int x_f64, const int64_t* t_o
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (x_f64)
         hipLaunchKernelGGL(gnm_ts_means_kernel<double>, dim3(S * bps), dim3(kMeanThreads), 0, s,
-                           static_cast<const double*>(x), t_off, n, bps, mean);
+                           static_cast<const double*>(x), t_off, 0, n, bps, mean);
     else
         hipLaunchKernelGGL(gnm_ts_means_kernel<float>, dim3(S * bps), dim3(kMeanThreads), 0, s,
-                           static_cast<const float*>(x), t_off, n, bps, mean);
+                           static_cast<const float*>(x), t_off, 0, n, bps, mean);
+    GNM_CHECK_LAUNCH();
+    return GNM_OK;
+}
+
+// the most windows one gnm_dynfc_corr launch takes at n ROIs (0 for an unsupported n): the caller splits above it
+extern "C" long long gnm_dynfc_max_windows(int n) {
+    if (n < 1 || n > kTsMaxN) return 0;
+    return (0x7fffffffLL / kGramThreads) / ts_pairs(n);
+}
+
+// the same column means for window w = rows w_beg[w] .. w_beg[w] + window: bitwise gnm_timeseries_means of those rows
+extern "C" int gnm_dynfc_means(const void* x, int x_f64, const int64_t* w_beg, int window, int W, int n, double* mean,
+                               void* stream) {
+    if (int e = ts_check(W, n)) return e;
+    if (window < 2) return GNM_ERR_BAD_ARG;
+    if (W == 0) return GNM_OK;
+    if (!x || !w_beg || !mean) return GNM_ERR_BAD_ARG;
+    const int bps = (n + kMeanThreads - 1) / kMeanThreads;
+    if ((long long)W * bps > 0x7fffffffLL / kMeanThreads) return GNM_ERR_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (x_f64)
+        hipLaunchKernelGGL(gnm_ts_means_kernel<double>, dim3(W * bps), dim3(kMeanThreads), 0, s,
+                           static_cast<const double*>(x), w_beg, window, n, bps, mean);
+    else
+        hipLaunchKernelGGL(gnm_ts_means_kernel<float>, dim3(W * bps), dim3(kMeanThreads), 0, s,
+                           static_cast<const float*>(x), w_beg, window, n, bps, mean);
+    GNM_CHECK_LAUNCH();
+    return GNM_OK;
+}
+
+// finished R of every window, one launch: taper NULL is np.corrcoef of the window's rows (mean: gnm_dynfc_means'),
+// taper [window] is the aweights form (mean is not read)
+extern "C" int gnm_dynfc_corr(const void* x, int x_f64, const int64_t* w_beg, int window, const double* mean,
+                              const double* taper, int W, int n, double* fc, void* stream) {
+    if (int e = ts_check(W, n)) return e;
+    if (window < 2) return GNM_ERR_BAD_ARG;
+    if (W == 0) return GNM_OK;
+    if (!x || !w_beg || !fc || (!mean && !taper)) return GNM_ERR_BAD_ARG;
+    const long long P = ts_pairs(n);
+    if ((long long)W * P > 0x7fffffffLL / kGramThreads) return GNM_ERR_UNSUPPORTED;
+    const int nb = (n + kBlk - 1) / kBlk;
+    const dim3 grid((unsigned)(W * P)), block(kGramThreads);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (x_f64 && taper)
+        hipLaunchKernelGGL((gnm_dynfc_corr_kernel<double, true>), grid, block, 0, s, static_cast<const double*>(x),
+                           w_beg, window, mean, taper, n, nb, (int)P, fc);
+    else if (x_f64)
+        hipLaunchKernelGGL((gnm_dynfc_corr_kernel<double, false>), grid, block, 0, s, static_cast<const double*>(x),
+                           w_beg, window, mean, taper, n, nb, (int)P, fc);
+    else if (taper)
+        hipLaunchKernelGGL((gnm_dynfc_corr_kernel<float, true>), grid, block, 0, s, static_cast<const float*>(x),
+                           w_beg, window, mean, taper, n, nb, (int)P, fc);
+    else
+        hipLaunchKernelGGL((gnm_dynfc_corr_kernel<float, false>), grid, block, 0, s, static_cast<const float*>(x),
+                           w_beg, window, mean, taper, n, nb, (int)P, fc);
     GNM_CHECK_LAUNCH();
     return GNM_OK;
 }

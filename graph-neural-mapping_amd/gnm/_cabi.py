@@ -123,6 +123,9 @@ SIGNATURES = {
     "gnm_timeseries_zscores": (_i, [_p, _i, _i, _p, _p, _p]),
     "gnm_timeseries_gram": (_i, [_p, _i, _p, _p, _i, _i, _p, _p, _p]),
     "gnm_timeseries_normalize": (_i, [_p, _i, _i, _p, _p]),
+    "gnm_dynfc_max_windows": (_ll, [_i]),
+    "gnm_dynfc_means": (_i, [_p, _i, _p, _i, _i, _i, _p, _p]),
+    "gnm_dynfc_corr": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _p, _p]),
     "gnm_adam_step": (_i, [_p, _p, _p, _p, _ll, _p, _p, _p]),
 }
 

@@ -17,6 +17,10 @@ From ROI time series instead of FC matrices (csrc/timeseries.hip; the contract i
 connectivity_from_timeseries):
 
     graphs = graphs_from_timeseries(model_or_arena, ts, sparsity, labels, node_features="mean_bold")
+
+One graph per sliding window of the series (dynamic connectivity; the contract is written out above window_starts):
+
+    graphs, windows = dynamic_graphs_from_timeseries(model_or_arena, ts, sparsity, labels, window, stride=1)
 """
 import numbers
 
@@ -388,3 +392,176 @@ def graphs_from_timeseries(model_or_arena, ts, sparsity, labels, node_features="
     feats = _ts_zscores(mean, S, n, torch.float32) if isinstance(node_features, str) else node_features
     gids = arena.add_connectivity(fc, sparsity, feats)
     return [ConnectomeGraph(arena, gid, n, lab) for gid, lab in zip(gids, labels)]
+
+
+# ---------------------------------------------------------------------------------------------------- sliding windows
+# Dynamic functional connectivity: one correlation matrix per sliding window of the same series, rectangular
+# (np.corrcoef of the window's rows) or tapered (np.cov(rows, aweights=taper), normalised as np.corrcoef does).  The
+# windows are described to the device (first row and one common length), never sliced out or copied, and
+# gnm_dynfc_corr (csrc/timeseries.hip) writes each finished R once.  A window's FC and features are bitwise the same
+# whichever call, stride, stack or list it is part of.
+
+# most bytes of window FC dynamic_graphs_from_timeseries holds at a time (one chunk; the buffer is reused)
+DYNFC_WORK_BYTES = 1 << 30
+
+
+def _window_args(window, stride):
+    if isinstance(window, (bool, np.bool_)) or not isinstance(window, numbers.Integral):
+        raise ValueError("window must be an int >= 2, got %r" % (window,))
+    if isinstance(stride, (bool, np.bool_)) or not isinstance(stride, numbers.Integral):
+        raise ValueError("stride must be an int >= 1, got %r" % (stride,))
+    window, stride = int(window), int(stride)
+    if window < 2:
+        raise ValueError("window must be >= 2 (a correlation needs two rows), got %d" % window)
+    if stride < 1:
+        raise ValueError("stride must be >= 1, got %d" % stride)
+    return window, stride
+
+
+def window_starts(T, window, stride):
+    """First rows of the sliding windows of a T-row series: np.arange(0, T - window + 1, stride) as int64.  Trailing
+    rows that do not fill a window are dropped."""
+    window, stride = _window_args(window, stride)
+    T = int(T)
+    if T < window:
+        raise ValueError("a series of %d time points is shorter than the window (%d)" % (T, window))
+    return np.arange(0, T - window + 1, stride, dtype=np.int64)
+
+
+def _taper_arg(taper, window):
+    """None, or the taper as a float64 numpy array [window]: finite, non-negative, at least two positive weights (with
+    one, np.cov's normalisation sum w - sum w^2 / sum w is zero)"""
+    if taper is None:
+        return None
+    w = taper.detach().cpu().numpy() if torch.is_tensor(taper) else np.asarray(taper)
+    if w.ndim != 1 or w.shape[0] != window:
+        raise ValueError("taper must be 1-D with window = %d weights, got shape %s" % (window, tuple(w.shape)))
+    if w.dtype.kind not in "fiu":
+        raise ValueError("taper must be real numbers, got dtype %s" % w.dtype)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("taper weights must be finite and non-negative")
+    if int((w > 0).sum()) < 2:
+        raise ValueError("taper needs at least two positive weights")
+    return w
+
+
+def _plan_windows(t_off, window, stride):
+    """(w_beg [sum W] int64: first row of each window in the packed series, windows [sum W, 3] int64: (subject, window
+    index, first row within the subject), counts [S]): subject-major, window-minor"""
+    begs, rows = [], []
+    for s in range(len(t_off) - 1):
+        T = int(t_off[s + 1] - t_off[s])
+        if T < window:
+            raise ValueError("ts[%d] has %d time points, fewer than the window (%d)" % (s, T, window))
+        st = window_starts(T, window, stride)
+        begs.append(t_off[s] + st)
+        rows.append(np.stack([np.full(st.shape[0], s, np.int64), np.arange(st.shape[0], dtype=np.int64), st], 1))
+    counts = np.array([b.shape[0] for b in begs], dtype=np.int64)
+    return np.concatenate(begs).astype(np.int64), np.concatenate(rows), counts
+
+
+def _plan_chunks(total, n, budget):
+    """[(lo, hi)] covering windows 0 .. total once and in order, each chunk's [hi - lo, n, n] float64 FC within
+    `budget` bytes (one window per chunk where a single matrix is larger)"""
+    per = max(1, int(budget) // (8 * n * n))
+    return [(lo, min(total, lo + per)) for lo in range(0, total, per)]
+
+
+def _dyn_means(x, w_beg, window, n):
+    W = int(w_beg.shape[0])
+    mean = torch.empty((W, n), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        check(lib.gnm_dynfc_means(x.data_ptr(), int(x.dtype == torch.float64), w_beg.data_ptr(), window, W, n,
+                                  mean.data_ptr(), st), "gnm_dynfc_means")
+    return mean
+
+
+def _dyn_corr(x, w_beg, window, mean, taper, n, out):
+    """out[w] = R of window w for every window of w_beg; one launch, split where the grid would pass the launch limit"""
+    W = int(w_beg.shape[0])
+    step = int(lib.gnm_dynfc_max_windows(n))
+    with torch.cuda.device(x.device):
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        for lo in range(0, W, step):
+            m = min(W, lo + step) - lo
+            check(lib.gnm_dynfc_corr(x.data_ptr(), int(x.dtype == torch.float64), w_beg[lo:].data_ptr(), window,
+                                     None if mean is None else mean[lo:].data_ptr(),
+                                     None if taper is None else taper.data_ptr(), m, n, out[lo:].data_ptr(), st),
+                  "gnm_dynfc_corr")
+    return out
+
+
+def dynamic_connectivity_from_timeseries(ts, window, stride=1, taper=None, device=None):
+    """One FC matrix per sliding window (first rows window_starts(T_s, window, stride)), float64 on the device:
+    [S, W, n, n] for an [S, T, n] stack, a list of [W_s, n, n] views of one buffer for a list of [T_s, n] arrays.
+    taper None: np.corrcoef(rows, rowvar=False) of each window; taper [window] (finite, non-negative, two positive
+    weights at least): np.cov(rows, rowvar=False, aweights=taper) normalised by its diagonal and clipped, as np.corrcoef
+    does.  Within 1e-12 elementwise of numpy with its NaN pattern.  ts as in connectivity_from_timeseries."""
+    window, stride = _window_args(window, stride)
+    w = _taper_arg(taper, window)
+    x, t_off, S, n = _timeseries(ts)
+    w_beg, _, counts = _plan_windows(t_off, window, stride)
+    dev = torch.device(device) if device is not None else _ts_device(ts)
+    x, _ = _to_device(x, t_off, dev)
+    w_beg = torch.from_numpy(w_beg).to(dev)
+    W = int(w_beg.shape[0])
+    fc = torch.empty((W, n, n), dtype=torch.float64, device=dev)
+    mean = _dyn_means(x, w_beg, window, n) if w is None else None
+    _dyn_corr(x, w_beg, window, mean, None if w is None else torch.from_numpy(w).to(dev), n, fc)
+    if isinstance(ts, (list, tuple)):
+        return list(torch.split(fc, counts.tolist()))
+    return fc.view(S, W // S, n, n)
+
+
+def dynamic_graphs_from_timeseries(model_or_arena, ts, sparsity, labels, window, stride=1, taper=None,
+                                   node_features="mean_bold"):
+    """(graphs, windows): one graph of load_data's shape per sliding window, registered in the arena.  graphs is a flat
+    list of ConnectomeGraph, subject-major and window-minor, each with its subject's label; windows [sum W, 3] int64 holds
+    (subject, window index, first row within the subject) of each.  node_features: "mean_bold" (the z-scores of the
+    plain window means, whatever the taper) or an array: [n, F] for every window, or [S, n, F] per subject.  The FC never
+    exists whole: windows go through means, z-scores, the fused correlation and GraphArena.add_connectivity in chunks of
+    at most DYNFC_WORK_BYTES of FC, in one buffer that is reused."""
+    arena = model_or_arena.arena() if hasattr(model_or_arena, "arena") and callable(model_or_arena.arena) \
+        else model_or_arena
+    _sparsity(sparsity)
+    window, stride = _window_args(window, stride)
+    w = _taper_arg(taper, window)
+    mean_bold = isinstance(node_features, str)
+    if mean_bold and node_features != "mean_bold":
+        raise ValueError("node_features must be \"mean_bold\" or an array, got %r" % (node_features,))
+    labels = [int(v) for v in (labels.tolist() if hasattr(labels, "tolist") else labels)]
+    x, t_off, S, n = _timeseries(ts)
+    if len(labels) != S:
+        raise ValueError("labels: %d values for %d subjects" % (len(labels), S))
+    w_beg_h, windows, _ = _plan_windows(t_off, window, stride)
+    per_subject = None
+    if not mean_bold:
+        ft = node_features if torch.is_tensor(node_features) else torch.as_tensor(np.asarray(node_features))
+        if ft.dim() == 3:
+            if int(ft.shape[0]) != S:
+                raise ValueError("node_features [S, n, F]: %d subjects for %d series" % (int(ft.shape[0]), S))
+            per_subject = ft
+    dev = arena.device
+    x, _ = _to_device(x, t_off, dev)
+    w_beg = torch.from_numpy(w_beg_h).to(dev)
+    subj = torch.from_numpy(windows[:, 0].copy()).to(dev)
+    if per_subject is not None:
+        per_subject = per_subject.to(device=dev, dtype=torch.float32)
+    wd = None if w is None else torch.from_numpy(w).to(dev)
+    total = int(w_beg.shape[0])
+    chunks = _plan_chunks(total, n, DYNFC_WORK_BYTES)
+    fc = torch.empty((max(hi - lo for lo, hi in chunks), n, n), dtype=torch.float64, device=dev)
+    gids = []
+    for lo, hi in chunks:
+        m = hi - lo
+        mean = _dyn_means(x, w_beg[lo:hi], window, n) if (w is None or mean_bold) else None
+        if mean_bold:
+            feats = _ts_zscores(mean, m, n, torch.float32)
+        else:
+            feats = node_features if per_subject is None else per_subject[subj[lo:hi]]
+        _dyn_corr(x, w_beg[lo:hi], window, mean if w is None else None, wd, n, fc[:m])
+        gids += arena.add_connectivity(fc[:m], sparsity, feats)
+    graphs = [ConnectomeGraph(arena, gid, n, labels[s]) for gid, s in zip(gids, windows[:, 0].tolist())]
+    return graphs, windows

@@ -686,6 +686,25 @@ int gnm_timeseries_gram(const void* x, int x_f64, const int64_t* t_off, const do
                         double* diag, void* stream);
 int gnm_timeseries_normalize(const double* diag, int S, int n, double* fc, void* stream);
 
+/* ---- sliding-window connectivity of the same packed series (csrc/timeseries.hip) ----------
+ * Windows are described, not copied: window w is the `window` rows from row w_beg[w] of x on (int64 [W], device, any
+ * order, overlapping freely; the caller keeps every w_beg[w] + window within x).  One common length, window >= 2
+ * (GNM_ERR_BAD_ARG below); n as above; W = 0 is GNM_OK; every argument is checked before anything is launched.
+ * gnm_dynfc_max_windows: the most windows one gnm_dynfc_corr launch takes at n ROIs (its grid is W x the 64 x 64 upper
+ *   block pairs); above it gnm_dynfc_corr returns GNM_ERR_UNSUPPORTED and the caller splits.  0 for an unsupported n.
+ * gnm_dynfc_means: mean[w, i] = the plain column mean of window w in numpy's pairwise order, bitwise what
+ *   gnm_timeseries_means gives for the same rows as a subject of their own; feeds gnm_timeseries_zscores unchanged.
+ * gnm_dynfc_corr: fc[w] ([W, n, n] fp64) = finished R of window w, both triangles, each entry written once, clipped to
+ *   [-1, 1] with NaN kept (n = 1: numpy's c / c).  taper NULL: np.corrcoef of the window's rows, centred on mean[w]
+ *   ([W, n], gnm_dynfc_means').  taper [window] fp64 (device): np.cov's aweights form, centre sum_t w_t x_t / sum_t w_t,
+ *   C = Xc^T (w * Xc) / (sum w - sum w^2 / sum w); mean is not read and may be NULL.  A window's R does not depend on the
+ *   other windows of the launch; values outside a window never reach it. */
+long long gnm_dynfc_max_windows(int n);
+int gnm_dynfc_means(const void* x, int x_f64, const int64_t* w_beg, int window, int W, int n, double* mean,
+                    void* stream);
+int gnm_dynfc_corr(const void* x, int x_f64, const int64_t* w_beg, int window, const double* mean, const double* taper,
+                   int W, int n, double* fc, void* stream);
+
 /* gnm_adam_step replaces optimizer.step() of optim.Adam(model.parameters(), lr) (main.py:136, 39-41) on a flat
  * fp32 parameter buffer: torch.optim.Adam's default update (no AMSGrad, L2 weight decay).
  * hyper: DEVICE array of 6 doubles {lr, beta1, beta2, eps, weight_decay, grad_scale} (grad is multiplied by
