@@ -9,53 +9,11 @@ import numpy as np
 import pytest
 import torch
 
+from dynfc_cases import (NS, WINDOWS, bits_eq, check_against_numpy, host_windows, nan_windows, same_graphs, series,
+                         tapers)
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-NS = [1, 2, 7, 63, 64, 65, 129, 400]              # both sides of the 64-column block, the skipped lower quadrant
-WINDOWS = [2, 3, 15, 16, 17, 32, 33, 50]          # both sides of the 16-row stage
-
-
-def ref_fc(xw, w=None):
-    n = xw.shape[1]
-    if w is None:
-        return np.asarray(np.corrcoef(xw, rowvar=False)).reshape(n, n)
-    c = np.atleast_2d(np.cov(xw, rowvar=False, aweights=w))
-    s = np.sqrt(np.diag(c)); r = c / s[:, None]; r = r / s[None, :]
-    return np.clip(r, -1, 1)
-
-
-def bits_eq(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def series(rng, T, n, offset=0.0, scale=1.0):
-    shared = rng.standard_normal((T, 1))
-    return offset + scale * (rng.standard_normal((T, n)) + 0.5 * shared * rng.standard_normal((1, n)))
-
-
-def tapers(window):
-    t = np.arange(window, dtype=np.float64)
-    gauss = np.exp(-0.5 * ((t - (window - 1) / 2.0) / (window / 4.0)) ** 2)
-    return [None, np.hamming(window + 2)[1:-1], gauss]
-
-
-def host_windows(ts, window, stride):
-    from gnm.connectome import window_starts
-    return [(s, k, int(t0)) for s, x in enumerate(ts) for k, t0 in enumerate(window_starts(len(x), window, stride))]
-
-
-def check_against_numpy(got, xw, w, what):
-    with np.errstate(all="ignore"):
-        want = ref_fc(xw, w)
-    assert got.shape == want.shape and got.dtype == np.float64, what
-    assert np.array_equal(np.isnan(got), np.isnan(want)), what
-    ok = ~np.isnan(want)
-    err = np.abs(got[ok] - want[ok]).max(initial=0.0)
-    assert err <= 1e-12, (what, err)
-    assert np.all(np.abs(got[ok]) <= 1.0), what
-    return err
 
 
 @pytest.mark.parametrize("window", WINDOWS)
@@ -91,10 +49,6 @@ def test_stack_shape_and_windows():
     for s in range(3):
         for k in range(8):
             check_against_numpy(got[s, k], ts[s, 4 * k:4 * k + 10], None, (s, k))
-
-
-def nan_windows(got):
-    return [k for k in range(got.shape[0]) if np.isnan(got[k]).any()]
 
 
 def test_constant_roi_inside_exactly_one_rectangular_window():
@@ -205,14 +159,6 @@ def test_window_mean_bold_is_bitwise_the_static_paths(dtype):
     assert bits_eq(C._ts_zscores(mean, len(where), n, torch.float64).cpu().numpy(), want64)
     sx, st, sS, _ = C._as_timeseries(slices, torch.device(DEV))
     assert bits_eq(mean.cpu().numpy(), C._ts_means(sx, st, sS, n).cpu().numpy())
-
-
-def same_graphs(a, b):
-    assert len(a) == len(b)
-    for g, h in zip(a, b):
-        assert np.array_equal(g.edge_mat.numpy(), h.edge_mat.numpy())
-        assert g.neighbors == h.neighbors and g.max_neighbor == h.max_neighbor and g.label == h.label
-        assert bits_eq(g.node_features.numpy(), h.node_features.numpy())
 
 
 @pytest.mark.parametrize("tapered", [False, True])
