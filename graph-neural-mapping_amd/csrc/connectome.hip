@@ -7,6 +7,8 @@
 //                              degrees, and the node order networkx gives the graph load_data builds (util.py:43-76):
 //                              rank[y] = place of y in pi, the nodes sorted by (t(y), y), t(y) the first row i < y with
 //                              an edge {i, y} (y itself if none).  Per graph: edge count and "has an isolated node".
+//   gnm_connectome_knn_structure  the same workspace from another edge rule: row i selects its k largest entries, and
+//                              {u, v} is an edge when either end (or, "mutual", each end) selects the other.
 //   gnm_connectome_emit        the graph's arena CSR (util.py:97-103 edge_mat, then GraphArena.add's host CSR,
 //                              gnm_csr_from_edge_mat + gnm_csr_parity_order): row x lists its later-in-pi neighbours by
 //                              ascending id, then its earlier-in-pi neighbours in pi order, then the parity reorder.
@@ -157,44 +159,47 @@ __global__ void __launch_bounds__(kCtThreads) gnm_connectome_thr_kernel(const do
 }
 
 // ---------------------------------------------------------------------------------------------------- structure
-__global__ void __launch_bounds__(kCtThreads) gnm_connectome_structure_kernel(const double* __restrict__ fc, int n,
-                                                                             const double* __restrict__ thr,
-                                                                             uint32_t* __restrict__ work,
-                                                                             int32_t* __restrict__ nnz_out,
-                                                                             int32_t* __restrict__ iso_out) {
-    __shared__ int s_t[kCtMaxN], s_deg[kCtMaxN], s_cnt[kCtMaxN];
-    __shared__ int s_wave[kCtWaves];
-    __shared__ int s_red[2];
-    const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+// From an edge rule to the workspace of one graph: upper-triangle bit rows, degrees, the node order, nnz and iso.  The
+// rule is a type with  load(i, v) -> value  (called for i < v < n, all loads of four chunks before their tests) and
+// test(value) -> bool: the percentile rule reads fc and compares, the kNN rule reads two selection bits.
+struct CtLds {
+    int *t, *deg, *cnt;     // [kCtMaxN] each
+    int *wave;              // [kCtWaves]
+    int *red;               // [2]
+};
+
+template <class Rule>
+__device__ __forceinline__ void ct_structure(const Rule& rule, int n, int g, uint32_t* __restrict__ work,
+                                             int32_t* __restrict__ nnz_out, int32_t* __restrict__ iso_out,
+                                             const CtLds& s) {
+    int *s_t = s.t, *s_deg = s.deg, *s_cnt = s.cnt, *s_wave = s.wave, *s_red = s.red;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int W = ct_row_words(n);
-    const double* m = fc + (size_t)g * (size_t)n * (size_t)n;
     uint32_t* bits = work + (size_t)g * (size_t)ct_graph_words(n);
     int32_t* rank = reinterpret_cast<int32_t*>(bits + (size_t)n * W);
     int32_t* deg = rank + n;
-    const double th = thr[g];
     for (int v = t; v < n; v += kCtThreads) { s_t[v] = v; s_deg[v] = 0; s_cnt[v] = 0; }
     if (t < 2) s_red[t] = 0;
     __syncthreads();
     // upper-triangle edges, one wave per row i: bits of v > i, degrees of both ends, t(v) = min i
     for (int i = wave; i < n; i += kCtWaves) {
-        const double* row = m + (size_t)i * n;
         uint32_t* ub = bits + (size_t)i * W;
         const int first = (i + 1) & ~63;                      // 64-column chunk holding column i + 1
         for (int w = lane; w < (first >> 5) && w < W; w += 64) ub[w] = 0u;
         int up = 0;
         for (int base = first; base < n; base += 256) {
-            double x[4];
+            typename Rule::value x[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int v = base + 64 * u + lane;
-                x[u] = (v > i && v < n) ? row[v] : 0.0;
+                x[u] = (v > i && v < n) ? rule.load(i, v) : typename Rule::value(0);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int b0 = base + 64 * u;
                 if (b0 >= n) break;
                 const int v = b0 + lane;
-                const bool e = v > i && v < n && x[u] > th;
+                const bool e = v > i && v < n && rule.test(x[u]);
                 const unsigned long long bm = __ballot(e);
                 if (lane == 0) {
                     ub[b0 >> 5] = (uint32_t)bm;
@@ -231,6 +236,168 @@ __global__ void __launch_bounds__(kCtThreads) gnm_connectome_structure_kernel(co
         }
     }
     if (t == 0) { nnz_out[g] = s_red[0]; iso_out[g] = s_red[1]; }
+}
+
+// dataset.py:94-100: fc[s, i, v] > thr[s]
+struct CtPercentileRule {
+    typedef double value;
+    const double* __restrict__ m;
+    int n;
+    double th;
+    __device__ __forceinline__ double load(int i, int v) const { return m[(size_t)i * n + v]; }
+    __device__ __forceinline__ bool test(double x) const { return x > th; }
+};
+
+__global__ void __launch_bounds__(kCtThreads) gnm_connectome_structure_kernel(const double* __restrict__ fc, int n,
+                                                                             const double* __restrict__ thr,
+                                                                             uint32_t* __restrict__ work,
+                                                                             int32_t* __restrict__ nnz_out,
+                                                                             int32_t* __restrict__ iso_out) {
+    __shared__ int s_t[kCtMaxN], s_deg[kCtMaxN], s_cnt[kCtMaxN];
+    __shared__ int s_wave[kCtWaves];
+    __shared__ int s_red[2];
+    const int g = blockIdx.x;
+    const CtPercentileRule rule{fc + (size_t)g * (size_t)n * (size_t)n, n, thr[g]};
+    ct_structure(rule, n, g, work, nnz_out, iso_out, CtLds{s_t, s_deg, s_cnt, s_wave, s_red});
+}
+
+// ---------------------------------------------------------------------------------------------------- kNN structure
+// k-nearest-neighbour edges of one matrix fc[s] ([n, n], read as stored: it need not be symmetric):
+//   candidates  of row i: the columns v != i with fc[s, i, v] not NaN;
+//   key         fc[s, i, v], or |fc[s, i, v]| (flags bit 1, "absolute"); +0.0 and -0.0 are one key, +-inf ordinary;
+//   order       descending key, ascending column among equal keys;
+//   selection   row i selects its first min(k, number of candidates) candidates in that order;
+//   edge        {u, v}, u < v: u selects v or v selects u; with flags bit 0 ("mutual"): and.
+// Phase 1, one wave per row: the min(k, candidates)-th key by an 8-bit radix select over ct_key (the wave's histogram in
+// LDS, the digit found by a wave scan from the top bin down), left as soon as the bucket of the sought key is wanted
+// whole; then one pass takes every column above the found prefix and the first `need` columns equal to it, ascending
+// (ballot prefix per 64-column chunk), and writes the row's directed selection bits to sel.  Phase 2, after a barrier:
+// ct_structure with the rule sel[i][v] | sel[v][i] (or &).  No float arithmetic, no float atomics: the bits depend on
+// the matrix alone.  The histograms of phase 1 lie in the LDS that phase 2 uses for its bucket counts.
+__device__ __forceinline__ void ct_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the key of a candidate value: -0.0 made +0.0 (ct_key orders them apart), the sign dropped under `absolute`
+__device__ __forceinline__ unsigned long long ct_knn_key(double x, bool absolute) {
+    if (absolute) x = fabs(x);
+    if (x == 0.0) x = 0.0;
+    return ct_key(x);
+}
+
+struct CtKnnRule {
+    typedef uint32_t value;
+    const uint32_t* sel;    // [n, W] of this graph, written by this workgroup in phase 1
+    int W;
+    bool mutual;
+    __device__ __forceinline__ uint32_t load(int i, int v) const {
+        const uint32_t a = (sel[(size_t)i * W + (v >> 5)] >> (v & 31)) & 1u;
+        const uint32_t b = (sel[(size_t)v * W + (i >> 5)] >> (i & 31)) & 1u;
+        return mutual ? (a & b) : (a | b);
+    }
+    __device__ __forceinline__ bool test(uint32_t x) const { return x != 0u; }
+};
+
+static_assert(kCtWaves * 256 <= kCtMaxN, "the per-wave histograms of the kNN select alias the bucket counts");
+
+__global__ void __launch_bounds__(kCtThreads) gnm_connectome_knn_kernel(const double* __restrict__ fc, int n, int k,
+                                                                       int flags, uint32_t* sel_all,
+                                                                       uint32_t* __restrict__ work,
+                                                                       int32_t* __restrict__ nnz_out,
+                                                                       int32_t* __restrict__ iso_out) {
+    __shared__ int s_t[kCtMaxN], s_deg[kCtMaxN], s_cnt[kCtMaxN];
+    __shared__ int s_wave[kCtWaves];
+    __shared__ int s_red[2];
+    const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int W = ct_row_words(n);
+    const bool absolute = flags & 2;
+    const double* m = fc + (size_t)g * (size_t)n * (size_t)n;
+    uint32_t* sel = sel_all + (size_t)g * (size_t)n * W;
+    unsigned* hist = reinterpret_cast<unsigned*>(s_cnt) + wave * 256;
+    const unsigned long long below = lanes_below();
+    for (int i = wave; i < n; i += kCtWaves) {
+        const double* row = m + (size_t)i * n;
+        unsigned long long prefix = 0, mask = 0;
+        int need = min(k, n - 1);
+        for (int shift = 56; shift >= 0; shift -= 8) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) hist[4 * lane + j] = 0u;
+            ct_wave_sync();
+            for (int base = 0; base < n; base += 256) {
+                double x[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int v = base + 64 * u + lane;
+                    x[u] = (v < n && v != i) ? row[v] : __longlong_as_double(0x7ff8000000000000ll);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (x[u] == x[u]) {
+                        const unsigned long long key = ct_knn_key(x[u], absolute);
+                        if ((key & mask) == prefix) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
+                    }
+                }
+            }
+            ct_wave_sync();
+            // bins 4 lane .. 4 lane + 3 in this lane; above = keys in the bins of higher lanes
+            int h[4], mine = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { h[j] = (int)hist[4 * lane + j]; mine += h[j]; }
+            int incl = mine;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int o = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += o;
+            }
+            const int total = __shfl(incl, 63, 64);
+            if (shift == 56) need = min(need, total);          // total: the row's candidates
+            if (need == 0) { prefix = mask = ~0ull; break; }   // nothing to select: no key is above or equal
+            int above = total - incl, digit = 0, count = 0;
+            const bool here = above < need && need <= above + mine;
+            if (here) {
+#pragma unroll
+                for (int j = 3; j >= 0; --j) {
+                    if (need <= above + h[j]) { digit = 4 * lane + j; count = h[j]; break; }
+                    above += h[j];
+                }
+            }
+            const int src = __ffsll((long long)__ballot(here)) - 1;      // exactly one lane
+            digit = __shfl(digit, src, 64);
+            above = __shfl(above, src, 64);
+            count = __shfl(count, src, 64);
+            need -= above;
+            prefix |= (unsigned long long)digit << shift;
+            mask |= 255ull << shift;
+            if (need == count) break;                          // the whole bucket is selected
+        }
+        // every column above the prefix, then the first `need` columns equal to it
+        uint32_t* sb = sel + (size_t)i * W;
+        int taken = 0;
+        for (int base = 0; base < n; base += 64) {
+            const int v = base + lane;
+            bool gt = false, eq = false;
+            if (v < n && v != i) {
+                const double x = row[v];
+                if (x == x) {
+                    const unsigned long long km = ct_knn_key(x, absolute) & mask;
+                    gt = km > prefix;
+                    eq = km == prefix;
+                }
+            }
+            const unsigned long long be = __ballot(eq);
+            const unsigned long long bm = __ballot(gt || (eq && taken + __popcll(be & below) < need));
+            if (lane == 0) {
+                sb[base >> 5] = (uint32_t)bm;
+                if ((base >> 5) + 1 < W) sb[(base >> 5) + 1] = (uint32_t)(bm >> 32);
+            }
+            taken += __popcll(be);
+        }
+    }
+    __syncthreads();                                           // sel complete and visible; the histograms are free
+    const CtKnnRule rule{sel, W, (flags & 1) != 0};
+    ct_structure(rule, n, g, work, nnz_out, iso_out, CtLds{s_t, s_deg, s_cnt, s_wave, s_red});
 }
 
 // ---------------------------------------------------------------------------------------------------- emission
@@ -351,6 +518,28 @@ extern "C" int gnm_connectome_structure(const double* fc, int S, int n, const do
     if (!fc || !thr || !work || !nnz || !iso || (reinterpret_cast<uintptr_t>(work) & 15)) return GNM_ERR_BAD_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(gnm_connectome_structure_kernel, dim3(S), dim3(kCtThreads), 0, s, fc, n, thr, work, nnz, iso);
+    GNM_CHECK_LAUNCH();
+    return GNM_OK;
+}
+
+extern "C" long long gnm_connectome_knn_scratch_words(int S, int n) {
+    if (S < 0 || n < 1 || n > kCtMaxN) return -1;
+    return (long long)S * n * ct_row_words(n);
+}
+
+// the kNN edge rule (contract above gnm_connectome_knn_kernel) into the workspace layout of gnm_connectome_structure;
+// flags: bit 0 mutual, bit 1 absolute; k >= n behaves as n - 1
+extern "C" int gnm_connectome_knn_structure(const double* fc, int S, int n, int k, int flags, uint32_t* sel,
+                                            uint32_t* work, int32_t* nnz, int32_t* iso, void* stream) {
+    if (S < 0 || n < 1 || k < 1 || (flags & ~3)) return GNM_ERR_BAD_ARG;
+    if (n > kCtMaxN) return GNM_ERR_UNSUPPORTED;
+    if (S == 0) return GNM_OK;
+    if (!fc || !sel || !work || !nnz || !iso || (reinterpret_cast<uintptr_t>(work) & 15) ||
+        (reinterpret_cast<uintptr_t>(sel) & 3))
+        return GNM_ERR_BAD_ARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(gnm_connectome_knn_kernel, dim3(S), dim3(kCtThreads), 0, s, fc, n, k, flags, sel, work, nnz,
+                       iso);
     GNM_CHECK_LAUNCH();
     return GNM_OK;
 }

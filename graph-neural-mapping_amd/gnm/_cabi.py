@@ -117,6 +117,8 @@ SIGNATURES = {
     "gnm_connectome_workspace_words": (_ll, [_i, _i]),
     "gnm_connectome_thresholds": (_i, [_p, _i, _i, _ll, _ll, C.c_double, _p, _p]),
     "gnm_connectome_structure": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
+    "gnm_connectome_knn_scratch_words": (_ll, [_i, _i]),
+    "gnm_connectome_knn_structure": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "gnm_connectome_emit": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
     "gnm_timeseries_max_nodes": (_i, []),
     "gnm_timeseries_means": (_i, [_p, _i, _p, _i, _i, _p, _p]),

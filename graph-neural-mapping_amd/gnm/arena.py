@@ -243,16 +243,21 @@ class GraphArena:
         self._dev_tables = None
         return list(range(first, len(self.n)))
 
-    # workspace of gnm_connectome_structure / _emit per call: subjects are processed in chunks that fit
+    # workspace of gnm_connectome_structure / _emit per call (with the kNN rule: plus its selection bits): subjects are
+    # processed in chunks that fit
     CONNECTOME_WORK_BYTES = 256 << 20
 
-    def add_connectivity(self, fc, sparsity, feats):
+    def add_connectivity(self, fc, sparsity, feats, *, knn=None, mutual=False, absolute=False):
         """Append the graphs of an [S, n, n] FC stack thresholded at `sparsity` percent (gnm/connectome.py: the
         reference's load_data, util.py:20-122), built on the device: thresholds, edges, node order and the CSR rows
         (csrc/connectome.hip) written straight into the arena's buffers, node features (feats: [n, F] for every
         subject or [S, n, F]) copied device to device.  The same buffers and tables as _append_host, so graphs from
-        both paths mix in one batch.  Returns the new arena ids."""
-        from .connectome import _as_fc, _thresholds_dev
+        both paths mix in one batch.  Returns the new arena ids.
+        knn=k (with sparsity None) builds k-nearest-neighbour graphs instead (gnm/connectome.py knn_edges: each row
+        selects its k largest entries, |entries| with absolute; an edge where either end selects the other, both ends
+        with mutual): no threshold launch, gnm_connectome_knn_structure in place of gnm_connectome_structure."""
+        from .connectome import _as_fc, _edge_rule, _thresholds_dev
+        sparsity, knn, flags = _edge_rule(sparsity, knn, mutual, absolute)
         fcd = _as_fc(fc, self.device)              # shapes checked first; GnmError on an arena that is not on a GPU
         S, n = int(fcd.shape[0]), int(fcd.shape[1])
         ft = feats if torch.is_tensor(feats) else torch.as_tensor(np.asarray(feats))
@@ -263,14 +268,16 @@ class GraphArena:
         if ft.dim() != 3 or tuple(ft.shape) != (S, n, F0):
             raise ValueError("node_features must be [n, %d] or [S, n, %d] with S = %d, n = %d, got %s"
                              % (F0, F0, S, n, tuple(feats.shape)))
-        thr = _thresholds_dev(fcd, sparsity)
+        thr = _thresholds_dev(fcd, sparsity) if knn is None else None
         if S == 0:
             return []
         if self.feat is None:
             self.feat = _Growable(torch.float32, self.device, width=F0)
         per = int(lib.gnm_connectome_workspace_words(1, n))
-        chunk = max(1, min(S, self.CONNECTOME_WORK_BYTES // (4 * per)))
+        per_sel = 0 if knn is None else int(lib.gnm_connectome_knn_scratch_words(1, n))
+        chunk = max(1, min(S, self.CONNECTOME_WORK_BYTES // (4 * (per + per_sel))))
         work = torch.empty(chunk * per, dtype=torch.int32, device=self.device)
+        sel = torch.empty(chunk * per_sel, dtype=torch.int32, device=self.device) if per_sel else None
         nnz = torch.empty(S, dtype=torch.int32, device=self.device)
         iso = torch.empty(S, dtype=torch.int32, device=self.device)
         first = len(self.n)
@@ -278,9 +285,14 @@ class GraphArena:
             st = torch.cuda.current_stream(self.device).cuda_stream
             for c0 in range(0, S, chunk):
                 m = min(S, c0 + chunk) - c0
-                check(lib.gnm_connectome_structure(fcd[c0].data_ptr(), m, n, thr[c0:].data_ptr(), work.data_ptr(),
-                                                   nnz[c0:].data_ptr(), iso[c0:].data_ptr(), st),
-                      "gnm_connectome_structure")
+                if knn is None:
+                    check(lib.gnm_connectome_structure(fcd[c0].data_ptr(), m, n, thr[c0:].data_ptr(), work.data_ptr(),
+                                                       nnz[c0:].data_ptr(), iso[c0:].data_ptr(), st),
+                          "gnm_connectome_structure")
+                else:
+                    check(lib.gnm_connectome_knn_structure(fcd[c0].data_ptr(), m, n, knn, flags, sel.data_ptr(),
+                                                           work.data_ptr(), nnz[c0:].data_ptr(), iso[c0:].data_ptr(),
+                                                           st), "gnm_connectome_knn_structure")
                 nh = nnz[c0:c0 + m].cpu().numpy().astype(np.int64)       # the one small download: space to reserve
                 ih = iso[c0:c0 + m].cpu().numpy()
                 rp_base = self.rowptr.reserve(m * (n + 1))

@@ -21,6 +21,14 @@ connectivity_from_timeseries):
 One graph per sliding window of the series (dynamic connectivity; the contract is written out above window_starts):
 
     graphs, windows = dynamic_graphs_from_timeseries(model_or_arena, ts, sparsity, labels, window, stride=1)
+
+k-nearest-neighbour graphs instead of a percentile threshold (every node keeps at least k neighbours; the contract is
+written out above knn_edges): the three builders and GraphArena.add_connectivity take sparsity=None with the keyword
+arguments knn=k, mutual=False, absolute=False.  knn_edges is the rule in numpy on the host, knn_adjacency the adjacency
+the device selects:
+
+    graphs = graphs_from_connectivity(model_or_arena, fc, None, node_features, labels, knn=20)
+    adj = knn_adjacency(fc, 20)                      # [S, n, n] bool, on the device
 """
 import numbers
 
@@ -37,6 +45,28 @@ def _sparsity(sparsity):
     if not 0 <= s <= 100:                     # NaN fails too
         raise ValueError("sparsity must be in [0, 100], got %r" % (sparsity,))
     return s
+
+
+def _knn(knn):
+    if isinstance(knn, (bool, np.bool_)) or not isinstance(knn, numbers.Integral):
+        raise ValueError("knn must be an int >= 1, got %r" % (knn,))
+    if int(knn) < 1:
+        raise ValueError("knn must be >= 1, got %r" % (knn,))
+    return int(knn)
+
+
+def _edge_rule(sparsity, knn, mutual=False, absolute=False):
+    """(sparsity, None, 0) for the percentile rule or (None, k, flags) for the kNN rule (flags: bit 0 mutual, bit 1
+    absolute, as gnm_connectome_knn_structure takes them): exactly one of sparsity and knn is given"""
+    if knn is None:
+        if sparsity is None:
+            raise ValueError("give sparsity (a percentile threshold) or knn (k nearest neighbours): got neither")
+        if mutual or absolute:
+            raise ValueError("mutual and absolute belong to the kNN rule: give knn, not sparsity")
+        return _sparsity(sparsity), None, 0
+    if sparsity is not None:
+        raise ValueError("give sparsity or knn, not both: with knn=%r sparsity must be None, got %r" % (knn, sparsity))
+    return None, _knn(knn), (1 if mutual else 0) | (2 if absolute else 0)
 
 
 def percentile_indexes(N, sparsity):
@@ -128,6 +158,66 @@ def order_graph(n, iu, ju):
     return edge_mat, neighbors, int(deg.max()) if n else 0
 
 
+# ---------------------------------------------------------------------------------------------------- kNN rule
+# The other edge rule of the builders (knn=k in place of sparsity): a k-nearest-neighbour graph, minimum degree >= k
+# where a percentile of the whole matrix bounds no node's degree from below.  Of one matrix fc ([n, n], float64, or
+# float32 widened first):
+#   candidates  of row i: the columns v != i with fc[i, v] not NaN.  The row is read as stored: the matrix need not be
+#               symmetric (np.corrcoef's is not, to the ulp);
+#   key         fc[i, v], or |fc[i, v]| with absolute=True;
+#   order       descending key, ascending column among equal keys; +0.0 and -0.0 are equal, +-inf ordinary values;
+#   selection   row i selects its first min(k, number of candidates) candidates in that order;
+#   edge        {u, v}, u < v: u selects v or v selects u (mutual=False), both select each other (mutual=True);
+#   graph       node order, edge_mat, neighbors, max_neighbor and arena rows exactly what the percentile path gives for
+#               the same upper-triangle edge set: order_graph(n, iu, ju) and the rows GraphArena.add builds from it;
+#               iso and nnz as there.  An all-NaN row gives an isolated node, not an error.
+# The device (csrc/connectome.hip, gnm_connectome_knn_structure) selects exactly, with no float arithmetic and no float
+# atomics: a graph's bits do not depend on the matrices it shares a call with, and two runs give the same bits.
+
+def knn_edges(fc, k, mutual=False, absolute=False):
+    """(iu, ju), iu < ju: the upper-triangle edges of the kNN graph of one [n, n] matrix, by the contract above, in
+    numpy on the host: the oracle gnm_connectome_knn_structure is tested against."""
+    k = _knn(k)
+    fc = np.asarray(fc, dtype=np.float64)
+    if fc.ndim != 2 or fc.shape[0] != fc.shape[1]:
+        raise ValueError("fc must be [n, n], got %s" % (fc.shape,))
+    n = fc.shape[0]
+    key = (np.abs(fc) if absolute else fc) + 0.0             # -0.0 + 0.0 = +0.0: one key for both zeros
+    key[np.arange(n), np.arange(n)] = np.nan                 # not a candidate, like a NaN
+    # per row: the candidates by descending key, equal keys by ascending column (stable); NaN sorts last
+    order = np.argsort(-key, axis=1, kind="stable")[:, :k]
+    taken = np.arange(order.shape[1])[None, :] < (~np.isnan(key)).sum(1)[:, None]
+    sel = np.zeros((n, n), dtype=bool)
+    sel[np.repeat(np.arange(n), taken.sum(1)), order[taken]] = True
+    A = (sel & sel.T) if mutual else (sel | sel.T)
+    return np.nonzero(np.triu(A, 1))
+
+
+def knn_adjacency(fc, k, mutual=False, absolute=False, device=None):
+    """[S, n, n] bool device tensor: the symmetric adjacency the builders use for knn=k, unpacked from the bit rows
+    gnm_connectome_knn_structure leaves in its workspace.  For inspection, and for testing the select apart from the
+    emission.  fc: [S, n, n] float64 or float32 (widened first), numpy or torch, host or device."""
+    _, k, flags = _edge_rule(None, k, mutual, absolute)
+    dev = torch.device(device) if device is not None else _default_device(fc)
+    fcd = _as_fc(fc, dev)
+    S, n = int(fcd.shape[0]), int(fcd.shape[1])
+    if S == 0:
+        return torch.zeros((0, n, n), dtype=torch.bool, device=dev)
+    per, W = int(lib.gnm_connectome_workspace_words(1, n)), (n + 31) // 32
+    work = torch.empty(S * per, dtype=torch.int32, device=dev)
+    sel = torch.empty(int(lib.gnm_connectome_knn_scratch_words(S, n)), dtype=torch.int32, device=dev)
+    nnz = torch.empty(S, dtype=torch.int32, device=dev)
+    iso = torch.empty(S, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        check(lib.gnm_connectome_knn_structure(fcd.data_ptr(), S, n, k, flags, sel.data_ptr(), work.data_ptr(),
+                                               nnz.data_ptr(), iso.data_ptr(), st), "gnm_connectome_knn_structure")
+    rows = work.view(S, per)[:, :n * W].reshape(S, n, W, 1)
+    shifts = torch.arange(32, dtype=torch.int32, device=dev)
+    up = ((rows >> shifts) & 1).reshape(S, n, W * 32)[:, :, :n].bool()       # bit v of row u: the edge {u < v}
+    return up | up.transpose(1, 2)
+
+
 class ConnectomeGraph:
     """S2VGraph-shaped (util.py:9-17) graph registered in a GraphArena by add_connectivity.  g, label and node_tags are
     plain; edge_mat, neighbors, max_neighbor and node_features are read back from the device on first access (and
@@ -202,18 +292,21 @@ class ConnectomeGraph:
         self._node_features = v
 
 
-def graphs_from_connectivity(model_or_arena, fc, sparsity, node_features, labels):
+def graphs_from_connectivity(model_or_arena, fc, sparsity, node_features, labels, *, knn=None, mutual=False,
+                             absolute=False):
     """S graphs of load_data's shape from an [S, n, n] FC stack (util.py:20-122 for one --sparsity value), registered
     in the arena (a model means model.arena()).  node_features: [n, F] shared by every subject, or [S, n, F];
-    labels: S ints.  Returns a list of ConnectomeGraph, usable wherever S2VGraph objects are."""
+    labels: S ints.  Returns a list of ConnectomeGraph, usable wherever S2VGraph objects are.
+    knn=k with sparsity None: k-nearest-neighbour graphs (the contract above knn_edges; mutual, absolute) instead of
+    the percentile threshold."""
     arena = model_or_arena.arena() if hasattr(model_or_arena, "arena") and callable(model_or_arena.arena) \
         else model_or_arena
-    _sparsity(sparsity)
+    _edge_rule(sparsity, knn, mutual, absolute)
     S = int(fc.shape[0]) if hasattr(fc, "shape") else len(fc)
     labels = [int(x) for x in (labels.tolist() if hasattr(labels, "tolist") else labels)]
     if len(labels) != S:
         raise ValueError("labels: %d values for %d matrices" % (len(labels), S))
-    gids = arena.add_connectivity(fc, sparsity, node_features)
+    gids = arena.add_connectivity(fc, sparsity, node_features, knn=knn, mutual=mutual, absolute=absolute)
     n = int(fc.shape[1])
     return [ConnectomeGraph(arena, gid, n, lab) for gid, lab in zip(gids, labels)]
 
@@ -372,14 +465,16 @@ def mean_bold_features(ts, device=None, dtype=torch.float32):
     return _ts_zscores(_ts_means(x, t_off, S, n), S, n, dtype)
 
 
-def graphs_from_timeseries(model_or_arena, ts, sparsity, labels, node_features="mean_bold"):
+def graphs_from_timeseries(model_or_arena, ts, sparsity, labels, node_features="mean_bold", *, knn=None, mutual=False,
+                           absolute=False):
     """S graphs of load_data's shape from ROI time series: the FC of connectivity_from_timeseries, kept on the device
     and passed straight to graphs_from_connectivity's builder (GraphArena.add_connectivity).  node_features:
     "mean_bold" (the loader's [n, 1] features of each subject, mean_bold_features) or an array as
-    graphs_from_connectivity takes it ([n, F] or [S, n, F]); labels: S ints."""
+    graphs_from_connectivity takes it ([n, F] or [S, n, F]); labels: S ints.  knn, mutual, absolute: the kNN rule in
+    place of sparsity, as graphs_from_connectivity takes them."""
     arena = model_or_arena.arena() if hasattr(model_or_arena, "arena") and callable(model_or_arena.arena) \
         else model_or_arena
-    _sparsity(sparsity)
+    _edge_rule(sparsity, knn, mutual, absolute)
     if isinstance(node_features, str) and node_features != "mean_bold":
         raise ValueError("node_features must be \"mean_bold\" or an array, got %r" % (node_features,))
     labels = [int(x) for x in (labels.tolist() if hasattr(labels, "tolist") else labels)]
@@ -390,7 +485,7 @@ def graphs_from_timeseries(model_or_arena, ts, sparsity, labels, node_features="
     mean = _ts_means(x, t_off, S, n)
     fc = _ts_fc(x, t_off, mean, S, n)
     feats = _ts_zscores(mean, S, n, torch.float32) if isinstance(node_features, str) else node_features
-    gids = arena.add_connectivity(fc, sparsity, feats)
+    gids = arena.add_connectivity(fc, sparsity, feats, knn=knn, mutual=mutual, absolute=absolute)
     return [ConnectomeGraph(arena, gid, n, lab) for gid, lab in zip(gids, labels)]
 
 
@@ -516,16 +611,17 @@ def dynamic_connectivity_from_timeseries(ts, window, stride=1, taper=None, devic
 
 
 def dynamic_graphs_from_timeseries(model_or_arena, ts, sparsity, labels, window, stride=1, taper=None,
-                                   node_features="mean_bold"):
+                                   node_features="mean_bold", *, knn=None, mutual=False, absolute=False):
     """(graphs, windows): one graph of load_data's shape per sliding window, registered in the arena.  graphs is a flat
     list of ConnectomeGraph, subject-major and window-minor, each with its subject's label; windows [sum W, 3] int64 holds
     (subject, window index, first row within the subject) of each.  node_features: "mean_bold" (the z-scores of the
     plain window means, whatever the taper) or an array: [n, F] for every window, or [S, n, F] per subject.  The FC never
     exists whole: windows go through means, z-scores, the fused correlation and GraphArena.add_connectivity in chunks of
-    at most DYNFC_WORK_BYTES of FC, in one buffer that is reused."""
+    at most DYNFC_WORK_BYTES of FC, in one buffer that is reused.  knn, mutual, absolute: the kNN rule in place of
+    sparsity, as graphs_from_connectivity takes them: every window's graph then has minimum degree >= k."""
     arena = model_or_arena.arena() if hasattr(model_or_arena, "arena") and callable(model_or_arena.arena) \
         else model_or_arena
-    _sparsity(sparsity)
+    _edge_rule(sparsity, knn, mutual, absolute)
     window, stride = _window_args(window, stride)
     w = _taper_arg(taper, window)
     mean_bold = isinstance(node_features, str)
@@ -562,6 +658,6 @@ def dynamic_graphs_from_timeseries(model_or_arena, ts, sparsity, labels, window,
         else:
             feats = node_features if per_subject is None else per_subject[subj[lo:hi]]
         _dyn_corr(x, w_beg[lo:hi], window, mean if w is None else None, wd, n, fc[:m])
-        gids += arena.add_connectivity(fc[:m], sparsity, feats)
+        gids += arena.add_connectivity(fc[:m], sparsity, feats, knn=knn, mutual=mutual, absolute=absolute)
     graphs = [ConnectomeGraph(arena, gid, n, labels[s]) for gid, s in zip(gids, windows[:, 0].tolist())]
     return graphs, windows

@@ -657,6 +657,14 @@ int gnm_loss_ce_bce_grad(const float* c_logit, int ldc, const long long* labels,
  * gnm_connectome_structure: edges {u < v} with fc[s, u, v] > thr[s] (dataset.py:94-100), degrees and the networkx
  *   node order of util.py:43-76, into work (gnm_connectome_workspace_words(S, n) 32-bit words, 16-byte aligned);
  *   nnz[s] = directed edge count (2 x undirected), iso[s] = 1 when a node has no neighbour.
+ * gnm_connectome_knn_structure: the same workspace from the k-nearest-neighbour rule instead of a threshold.  Row i
+ *   of fc[s] (read as stored; the matrix need not be symmetric) has as candidates the columns v != i whose entry is
+ *   not NaN, keyed by fc[s, i, v] (flags bit 1, "absolute": by |fc[s, i, v]|; +0.0 and -0.0 are one key, +-inf
+ *   ordinary values), ordered by descending key and ascending column among equal keys; it selects its first
+ *   min(k, candidates) candidates.  {u < v} is an edge when u selects v or v selects u (flags bit 0, "mutual": and).
+ *   k < 1 is GNM_ERR_BAD_ARG, k >= n behaves as n - 1.  sel: scratch for the directed selection bits,
+ *   gnm_connectome_knn_scratch_words(S, n) 32-bit words (-1 for a bad S or n).  work, nnz, iso as above; exact and
+ *   free of float arithmetic, so a graph's bits do not depend on the call it is part of.
  * gnm_connectome_emit: from work, graph s's CSR exactly as GraphArena.add builds it from util.py:97-103's edge_mat
  *   (gnm_csr_from_edge_mat, then gnm_csr_parity_order): rowptr[g_rp_off[s] ..][n + 1], col[g_col_off[s] ..][nnz[s]]. */
 int gnm_connectome_max_nodes(void);
@@ -665,6 +673,9 @@ int gnm_connectome_thresholds(const double* fc, int S, int n, long long k_lo, lo
                               void* stream);
 int gnm_connectome_structure(const double* fc, int S, int n, const double* thr, uint32_t* work, int32_t* nnz,
                              int32_t* iso, void* stream);
+long long gnm_connectome_knn_scratch_words(int S, int n);
+int gnm_connectome_knn_structure(const double* fc, int S, int n, int k, int flags, uint32_t* sel, uint32_t* work,
+                                 int32_t* nnz, int32_t* iso, void* stream);
 int gnm_connectome_emit(const uint32_t* work, int S, int n, int32_t* rowptr, uint16_t* col, const int64_t* g_rp_off,
                         const int64_t* g_col_off, void* stream);
 
