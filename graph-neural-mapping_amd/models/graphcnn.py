@@ -16,6 +16,7 @@ csrc/maxpool.hip in place of the aggregation kernels (gnm/maxnb.py builds its ne
 lists from graph.neighbors, as graphcnn.py:55-81 does); only the hipGraph replays and the
 layer-0 cache are not offered for it.
 """
+import contextlib
 import functools
 import os
 import sys
@@ -33,15 +34,21 @@ for _p in (_PKG, _HERE):
 from mlp import MLP  # noqa: E402
 from discriminator import Discriminator  # noqa: E402
 from gnm.arena import GraphArena  # noqa: E402
-from gnm.core import (DiscUnit, GinInfoMaxFn, GinSpec, class_activation_hip, disconnect_decline,  # noqa: E402
-                      disconnect_hip, edge_saliency_hip, eval_forward_fused, eval_fused_ok, integrated_gradients_hip,
-                      launch_device, lesion_decline, lesion_hip, occlusion_decline, occlusion_hip, saliency_decline,
-                      saliency_hip, saliency_maps_hip, shapley_exact_hip, shapley_hip, shapley_permutation_hip)
+from gnm.core import DiscUnit, GinInfoMaxFn, GinSpec, eval_forward_fused, eval_fused_ok, launch_device  # noqa: E402
+from gnm.attribution import (class_activation_hip, disconnect_decline, disconnect_hip, edge_saliency_hip,  # noqa: E402
+                             integrated_gradients_hip, lesion_decline, lesion_hip, occlusion_decline, occlusion_hip,
+                             saliency_decline, saliency_hip, saliency_maps_hip, shapley_exact_hip, shapley_hip,
+                             shapley_permutation_hip)
 from gnm import shapley as shapley_host  # noqa: E402
 from gnm.intgrad import quadrature  # noqa: E402
 from gnm.lesion import curve_area, default_fractions, masks_from_ranking, pair_sets  # noqa: E402
 
 __all__ = ["GIN_InfoMaxReg", "GraphCNN", "MLP", "Discriminator"]
+
+
+def _as_np(v):
+    """a tensor (detached, on the host) or anything array-like as a numpy array"""
+    return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
 
 
 def _nonfinite_graphs(batch, X):
@@ -229,6 +236,23 @@ class GIN_InfoMaxReg(nn.Module):
             pl = self._plist = (names, tensors, dict(self.named_buffers()))
         return pl
 
+    def _named_tensors(self):
+        """{name: tensor} over _param_lists()' parameters and buffers: the P the eval-mode drivers of gnm/ read"""
+        names, tensors, buffers = self._param_lists()
+        P = dict(zip(names, tensors))
+        P.update(buffers)
+        return P
+
+    @contextlib.contextmanager
+    def _eval_mode(self):
+        """eval mode (BatchNorm on its running statistics, no dropout), the previous mode restored on exit"""
+        was_training = self.training
+        self.eval()
+        try:
+            yield
+        finally:
+            self.train(was_training)
+
     def _run(self, batch, X, perm, want_disc, P0=None, hand_over=True, allow_fused=True):
         names, tensors, buffers = self._param_lists()
         if (allow_fused and not self.training and self.eval_fused and not X.requires_grad
@@ -238,8 +262,7 @@ class GIN_InfoMaxReg(nn.Module):
             # (csrc/evallayer.hip / csrc/evalfwd.hip) instead of ~20 training-kernel launches per layer.  It records
             # no autograd graph; in grad mode the outputs are attached lazily (_LazyEvalGradBatch), as the reference's
             # eval outputs carry one (main.py:54 detaches them).  Saliency (X.requires_grad) takes the path below.
-            P = dict(zip(names, tensors))
-            P.update(buffers)
+            P = self._named_tensors()
             if eval_fused_ok(self._spec, batch, X, P, self.eval_fused):
                 with torch.no_grad():
                     c_logit, d_logit, g_f = eval_forward_fused(self._spec, batch, perm, P, X, want_disc, self.eval_fused)
@@ -280,9 +303,7 @@ class GIN_InfoMaxReg(nn.Module):
         running statistics, so batching does not change a graph's result.  Returns c_logit [len(graphs), C], or
         the [len(graphs), L*H] latent array when latent=True.  Graphs of a batch must have equal node counts
         (discriminator.py:24), as in forward()."""
-        was_training = self.training
-        self.eval()
-        try:
+        with self._eval_mode():
             out = []
             for i in range(0, len(graphs), batch_size):
                 chunk = graphs[i:i + batch_size]
@@ -291,8 +312,6 @@ class GIN_InfoMaxReg(nn.Module):
             if latent:
                 return np.concatenate(out, 0) if out else np.zeros((0, 0), dtype=np.float32)
             return torch.cat(out, 0) if out else torch.zeros((0, 0), device=self.eps.device)
-        finally:
-            self.train(was_training)
 
     def saliency(self, graphs, cls, batch_size=256):
         """Input saliency of many graphs in batches: what main.py:60-68 builds from one compute_saliency([g], c) call
@@ -314,8 +333,8 @@ class GIN_InfoMaxReg(nn.Module):
         "autograd" entry), so its NaN / inf pattern is compute_saliency's."""
         F0 = self.mlps[0].linear.in_features if self.num_mlp_layers == 1 else self.mlps[0].linears[0].in_features
         routes = []
-        out = self._interpret("saliency", graphs, cls, batch_size, (F0,), functools.partial(self._saliency_batch,
-                                                                                          routes=routes))
+        out = self._interpret(graphs, *self._interpret_args("saliency", graphs, cls, batch_size), batch_size, (F0,),
+                              functools.partial(self._saliency_batch, routes=routes))
         self.saliency_routes = routes
         return out
 
@@ -336,20 +355,15 @@ class GIN_InfoMaxReg(nn.Module):
             raise ValueError("%s: batch_size must be positive" % name)
         return single, classes
 
-    def _interpret(self, name, graphs, cls, batch_size, tail, run_batch, square=False):
-        """The batching saliency(), class_activation() and edge_saliency() share (`name`, which prefixes the errors):
-        the argument checks, eval mode with the previous mode restored on exit, chunks of batch_size graphs, and the
+    def _interpret(self, graphs, single, classes, batch_size, tail, run_batch, square=False):
+        """The batching saliency(), class_activation() and edge_saliency() share, after _interpret_args (which gives
+        `single` and `classes`): eval mode with the previous mode restored on exit, chunks of batch_size graphs, and the
         result layout.  run_batch(chunk, batch, P, classes, dst) returns one batch's [len(classes), N, *tail] result
         (or a list of per-class [N, *tail] tensors), written into dst when that is given: the batch's view of the dense
         [len(classes), len(graphs), n, *tail] result.  Graphs of different node counts get per-graph lists instead;
         square: an [n, n] map per graph (tail (n,), each graph's map cropped to its n_g columns)."""
-        single, classes = self._interpret_args(name, graphs, cls, batch_size)
-        was_training = self.training
-        self.eval()
-        try:
-            names, tensors, buffers = self._param_lists()
-            P = dict(zip(names, tensors))
-            P.update(buffers)
+        with self._eval_mode():
+            P = self._named_tensors()
             ns = [len(g.g) for g in graphs]
             ragged = any(k != ns[0] for k in ns)
             if square:
@@ -371,8 +385,6 @@ class GIN_InfoMaxReg(nn.Module):
             if full is not None:
                 return full[0] if single else full
             return per_graph[0] if single else per_graph
-        finally:
-            self.train(was_training)
 
     def _saliency_batch(self, chunk, batch, P, classes, dst, routes):
         """saliency() of one batch: a list of [N, F0] tensors (written into dst when given), one per class"""
@@ -448,7 +460,7 @@ class GIN_InfoMaxReg(nn.Module):
         buffer or numpy RNG state is touched, and the train / eval mode is restored on exit."""
         if kind not in self.CAM_KINDS:
             raise ValueError("class_activation: kind must be one of %s, not %r" % (self.CAM_KINDS, kind))
-        return self._interpret("class_activation", graphs, cls, batch_size, (),
+        return self._interpret(graphs, *self._interpret_args("class_activation", graphs, cls, batch_size), batch_size, (),
                                functools.partial(self._cam_batch, kind=kind))
 
     def _cam_batch(self, chunk, batch, P, classes, dst, kind):
@@ -484,7 +496,8 @@ class GIN_InfoMaxReg(nn.Module):
         node counts a list of [n_g, n_g] tensors (a list of such lists for a sequence `cls`).  The output is n^2 per
         graph and class, hence the smaller default batch.  No parameter .grad, BatchNorm buffer or numpy RNG state is
         touched, and the train / eval mode is restored on exit."""
-        return self._interpret("edge_saliency", graphs, cls, batch_size, (), self._edge_saliency_batch, square=True)
+        return self._interpret(graphs, *self._interpret_args("edge_saliency", graphs, cls, batch_size), batch_size, (),
+                               self._edge_saliency_batch, square=True)
 
     def _edge_saliency_batch(self, chunk, batch, P, classes, dst):
         """edge_saliency() of one batch: [len(classes), N, n_max] (dst when given)"""
@@ -528,16 +541,16 @@ class GIN_InfoMaxReg(nn.Module):
 
         The n deleted copies of an n-node graph need 2 n^2 hidden_dim floats of scratch: the default batch_size keeps a
         batch of 400-node graphs at hidden_dim 128 under 2 GiB (8 x 0.16 GiB + the readout shares), and a larger batch
-        is run in chunks under that budget (gnm/core.py OCCLUSION_SCRATCH_BYTES).  The result is bitwise the same run to
-        run and for any batch_size.  No parameter .grad, BatchNorm buffer or numpy RNG state is touched, and the
+        is run in chunks under that budget (gnm/attribution.py OCCLUSION_SCRATCH_BYTES).  The result is bitwise the same
+        run to run and for any batch_size.  No parameter .grad, BatchNorm buffer or numpy RNG state is touched, and the
         train / eval mode is restored on exit."""
         for g in graphs:
             if len(g.g) < 2:
                 raise ValueError("occlusion: a graph of fewer than 2 nodes has no node-deleted copy")
         bases = []
-        occ = self._interpret("occlusion", graphs, cls, batch_size, (),
+        single, classes = self._interpret_args("occlusion", graphs, cls, batch_size)
+        occ = self._interpret(graphs, single, classes, batch_size, (),
                               functools.partial(self._occlusion_batch, bases=bases))
-        single = isinstance(cls, (int, np.integer))
         base = torch.cat(bases, 1)                          # [len(classes), len(graphs)]
         if single:
             base = base[0]
@@ -601,7 +614,7 @@ class GIN_InfoMaxReg(nn.Module):
 
         The result is bitwise the same run to run, for any batch_size and whatever other sets share the call (no
         atomics, fixed summation orders, one virtual graph per workgroup column).  A virtual graph needs 2 n
-        hidden_dim floats of scratch; the virtual graphs of a batch run in chunks under gnm/core.py
+        hidden_dim floats of scratch; the virtual graphs of a batch run in chunks under gnm/attribution.py
         LESION_SCRATCH_BYTES.  No parameter .grad, BatchNorm buffer or numpy RNG state is touched, and the
         train / eval mode is restored on exit."""
         single, classes = self._interpret_args("lesion", graphs, cls, batch_size)
@@ -615,20 +628,14 @@ class GIN_InfoMaxReg(nn.Module):
         on exit, chunks of batch_size graphs -- run_batch(chunk, batch, P, i0) returns (base [len(classes), B], scores
         [len(classes), sum of S_g over the chunk]) of the chunk that starts at graph i0 -- then delta = base - scores
         as a [.., len(graphs), S] tensor when every graph has S = counts[g] sets and as per-graph lists otherwise."""
-        was_training = self.training
-        self.eval()
-        try:
-            names, tensors, buffers = self._param_lists()
-            P = dict(zip(names, tensors))
-            P.update(buffers)
+        with self._eval_mode():
+            P = self._named_tensors()
             bases, parts = [], []
             for i0 in range(0, len(graphs), batch_size):
                 chunk = graphs[i0:i0 + batch_size]
                 base, les = run_batch(chunk, self._batch_of(chunk), P, i0)
                 bases.append(base)
                 parts.append(les)
-        finally:
-            self.train(was_training)
         base = torch.cat(bases, 1)                          # [len(classes), len(graphs)]
         flat = torch.cat(parts, 1)                          # [len(classes), sum of S_g]
         if all(k == counts[0] for k in counts):
@@ -650,11 +657,18 @@ class GIN_InfoMaxReg(nn.Module):
             isinstance(rois, (list, tuple)) and len(rois) > 0 and np.ndim(rois[0]) == 1 and not torch.is_tensor(rois[0]))
 
     @staticmethod
+    def _shared_labels(labels):
+        """whether `labels` is ONE [n] labelling for all graphs (an array, a tensor or a flat sequence), not a per-graph
+        list"""
+        return torch.is_tensor(labels) or isinstance(labels, np.ndarray) or (
+            isinstance(labels, (list, tuple)) and len(labels) > 0 and np.ndim(labels[0]) == 0)
+
+    @staticmethod
     def _lesion_sets(graphs, rois, method="lesion", name="rois", proper=True):
         """lesion()'s `rois` (disconnect()'s `a` / `b`: `method`, `name`) as one bool [S_g, n_g] array per graph,
         checked; proper: a set must leave a node of its graph (a lesion; a cut may name every node)"""
         def as_mask(a, what):
-            a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+            a = _as_np(a)
             if a.ndim != 2:
                 raise ValueError("%s: %s must be a 2-D [sets, nodes] array, got shape %s" % (method, what, list(a.shape)))
             if a.dtype != np.bool_:
@@ -786,9 +800,9 @@ class GIN_InfoMaxReg(nn.Module):
         and no other entry is.  A mask of the wrong width or with an entry other than 0 / 1, a and b of different
         shapes and a shared mask over graphs of different node counts raise ValueError.
 
-        The result is bitwise the same run to run, for any batch_size, any chunking (gnm/core.py LESION_SCRATCH_BYTES)
-        and whatever other pairs share the call.  No parameter .grad, BatchNorm buffer or numpy RNG state is touched,
-        and the train / eval mode is restored on exit."""
+        The result is bitwise the same run to run, for any batch_size, any chunking (gnm/attribution.py
+        LESION_SCRATCH_BYTES) and whatever other pairs share the call.  No parameter .grad, BatchNorm buffer or numpy
+        RNG state is touched, and the train / eval mode is restored on exit."""
         single, classes = self._interpret_args("disconnect", graphs, cls, batch_size)
         sa = self._lesion_sets(graphs, a, "disconnect", "a", proper=False)
         if b is None:
@@ -826,10 +840,8 @@ class GIN_InfoMaxReg(nn.Module):
         return_scores=True returns (delta, base, scores), scores laid out as delta -- bitwise disconnect()'s values
         for those pairs.  A network without nodes in a graph gives an empty cut.  Otherwise as disconnect()."""
         self._interpret_args("disconnection_matrix", graphs, cls, batch_size)
-        as_np = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)     # noqa: E731
-        shared = torch.is_tensor(labels) or isinstance(labels, np.ndarray) or (
-            isinstance(labels, (list, tuple)) and len(labels) > 0 and np.ndim(labels[0]) == 0)
-        per = [as_np(labels)] if shared else [as_np(v) for v in labels]
+        shared = self._shared_labels(labels)
+        per = [_as_np(labels)] if shared else [_as_np(v) for v in labels]
         if not shared and len(per) != len(graphs):
             raise ValueError("disconnection_matrix: %d label vectors for %d graphs" % (len(per), len(graphs)))
         for v in per:
@@ -893,9 +905,9 @@ class GIN_InfoMaxReg(nn.Module):
         gnm_coalition_pack writes lesion()'s keep masks on the device), the forward is lesion()'s kernels unchanged, and
         the scores are combined on the device in fp64 from the fp32 scores -- differences first, fixed summation
         orders, no atomics (gnm_shapley_exact / gnm_shapley_permutation; gnm/shapley.py restates them in numpy).  The
-        results are bitwise the same run to run, for any batch_size, any chunking (gnm/core.py LESION_SCRATCH_BYTES)
-        and any set of classes.  A group with no node in a graph has phi exactly 0.0 there (and a zero inter row)
-        wherever the graph's scores are finite.
+        results are bitwise the same run to run, for any batch_size, any chunking (gnm/attribution.py
+        LESION_SCRATCH_BYTES) and any set of classes.  A group with no node in a graph has phi exactly 0.0 there (and a
+        zero inter row) wherever the graph's scores are finite.
 
         NaN: every coalition enters every player's sum, so ONE NaN coalition score makes that graph's phi and inter
         NaN for that class (and no other graph's).  Under neighbour "average" with learned eps this is common: any
@@ -910,17 +922,15 @@ class GIN_InfoMaxReg(nn.Module):
         single, classes = self._interpret_args("shapley", graphs, cls, batch_size)
         if method not in ("exact", "permutation"):
             raise ValueError("shapley: method must be 'exact' or 'permutation', not %r" % (method,))
-        as_np = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)     # noqa: E731
         ns = [len(g.g) for g in graphs]
-        shared = torch.is_tensor(labels) or isinstance(labels, np.ndarray) or (
-            isinstance(labels, (list, tuple)) and len(labels) > 0 and np.ndim(labels[0]) == 0)
+        shared = self._shared_labels(labels)
         if shared and any(k != ns[0] for k in ns):
             raise ValueError("shapley: a shared [n] labelling needs graphs of one node count")
         if not shared and (not isinstance(labels, (list, tuple)) or len(labels) != len(graphs)):
             raise ValueError("shapley: labels must be one [n] vector or a list of one [n_g] vector per graph")
         try:
-            per = [shapley_host.check_labels(as_np(labels), ns[0])] * len(graphs) if shared else \
-                [shapley_host.check_labels(as_np(v), n) for v, n in zip(labels, ns)]
+            per = [shapley_host.check_labels(_as_np(labels), ns[0])] * len(graphs) if shared else \
+                [shapley_host.check_labels(_as_np(v), n) for v, n in zip(labels, ns)]
         except ValueError as e:
             raise ValueError("shapley: %s" % e) from None
         K = max([int(v.max()) + 1 for v in per if v.size] + [0])
@@ -944,7 +954,7 @@ class GIN_InfoMaxReg(nn.Module):
                 if isinstance(permutations, (int, np.integer)):
                     perms = shapley_host.draw_permutations(int(permutations), K, seed)
                 else:
-                    perms = shapley_host.check_permutations(as_np(permutations), K)
+                    perms = shapley_host.check_permutations(_as_np(permutations), K)
             except ValueError as e:
                 raise ValueError("shapley: %s" % e) from None
             ranks, M = shapley_host.ranks_of(perms), perms.shape[0]
@@ -1014,10 +1024,10 @@ class GIN_InfoMaxReg(nn.Module):
 
         The K virtual copies of a batch hold (m L + L + 3) K N hidden_dim floats on the device (0.47 GB at K = 32 for 8
         graphs of 400 nodes, hidden_dim 64, 5 layers of 2 Linears), hence the small default batch; a larger batch is run
-        in chunks of whole graphs under gnm/core.py INTGRAD_SCRATCH_BYTES.  The result is bitwise the same run to run
-        (no atomics, fixed summation orders); it may differ in the last bits between batch sizes, because the forward
-        chooses its aggregation kernel per batch.  No parameter .grad, BatchNorm buffer or numpy RNG state is touched,
-        and the train / eval mode is restored on exit."""
+        in chunks of whole graphs under gnm/attribution.py INTGRAD_SCRATCH_BYTES.  The result is bitwise the same run to
+        run (no atomics, fixed summation orders); it may differ in the last bits between batch sizes, because the
+        forward chooses its aggregation kernel per batch.  No parameter .grad, BatchNorm buffer or numpy RNG state is
+        touched, and the train / eval mode is restored on exit."""
         alphas, weights = quadrature(method, steps)
         F0 = self.mlps[0].linear.in_features if self.num_mlp_layers == 1 else self.mlps[0].linears[0].in_features
         if baseline is not None and len(graphs):
@@ -1033,12 +1043,12 @@ class GIN_InfoMaxReg(nn.Module):
             if not bool(torch.isfinite(baseline).all()):
                 raise ValueError("integrated_gradients: the baseline has a non-finite entry")
         scores = [] if return_scores else None
-        attr = self._interpret("integrated_gradients", graphs, cls, batch_size, (F0,), functools.partial(
+        single, classes = self._interpret_args("integrated_gradients", graphs, cls, batch_size)
+        attr = self._interpret(graphs, single, classes, batch_size, (F0,), functools.partial(
             self._intgrad_batch, alphas=alphas, weights=weights, baseline=baseline, scores=scores))
         if not return_scores:
             return attr
-        single = isinstance(cls, (int, np.integer))
-        base = torch.cat([s[0] for s in scores], 1)         # [len(classes), len(graphs)]
+        base =torch.cat([s[0] for s in scores], 1)         # [len(classes), len(graphs)]
         base0 = torch.cat([s[1] for s in scores], 1)
         if torch.is_tensor(attr):
             total = attr.sum((-2, -1))

@@ -222,7 +222,7 @@ def one_node_sets(n):
 
 
 def ig_declined(case, graph):
-    """the condition integrated_gradients() declines on these graphs (core.saliency_decline): neighbour average with
+    """the condition integrated_gradients() declines on these graphs (attribution.saliency_decline): neighbour average with
     learned eps and a node without neighbours -- an empty row of edge_mat[0]"""
     if not (case.npool == "average" and case.eps):
         return False

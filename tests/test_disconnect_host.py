@@ -391,7 +391,7 @@ def test_row_mask_identity_with_an_explicit_self_edge():
 
 # ---------------------------------------------------------------------------------------------- the C ABI
 def test_disconnect_entries_declared_bound_and_exported():
-    from gnm import _build, _cabi, core
+    from gnm import _build, _cabi, attribution
     header = open(os.path.join(ROOT, "include", "gnm_hip.h")).read()
     declared = set(re.findall(r"\b(gnm_[a-z0-9_]+)\s*\(", header))
     for name in NEW:
@@ -403,7 +403,7 @@ def test_disconnect_entries_declared_bound_and_exported():
     assert f(840 * 400, 840, 400, 64, 5) == 2 * 840 * 400 * 64 + 5 * 840 * 13 * 64
     for args in ((33, 1, 33, 32, 1), (160 * 400, 160, 400, 64, 5), (-1, 1, 1, 1, 1), (1, 1, 1, 1, -1)):
         assert f(*args) == _cabi.lib.gnm_lesion_scratch_floats(*args)
-    assert core.disconnect_decline is core.lesion_decline
+    assert attribution.disconnect_decline is attribution.lesion_decline
 
 
 def test_disconnect_kernels_in_the_code_object(tmp_path):

@@ -258,7 +258,7 @@ def test_ragged_batch_is_bitwise_each_graph_alone():
 
 
 def test_determinism_batch_size_chunks_and_other_pairs(monkeypatch):
-    from gnm import core
+    from gnm import attribution, core
     from gnm._cabi import lib
     from rowblock_midrange_cases import chunk_graphs
     model = model_of(3, 2, 7, 64, True, "average", "average", seed=2)
@@ -280,7 +280,7 @@ def test_determinism_batch_size_chunks_and_other_pairs(monkeypatch):
     calls = []
     real = lib.gnm_disconnect
     monkeypatch.setattr(core.lib, "gnm_disconnect", lambda *x: calls.append(1) or real(*x), raising=False)
-    monkeypatch.setattr(core, "LESION_SCRATCH_BYTES", 4 * int(lib.gnm_disconnect_scratch_floats(7 * 257, 7, 257, 64, 3)))
+    monkeypatch.setattr(attribution, "LESION_SCRATCH_BYTES", 4 * int(lib.gnm_disconnect_scratch_floats(7 * 257, 7, 257, 64, 3)))
     d, bb, s = model.disconnect(gs, (0, 1), a, b, batch_size=8, return_scores=True)        # 30 virtual graphs, 7 to a chunk
     assert len(calls) == 5
     assert torch.equal(nn7(d), nn7(d0)) and torch.equal(bb, b0) and torch.equal(nn7(s), nn7(s0))

@@ -120,7 +120,7 @@ def test_32_steps_asymmetric_and_ragged():
 def test_one_step_at_the_input_is_saliency_times_x(npool, gpool, le):
     """the driver with alphas = [1], weights = [1] and a zero baseline against gnm_saliency: saliency_hip(X) * X.  Not
     bitwise: layer 0 takes another route (alpha P + b instead of the Linear of the aggregate)."""
-    from gnm.core import integrated_gradients_hip, saliency_hip
+    from gnm.attribution import integrated_gradients_hip, saliency_hip
     model = model_of(3, 2, 7, 64, le, gpool, npool, seed=3).eval()
     gs = [random_graph(220 + j, 40, 0.2, 7) for j in range(2)]
     batch = model._batch_of(gs)
@@ -201,7 +201,7 @@ def test_400_node_dense(tag, one_hot, npool, gpool, learn_eps):
 
 # ---------------------------------------------------------------------------------------------- behaviour
 def test_classes_determinism_and_batch_size(monkeypatch):
-    from gnm import core
+    from gnm import attribution
     model = model_of(3, 2, 7, 64, True, "average", "average", seed=2)
     gs = [random_graph(240 + j, 40, 0.2, 7) for j in range(3)]
     base = baseline_of(40, 7)
@@ -216,10 +216,10 @@ def test_classes_determinism_and_batch_size(monkeypatch):
     scale = float(a0.abs().max())
     assert float((a1 - a3).abs().max()) <= RTOL * scale
     # the driver's chunks: room for two graphs' arrays -> chunks of 2 and 1 graphs, never a part of one graph's steps
-    monkeypatch.setattr(core, "INTGRAD_SCRATCH_BYTES", 4 * core._intgrad_floats(80, 64, 3, 2, 5))
+    monkeypatch.setattr(attribution, "INTGRAD_SCRATCH_BYTES", 4 * attribution._intgrad_floats(80, 64, 3, 2, 5))
     ac = model.integrated_gradients(gs, (0, 1), steps=5, baseline=base)
     assert float((ac - a0).abs().max()) <= RTOL * scale
-    monkeypatch.setattr(core, "INTGRAD_SCRATCH_BYTES", 1)
+    monkeypatch.setattr(attribution, "INTGRAD_SCRATCH_BYTES", 1)
     ac = model.integrated_gradients(gs, (0, 1), steps=5, baseline=base)                             # one graph a chunk
     assert float((ac - a0).abs().max()) <= RTOL * scale
 

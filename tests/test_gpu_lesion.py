@@ -200,7 +200,7 @@ def test_ragged_batches_and_result_shapes():
 
 # ---------------------------------------------------------------------------------------------- behaviour
 def test_determinism_batch_size_chunks_and_other_sets(monkeypatch):
-    from gnm import core
+    from gnm import attribution, core
     from gnm._cabi import lib
     model = model_of(3, 2, 7, 64, True, "average", "average", seed=2)
     gs = [random_graph(20 + i, 40, 0.2, 7) for i in range(5)]
@@ -220,7 +220,7 @@ def test_determinism_batch_size_chunks_and_other_sets(monkeypatch):
     calls = []
     real = lib.gnm_lesion
     monkeypatch.setattr(core.lib, "gnm_lesion", lambda *a: calls.append(1) or real(*a), raising=False)
-    monkeypatch.setattr(core, "LESION_SCRATCH_BYTES", 4 * int(lib.gnm_lesion_scratch_floats(7 * 40, 7, 40, 64, 3)))
+    monkeypatch.setattr(attribution, "LESION_SCRATCH_BYTES", 4 * int(lib.gnm_lesion_scratch_floats(7 * 40, 7, 40, 64, 3)))
     d, b, o = model.lesion(gs, (0, 1), sets, batch_size=8, return_scores=True)       # 30 virtual graphs, 7 to a chunk
     assert len(calls) == 5
     assert torch.equal(d, d0) and torch.equal(b, b0) and torch.equal(o, l0)

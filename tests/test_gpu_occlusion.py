@@ -162,7 +162,7 @@ def test_400_node_dense(tag, one_hot, npool, gpool, learn_eps):
 
 # ---------------------------------------------------------------------------------------------- behaviour
 def test_batch_size_invariance_and_determinism(monkeypatch):
-    from gnm import core
+    from gnm import attribution
     model = model_of(3, 2, 7, 64, True, "average", "average", seed=2)
     gs = [random_graph(20 + i, 40, 0.2, 7) for i in range(5)]
     d0, b0, o0 = model.occlusion(gs, (0, 1), return_scores=True)
@@ -171,7 +171,7 @@ def test_batch_size_invariance_and_determinism(monkeypatch):
         d, b, o = model.occlusion(gs, (0, 1), batch_size=bs, return_scores=True)
         assert torch.equal(d, d0) and torch.equal(b, b0) and torch.equal(o, o0), bs      # (256 again: run to run)
     from gnm._cabi import lib
-    monkeypatch.setattr(core, "OCCLUSION_SCRATCH_BYTES", 4 * int(lib.gnm_occlusion_scratch_floats(2 * 1600, 80, 40, 64, 3)))
+    monkeypatch.setattr(attribution, "OCCLUSION_SCRATCH_BYTES", 4 * int(lib.gnm_occlusion_scratch_floats(2 * 1600, 80, 40, 64, 3)))
     #                                                             (the scratch of two graphs: chunks of 2, 2 and 1)
     d, b, o = model.occlusion(gs, (0, 1), batch_size=256, return_scores=True)
     assert torch.equal(d, d0) and torch.equal(b, b0) and torch.equal(o, o0)

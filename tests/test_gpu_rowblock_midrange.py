@@ -171,7 +171,7 @@ def test_ragged_batch_across_the_word_group_boundary():
 def test_chunks_and_batch_sizes_at_eight_half_row_words(monkeypatch):
     """n = 257, 5 graphs x 6 sets: the scratch budgets lowered until lesion() runs in 5 chunks and occlusion() in 3 --
     bitwise the unchunked result, as is every batch size"""
-    from gnm import core
+    from gnm import attribution, core
     from gnm._cabi import lib
     model, gs, sets = model_for(T.CHUNK_CASE), T.chunk_graphs(), T.chunk_sets()
     d0, b0, l0 = model.lesion(gs, (0, 1), sets, return_scores=True)
@@ -195,8 +195,8 @@ def test_chunks_and_batch_sizes_at_eight_half_row_words(monkeypatch):
 
     monkeypatch.setattr(core.lib, "gnm_lesion", counted("gnm_lesion"), raising=False)
     monkeypatch.setattr(core.lib, "gnm_occlusion", counted("gnm_occlusion"), raising=False)
-    monkeypatch.setattr(core, "LESION_SCRATCH_BYTES", 4 * int(lib.gnm_lesion_scratch_floats(7 * 257, 7, 257, 64, 3)))
-    monkeypatch.setattr(core, "OCCLUSION_SCRATCH_BYTES",
+    monkeypatch.setattr(attribution, "LESION_SCRATCH_BYTES", 4 * int(lib.gnm_lesion_scratch_floats(7 * 257, 7, 257, 64, 3)))
+    monkeypatch.setattr(attribution, "OCCLUSION_SCRATCH_BYTES",
                         4 * int(lib.gnm_occlusion_scratch_floats(2 * 257 * 257, 2 * 257, 257, 64, 3)))
     d, b, o = model.lesion(gs, (0, 1), sets, batch_size=8, return_scores=True)     # 30 virtual graphs, 7 to a chunk
     assert calls["gnm_lesion"] == 5

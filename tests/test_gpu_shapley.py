@@ -225,7 +225,7 @@ def test_against_the_fp64_oracle_400_nodes():
 def test_device_reduction_on_the_two_additive_game(K):
     """the kernels alone, no forward: [2 classes, 3 graphs] of 2-additive games with known phi and inter; K = 16
     exercises the bit-insert indexing at the cap"""
-    from gnm.core import shapley_exact_hip
+    from gnm.attribution import shapley_exact_hip
     from gnm.shapley import interactions_from_values, shapley_from_values
     games = [two_additive(K, 100 + s) for s in range(6)]
     v = np.stack([gm[0] for gm in games]).reshape(2, 3, 1 << K)
@@ -276,6 +276,41 @@ def test_axioms_efficiency_null_player_and_the_empty_coalition():
     _, _, les = model.lesion([gs[0], gs[2]], (0, 1), [coalition_removed(labs[0], [0]), coalition_removed(labs[2], [0])],
                              return_scores=True)
     assert torch.equal(values[:, [0, 2], 0], les[:, :, 0])
+
+
+def test_a_call_of_empty_coalitions_launches_nothing_and_a_mixed_call_scores_the_rest_alike(monkeypatch):
+    """shapley_hip on coalitions that keep no node (every node labelled, no background).  Only such coalitions in the
+    call: every score is the bias sum, bitwise, and neither the pack nor gnm_lesion runs.  Some of them among others:
+    they get the bias sum, and the others the bits of a call that holds those others alone."""
+    from gnm import attribution, core
+    from gnm._cabi import lib
+    K = 3
+    model = model_of(1, 1, 7, 32, True, "sum", "sum", seed=61)
+    gs = [random_graph(91 + i, 6, 0.4, 7) for i in range(2)]
+    batch = model._batch_of(gs)
+    X = batch.arena.features(batch).detach()
+    P = model._named_tensors()
+    labels = np.stack([np.arange(6) % K] * 2)
+    calls = []
+    for entry in ("gnm_lesion", "gnm_coalition_pack"):
+        real = getattr(lib, entry)
+        monkeypatch.setattr(core.lib, entry, lambda *a, real=real, entry=entry: calls.append(entry) or real(*a),
+                            raising=False)
+    want = torch.as_tensor(bias_sum(model, (0, 1)), device=DEV)
+
+    def score(vgraph, ids):
+        return attribution.shapley_hip(model._spec, batch, X, P, (0, 1), labels, np.asarray(vgraph), np.asarray(ids), K)
+    out = score([0, 0, 1, 1], [0, 0, 0, 0])
+    assert out.shape == (2, 4) and torch.equal(out, want[:, None].expand(2, 4))
+    assert calls == []
+    vgraph, ids = np.array([0, 0, 0, 1, 1, 1]), np.array([0, 0b011, 0b111, 0, 0b100, 0])
+    mixed = score(vgraph, ids)
+    assert calls == ["gnm_coalition_pack", "gnm_lesion"]
+    run = ids != 0
+    alone = score(vgraph[run], ids[run])
+    assert torch.isfinite(alone).all() and torch.equal(mixed[:, torch.as_tensor(run, device=DEV)], alone)
+    assert torch.equal(mixed[:, torch.as_tensor(~run, device=DEV)], want[:, None].expand(2, 3))
+    assert calls == ["gnm_coalition_pack", "gnm_lesion"] * 2
 
 
 # ---------------------------------------------------------------------------------------------- 6. permutation mode
@@ -335,7 +370,7 @@ def test_per_roi_players_sampled():
 
 # ---------------------------------------------------------------------------------------------- 7. determinism
 def test_determinism_batch_size_chunks_and_classes(monkeypatch):
-    from gnm import core
+    from gnm import attribution, core
     from gnm._cabi import lib
     K = 6
     model = model_of(3, 2, 7, 64, True, "average", "average", seed=2, C=11)
@@ -353,7 +388,7 @@ def test_determinism_batch_size_chunks_and_classes(monkeypatch):
     calls = []
     real = lib.gnm_lesion
     monkeypatch.setattr(core.lib, "gnm_lesion", lambda *a: calls.append(1) or real(*a), raising=False)
-    monkeypatch.setattr(core, "LESION_SCRATCH_BYTES", 4 * int(lib.gnm_lesion_scratch_floats(7 * 257, 7, 257, 64, 3)))
+    monkeypatch.setattr(attribution, "LESION_SCRATCH_BYTES", 4 * int(lib.gnm_lesion_scratch_floats(7 * 257, 7, 257, 64, 3)))
     p, i, v = model.shapley(gs[:1], cls, labs[:1], interactions=True, return_scores=True)      # 64 coalitions, 7 to a chunk
     assert len(calls) == 10
     assert torch.equal(p, p0[:, :1]) and torch.equal(i, i0[:, :1]) and torch.equal(v, v0[:, :1])

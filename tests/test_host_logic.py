@@ -582,9 +582,9 @@ def test_linear_backward_routing_table(monkeypatch, K, H, pro, below, need_dA):
     ([4], 0), ([], 100),
 ])
 def test_runs_within_against_brute_force(sizes, budget):
-    """core._runs_within (the chunking of occlusion_hip, lesion_hip and integrated_gradients_hip): in order, no run
+    """attribution._runs_within (the chunking of occlusion_hip, lesion_hip and integrated_gradients_hip): in order, no run
     empty, each run the longest that fits -- against the definition, tried run by run"""
-    from gnm import core
+    from gnm import attribution
     asked = []
 
     def floats_of(i0, i1):
@@ -600,8 +600,29 @@ def test_runs_within_against_brute_force(sizes, budget):
             i1 += 1
         want.append((i0, i1))
         i0 = i1
-    assert list(core._runs_within(len(sizes), floats_of, budget)) == want
+    assert list(attribution._runs_within(len(sizes), floats_of, budget)) == want
     assert [i for a, b in want for i in range(a, b)] == list(range(len(sizes)))     # every item once, in order
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_runs_under_is_runs_within_on_a_prefix_array(seed):
+    """attribution._runs_under (shapley_hip's chunking) against its docstring: _runs_within for the cost
+    f[i1] - f[i0] of a non-decreasing prefix array f.  _runs_under's budget is in floats, _runs_within's in bytes.
+    Budgets from below the smallest item (every item alone, most of them over the budget) to the whole array in one run,
+    the exact boundaries f[j] - f[i] and their neighbours among them; zero-cost items and an empty array too."""
+    from gnm import attribution
+    rng = np.random.default_rng(seed)
+    count = int(rng.integers(0, 40))
+    steps = rng.integers(0 if seed % 2 else 1, 50, count)   # (odd seeds: items of cost 0, f not strictly increasing)
+    if count:
+        steps[int(rng.integers(0, count))] = 400            # one item far above most budgets below
+    f = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
+    edges = {int(f[j] - f[i]) for i in range(count + 1) for j in range(i, count + 1)}
+    budgets = {0, 1, 49, 399, 400, 401, int(f[-1]), int(f[-1]) + 1} | {e + d for e in list(edges)[:60] for d in (-1, 0, 1)}
+    for budget in sorted(b for b in budgets if b >= 0):
+        want = list(attribution._runs_within(len(f) - 1, lambda a, b: int(f[b] - f[a]), 4 * budget))
+        assert list(attribution._runs_under(f, budget)) == want, (seed, budget)
+        assert [i for a, b in want for i in range(a, b)] == list(range(count))
 
 
 def test_gradient_collector():

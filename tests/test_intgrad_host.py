@@ -257,9 +257,9 @@ def test_intgrad_entries_declared_bound_and_exported():
     assert (_cabi.lib.gnm_integrated_gradients_scratch_floats(3200, 64, 32)
             == _cabi.lib.gnm_saliency_scratch_floats(32 * 3200, 64) + 2 * 3200 * 64)
     # the documented default (8 graphs of 400 nodes, K = 32, H = 64, m = 2, L = 5) is one chunk of the driver
-    from gnm import core
-    assert 4 * core._intgrad_floats(3200, 64, 5, 2, 32) < core.INTGRAD_SCRATCH_BYTES
-    assert core._intgrad_floats(3200, 64, 5, 2, 32) >= 2 * 5 * 32 * 3200 * 64        # the forward's z arrays count
+    from gnm import attribution
+    assert 4 * attribution._intgrad_floats(3200, 64, 5, 2, 32) < attribution.INTGRAD_SCRATCH_BYTES
+    assert attribution._intgrad_floats(3200, 64, 5, 2, 32) >= 2 * 5 * 32 * 3200 * 64        # the forward's z arrays count
 
 
 def test_intgrad_kernels_in_the_code_object(tmp_path):

@@ -333,8 +333,8 @@ def test_lesion_entries_declared_bound_and_exported():
     assert f(33, 1, 33, 32, 1) == 2 * 33 * 32 + 2 * 32
     for bad in ((-1, 1, 1, 1, 1), (1, -1, 1, 1, 1), (1, 1, -1, 1, 1), (1, 1, 1, -1, 1), (1, 1, 1, 1, -1)):
         assert f(*bad) == 0
-    from gnm import core
-    assert core.LESION_SCRATCH_BYTES == 2 << 30
+    from gnm import attribution
+    assert attribution.LESION_SCRATCH_BYTES == 2 << 30
 
 
 def test_lesion_kernels_in_the_code_object(tmp_path):

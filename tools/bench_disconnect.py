@@ -7,7 +7,7 @@ them in the arena, (c) model.predict() on the registered copies.  400-node dense
 H = 64, for F0 = 7 and one-hot F0 = 400; 8 subjects x the 105 pairs of a 14-group labelling (7 networks x 2
 hemispheres).  One JSON line per (F0, route); times are medians after a warm-up, per VIRTUAL graph (one cut copy, both
 classes).  `disconnect` is the whole method call (the base forward, the host mask arrays, the uploads); `disconnect_hip`
-is gnm/core.py disconnect_hip alone on the registered batch (XW, the mask packing, L + 1 launches); `lesion` /
+is gnm/attribution.py disconnect_hip alone on the registered batch (XW, the mask packing, L + 1 launches); `lesion` /
 `lesion_hip` are the same two figures of lesion() with each pair's set A as the removed set.
     python tools/bench_disconnect.py [--subjects 8] [--groups 14] [--reps 5] [--f0 7,400] [--no-parent] [--out FILE]"""
 import argparse
@@ -40,7 +40,7 @@ def emit(rec):
 
 
 import torch
-from gnm import core, synth
+from gnm import attribution, synth
 from gnm.lesion import cut_edge_counts, pair_sets
 from models.graphcnn import GIN_InfoMaxReg
 
@@ -98,14 +98,14 @@ for f0 in [int(x) for x in args.f0.split(",")]:
     in_a = np.tile(a, (args.subjects, 1)).astype(np.uint8)
     in_b = np.tile(b, (args.subjects, 1)).astype(np.uint8)
     vgraph = np.repeat(np.arange(args.subjects, dtype=np.int32), S)
-    th = timed(lambda: core.disconnect_hip(model._spec, batch, X, P, [0, 1], in_a, in_b, vgraph), args.reps)
+    th = timed(lambda: attribution.disconnect_hip(model._spec, batch, X, P, [0, 1], in_a, in_b, vgraph), args.reps)
     emit(dict(route="disconnect", ms=round(t * 1e3, 3), us_per_virtual_graph=round(t / V * 1e6, 3),
               disconnect_hip_ms=round(th * 1e3, 3), disconnect_hip_us_per_virtual_graph=round(th / V * 1e6, 3), **common))
     # lesion() on the same number of sets, in the same run
     model.lesion(graphs, (0, 1), a)
     tl = timed(lambda: model.lesion(graphs, (0, 1), a), args.reps)
     model.eval()
-    tlh = timed(lambda: core.lesion_hip(model._spec, batch, X, P, [0, 1], in_a, vgraph), args.reps)
+    tlh = timed(lambda: attribution.lesion_hip(model._spec, batch, X, P, [0, 1], in_a, vgraph), args.reps)
     emit(dict(route="lesion", ms=round(tl * 1e3, 3), us_per_virtual_graph=round(tl / V * 1e6, 3),
               lesion_hip_ms=round(tlh * 1e3, 3), lesion_hip_us_per_virtual_graph=round(tlh / V * 1e6, 3),
               disconnect_over_lesion=round(t / tl, 3), disconnect_hip_over_lesion_hip=round(th / tlh, 3), **common))

@@ -6,7 +6,7 @@ the registered copies (one call per set size: a batch holds graphs of one node c
 graphs at L = 5, m = 2, H = 64, for F0 = 7 and one-hot F0 = 400; 8 subjects x the 20 sets of a deletion curve (fractions
 0, 0.05, ..., 0.95 of a random ranking).  One JSON line per (F0, route); times are medians after a warm-up, per
 VIRTUAL graph (one lesioned copy, both classes).  `lesion` is the whole method call (the base forward, the host mask
-arrays, the uploads, the one read-back of the kept counts); `lesion_hip` is gnm/core.py lesion_hip alone on the
+arrays, the uploads, the one read-back of the kept counts); `lesion_hip` is gnm/attribution.py lesion_hip alone on the
 registered batch (XW, the mask packing, the read-back, L + 1 launches).
     python tools/bench_lesion.py [--subjects 8] [--sets 20] [--reps 5] [--f0 7,400] [--no-parent] [--out FILE]"""
 import argparse
@@ -39,7 +39,7 @@ def emit(rec):
 
 
 import torch
-from gnm import core, synth
+from gnm import attribution, synth
 from gnm.lesion import masks_from_ranking
 from models.graphcnn import GIN_InfoMaxReg
 
@@ -96,7 +96,7 @@ for f0 in [int(x) for x in args.f0.split(",")]:
     X = batch.arena.features(batch).detach()
     removed = np.concatenate(masks).astype(np.uint8)
     vgraph = np.repeat(np.arange(args.subjects, dtype=np.int32), args.sets)
-    th = timed(lambda: core.lesion_hip(model._spec, batch, X, P, [0, 1], removed, vgraph), args.reps)
+    th = timed(lambda: attribution.lesion_hip(model._spec, batch, X, P, [0, 1], removed, vgraph), args.reps)
     emit(dict(route="lesion", ms=round(t * 1e3, 3), us_per_virtual_graph=round(t / V * 1e6, 3),
               lesion_hip_ms=round(th * 1e3, 3), lesion_hip_us_per_virtual_graph=round(th / V * 1e6, 3), **common))
     if args.no_parent:

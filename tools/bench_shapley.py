@@ -6,7 +6,7 @@ explicit bool masks (the coalition that keeps no node left out: lesion() does no
 graphs at L = 5, m = 2, H = 64, for F0 = 7 and one-hot F0 = 400; 8 subjects, both classes; exact K = 7 and K = 12 (50
 unlabelled nodes) and permutation K = 400 (one player per node), M = 8.  One JSON line per (F0, case); times are medians
 after a warm-up, in microseconds per COALITION scored.  `call`: the whole method (base forward, host arrays, uploads,
-the forward, for shapley() the reduction too); `device`: gnm/core.py shapley_hip / lesion_hip alone on the registered
+the forward, for shapley() the reduction too); `device`: gnm/attribution.py shapley_hip / lesion_hip alone on the registered
 batch; `reduce`: the reduction kernel alone on the scores.
     python tools/bench_shapley.py [--subjects 8] [--reps 5] [--f0 7,400] [--cases exact7,exact12,perm400] [--out FILE]"""
 import argparse
@@ -39,7 +39,7 @@ def emit(rec):
 
 
 import torch
-from gnm import core, synth
+from gnm import attribution, synth
 from gnm import shapley as sh
 from models.graphcnn import GIN_InfoMaxReg
 
@@ -106,17 +106,17 @@ for f0 in [int(x) for x in args.f0.split(",")]:
         rows = np.tile(lab[None, :], (G, 1))
         vgraph = np.repeat(np.arange(G, dtype=np.int32), ids.shape[0])
         all_ids = np.tile(ids, G)
-        t_dev = timed(lambda: core.shapley_hip(model._spec, batch, X, P, [0, 1], rows, vgraph, all_ids, K, ranks),
+        t_dev = timed(lambda: attribution.shapley_hip(model._spec, batch, X, P, [0, 1], rows, vgraph, all_ids, K, ranks),
                       args.reps)
         rem = np.tile(masks, (G, 1)).astype(np.uint8)
         vg_l = np.repeat(np.arange(G, dtype=np.int32), masks.shape[0])
-        t_ldev = timed(lambda: core.lesion_hip(model._spec, batch, X, P, [0, 1], rem, vg_l), args.reps)
+        t_ldev = timed(lambda: attribution.lesion_hip(model._spec, batch, X, P, [0, 1], rem, vg_l), args.reps)
         if exact:
             vals = torch.randn((2, G, 1 << K), device=dev)
-            t_red = timed(lambda: core.shapley_exact_hip(vals, K, interactions=True), args.reps)
+            t_red = timed(lambda: attribution.shapley_exact_hip(vals, K, interactions=True), args.reps)
         else:
             vals = torch.randn((2, G, PERMS, K + 1), device=dev)
-            t_red = timed(lambda: core.shapley_permutation_hip(vals, ranks), args.reps)
+            t_red = timed(lambda: attribution.shapley_permutation_hip(vals, ranks), args.reps)
         us = lambda t, v: round(t / v * 1e6, 3)                           # noqa: E731
         emit(dict(case=case, f0=f0, n=args.n, subjects=G, K=K, H=H, L=L, coalitions=V, lesion_sets=Vl,
                   shapley_call_ms=round(t_call * 1e3, 3), shapley_call_us=us(t_call, V),
