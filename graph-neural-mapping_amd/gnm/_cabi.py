@@ -128,7 +128,13 @@ SIGNATURES = {
     "gnm_dynfc_max_windows": (_ll, [_i]),
     "gnm_dynfc_means": (_i, [_p, _i, _p, _i, _i, _i, _p, _p]),
     "gnm_dynfc_corr": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _p, _p]),
-    "gnm_adam_step": (_i, [_p, _p, _p, _p, _ll, _p, _p, _p]),
+    "gnm_states_max_k": (_i, []),
+    "gnm_states_workspace_doubles": (_ll, [_ll, _i, _i]),
+    "gnm_states_assign": (_i, [_p, _p, _ll, _i, _i, _i, _p, _p, _p, _p]),
+    "gnm_states_accumulate": (_i, [_p, _p, _ll, _i, _i, _p, _p, _p]),
+    "gnm_states_finish": (_i, [_p, _p, _i, _i, _p, _p]),
+    "gnm_states_inertia": (_i, [_p, _p, _ll, _i, _p, _p]),
+    "gnm_adam_step":(_i, [_p, _p, _p, _p, _ll, _p, _p, _p]),
 }
 
 

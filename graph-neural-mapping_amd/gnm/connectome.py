@@ -29,6 +29,11 @@ the device selects:
 
     graphs = graphs_from_connectivity(model_or_arena, fc, None, node_features, labels, knn=20)
     adj = knn_adjacency(fc, 20)                      # [S, n, n] bool, on the device
+
+Connectivity states, k-means over the window FC matrices (gnm/states.py, re-exported here; csrc/dynstates.hip):
+
+    st = connectivity_states_from_timeseries(ts, k, window, stride)      # centroids, labels, distances, counts, inertia
+    stats = state_statistics(st.labels, st.windows, k)                   # occupancy, dwell, transitions per subject
 """
 import numbers
 
@@ -661,3 +666,17 @@ def dynamic_graphs_from_timeseries(model_or_arena, ts, sparsity, labels, window,
         gids += arena.add_connectivity(fc[:m], sparsity, feats, knn=knn, mutual=mutual, absolute=absolute)
     graphs = [ConnectomeGraph(arena, gid, n, labels[s]) for gid, s in zip(gids, windows[:, 0].tolist())]
     return graphs, windows
+
+
+# ---------------------------------------------------------------------------------------------------- states
+# k-means over the window FC matrices (gnm/states.py, csrc/dynstates.hip), re-exported here; states.py imports this
+# module for the window plan and the sliding-window kernels, so the names are looked up on first use
+_STATES = ("ConnectivityStates", "StateStatistics", "connectivity_states", "connectivity_states_from_timeseries",
+           "assign_states", "state_statistics", "kmeanspp_draw")
+
+
+def __getattr__(name):
+    if name in _STATES:
+        from . import states
+        return getattr(states, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -716,6 +716,30 @@ int gnm_dynfc_means(const void* x, int x_f64, const int64_t* w_beg, int window, 
 int gnm_dynfc_corr(const void* x, int x_f64, const int64_t* w_beg, int window, const double* mean, const double* taper,
                    int W, int n, double* fc, void* stream);
 
+/* ---- connectivity states: k-means over window FC matrices (csrc/dynstates.hip) ----------
+ * fc: [W, n, n] fp64 as gnm_dynfc_corr writes it; the features of a window are its entries i < j and only i <= j is
+ * ever read.  cen: [k, n, n] fp64 centroids.  1 <= n <= gnm_timeseries_max_nodes(), 1 <= k <= gnm_states_max_k()
+ * (GNM_ERR_UNSUPPORTED above); W = 0 is GNM_OK.  No kernel uses an atomic; all sums have a fixed order.
+ * gnm_states_workspace_doubles: doubles of `work` for W windows (one partial per window, 64 x 64 upper block pair and
+ *   centroid); 0 for unsupported arguments.
+ * gnm_states_assign: dist[w, c] = sum_{i < j} (fc[w, i, j] - cen[c, i, j])^2 formed directly, dist [W, k]; label[w]
+ *   (int32 [W]) = the smallest c with the least distance, -1 when one of the k distances is not finite.  The order of a
+ *   window's sums depends on the window alone: its dist row is bitwise the same in any call.  groups: workgroups per
+ *   block pair, each striding over the windows (0: the launcher's choice); the result does not depend on it.
+ * gnm_states_accumulate: sum[c, i, j] (i <= j, [k, n, n]) = ((sum + x0) + x1) + .. over the windows with label[w] == c
+ *   in ascending w, on top of what sum holds; count[c] (int64 [k]) += the members.  Carried from chunk to chunk, so a
+ *   centroid does not depend on the chunking; the caller zeroes both before the first chunk.
+ * gnm_states_finish: cen[c, i, j] = cen[c, j, i] = sum[c, i, j] / count[c] (one division); count[c] == 0 keeps cen[c].
+ * gnm_states_inertia: inertia[0] = the sum of dist[w, label[w]] over the windows with label[w] >= 0, in ascending w. */
+int gnm_states_max_k(void);
+long long gnm_states_workspace_doubles(long long W, int n, int k);
+int gnm_states_assign(const double* fc, const double* cen, long long W, int n, int k, int groups, double* work,
+                      double* dist, int* label, void* stream);
+int gnm_states_accumulate(const double* fc, const int* label, long long W, int n, int k, double* sum, long long* count,
+                          void* stream);
+int gnm_states_finish(const double* sum, const long long* count, int n, int k, double* cen, void* stream);
+int gnm_states_inertia(const double* dist, const int* label, long long W, int k, double* inertia, void* stream);
+
 /* gnm_adam_step replaces optimizer.step() of optim.Adam(model.parameters(), lr) (main.py:136, 39-41) on a flat
  * fp32 parameter buffer: torch.optim.Adam's default update (no AMSGrad, L2 weight decay).
  * hyper: DEVICE array of 6 doubles {lr, beta1, beta2, eps, weight_decay, grad_scale} (grad is multiplied by
