@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(UNIT ? 256 : 1024) gnm_disc_score_kernel(const
             const int sub_e = lane & (LPR4 - 1), slot_e = lane / LPR4;
             const size_t vo = (size_t)(row0 + min(wave * (64 / LPR4) + slot_e, n - 1)) * ldh + 4 * sub_e;
 #pragma unroll
-            for (int l = 0; l < MLE; ++l) xe[l] = *reinterpret_cast<const float4*>(hp.p[min(l, L - 1)] + vo);
+            for (int l = 0; l < MLE; ++l) xe[l] = gnm_load16_once(hp.p[min(l, L - 1)] + vo);   // (each row is read once)
         }
     }
     for (int e = tid; e < L * H; e += nthreads) {
@@ -133,7 +133,7 @@ __global__ void __launch_bounds__(UNIT ? 256 : 1024) gnm_disc_score_kernel(const
 #define GNM_DS_LOAD(xx, r_)                                                                                      \
         {                                                                                                        \
             const size_t vo = (size_t)(row0 + min((r_), n - 1)) * ldh + 4 * sub;                                 \
-            _Pragma("unroll") for (int l = 0; l < ML; ++l) xx[l] = *reinterpret_cast<const float4*>(lp[l] + vo); \
+            _Pragma("unroll") for (int l = 0; l < ML; ++l) xx[l] = gnm_load16_once(lp[l] + vo);                  \
         }
 #define GNM_DS_FINISH(xx, r_)                                                                                    \
         {                                                                                                        \

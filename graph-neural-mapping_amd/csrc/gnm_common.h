@@ -48,6 +48,33 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 static constexpr int kWave = 64;           // CDNA wavefront
 static constexpr int kLdsBudget = 160 * 1024;  // bytes of LDS per CU (gfx950)
 
+// ---- cache policy of the big streams (the aux argument of the raw buffer builtins; gfx950: 1 = sc0, 2 = nt, 16 = sc1) ----
+// kLoadOnce: an [N, 64] array that a launch reads exactly once (a row is never wanted again, by this launch or the next:
+// the consumer of whatever is written starts at row 0, evicted long before).  nt on those loads measured -0.14 ms on the
+// 2.5 ms step (profiles/store_policy_ab.md); a site takes it only where its own launch got faster in the step.
+// kStoreStream: the 16-byte stores of an [N, 64] output.  sc1 (16: write through, drop the line, nothing dirty left for
+// the kernel boundary) measured a tie against the default on every site and in the step, so it stays 0; the define is
+// what tools/build_variant.py rebuilds that comparison with.
+#ifndef GNM_STORE_STREAM_AUX
+#define GNM_STORE_STREAM_AUX 0
+#endif
+#ifndef GNM_LOAD_ONCE_AUX
+#define GNM_LOAD_ONCE_AUX 2
+#endif
+static constexpr int kStoreStream = GNM_STORE_STREAM_AUX;
+static constexpr int kLoadOnce = GNM_LOAD_ONCE_AUX;
+
+// 16-byte kLoadOnce load through a pointer (the policies a pointer load can name here: default and nt).
+__device__ __forceinline__ float4 gnm_load16_once(const float* p) {
+    static_assert(kLoadOnce == 0 || kLoadOnce == 2, "pointer loads take the default policy or nt");
+    if constexpr (kLoadOnce == 0) {
+        return *reinterpret_cast<const float4*>(p);
+    } else {
+        const f32x4 u = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
+        return make_float4(u.x, u.y, u.z, u.w);
+    }
+}
+
 // ReLU the way torch computes it (graphcnn.py:166 / :190, mlp.py:48): a NaN stays a NaN, where fmaxf(x, 0) would
 // return 0 (IEEE maxNum) and quietly repair a poisoned row -- e.g. the 0/0 row of an isolated node under neighbour
 // "average" + learn_eps (graphcnn.py:157-158), which in the reference makes that graph's readout and logits NaN.

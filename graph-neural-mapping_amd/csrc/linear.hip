@@ -828,7 +828,7 @@ __global__ void __launch_bounds__(kSplitWaves * 64) gnm_lin_split_kernel(const L
         const long long row0 = (long long)tile * 32;
         const __amdgpu_buffer_rsrc_t rs = gnm_tile_rsrc(p.X + row0 * p.ldx, (GNM_L64_ABLATE & 2) ? 0LL : min((long long)p.N - row0, 32LL), p.ldx, KC);
 #pragma unroll
-        for (int j = 0; j < NLD; ++j) raw[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, in_voff, j * in_step, 0);
+        for (int j = 0; j < NLD; ++j) raw[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, in_voff, j * in_step, kLoadOnce);
     };
     int t = gw;
     load_tile(t);
@@ -978,7 +978,7 @@ __global__ void __launch_bounds__(kSplitWaves * 64) gnm_lin_split_kernel(const L
 #pragma unroll
         for (int st = 0; st < NST; ++st) {
             const gnm_u32x4 v = *reinterpret_cast<const gnm_u32x4*>(xi + st * WSTEP * XS);
-            __builtin_amdgcn_raw_buffer_store_b128(v, rz, out_voff + st * out_step, 0, 0);     // (row step in the vector offset: see above)
+            __builtin_amdgcn_raw_buffer_store_b128(v, rz, out_voff + st * out_step, 0, kStoreStream);     // (row step in the vector offset: see above)
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -2568,7 +2568,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_kernel(const LbArg
                 const int idx = lane + 64 * st;
                 const int row = idx / O4, oc = idx - row * O4;
                 const gnm_u32x4 v = *reinterpret_cast<const gnm_u32x4*>(Xs + row * XS + 4 * oc);
-                __builtin_amdgcn_raw_buffer_store_b128(v, rd, out_voff + st * out_step, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(v, rd, out_voff + st * out_step, 0, kStoreStream);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -2680,8 +2680,8 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_sz_kernel(const Lb
         const __amdgpu_buffer_rsrc_t rz = gnm_tile_rsrc(p.Z + row0 * p.ldz, rows, p.ldz, HP);
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
-            g4[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, gz_voff_g, j * gz_step_g, 0);
-            z4[j] = __builtin_amdgcn_raw_buffer_load_b128(rz, gz_voff_z, j * gz_step_z, 0);
+            g4[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, gz_voff_g, j * gz_step_g, kLoadOnce);
+            z4[j] = __builtin_amdgcn_raw_buffer_load_b128(rz, gz_voff_z, j * gz_step_z, kLoadOnce);
         }
     };
     auto do_tile = [&](int t, int t_next) {
@@ -2760,7 +2760,7 @@ __global__ void __launch_bounds__(256, 2) gnm_linear_bwd_pipe_sz_kernel(const Lb
                     const int row = idx / O4, oc = idx - row * O4;
                     const gnm_u32x4 v = *reinterpret_cast<const gnm_u32x4*>(Hs + row * XS + 4 * oc);
                     // (row step in the vector offset: see gnm_lin_stream_kernel)
-                    __builtin_amdgcn_raw_buffer_store_b128(v, rd, out_voff + (16 * q + (64 / O4) * st) * p.lda * 4, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(v, rd, out_voff + (16 * q + (64 / O4) * st) * p.lda * 4, 0, kStoreStream);
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();          // the half image has been read
@@ -2875,7 +2875,9 @@ static int launch_lb(const LbArgs& a, int grid, hipStream_t s) {
 // ---------------------------------------------------------------------------------
 // What gnm_linear_bwd_rz_kernel and its narrow form share beyond the helpers above.
 // G of a tile in the accumulator layout (lane = column 32 a + i, rows (r & 3) + 8 (r >> 2) + 4 h): 4-byte loads clipped by
-// the tile's descriptor; a tile past the end gets an empty one and no traffic.
+// the tile's descriptor; a tile past the end gets an empty one and no traffic.  AUX: the loads' cache policy (the wide
+// kernel reads G once and takes kLoadOnce; on the narrow one that measured a tie and it stays at the default).
+template <int AUX>
 __device__ __forceinline__ void rz_load_g(float (&g)[2][16], const float* G, int ldg, int N, int tile, int g_voff) {
     const long long row0 = (long long)tile * 32;
     const long long rows = min((long long)N - row0, 32LL);
@@ -2884,7 +2886,7 @@ __device__ __forceinline__ void rz_load_g(float (&g)[2][16], const float* G, int
     for (int r = 0; r < 16; ++r)
 #pragma unroll
         for (int a = 0; a < 2; ++a)
-            g[a][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rg, g_voff + 128 * a, ((r & 3) + 8 * (r >> 2)) * ldg * 4, 0));
+            g[a][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rg, g_voff + 128 * a, ((r & 3) + 8 * (r >> 2)) * ldg * 4, AUX));
 }
 // The BatchNorm backward on one column tile of the accumulators (lane = column col): dz holds Z - bias on entry and
 // dZ = cA (G - m1 - xhat m2) on exit, zero in rows past `rows`; dZ is also written to the wave's image Xs (for dgrad).
@@ -3050,14 +3052,14 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
                 const int idx = lane + 64 * st;
                 const int row = idx >> 4, oc = idx & 15;
                 const gnm_u32x4 v = *reinterpret_cast<const gnm_u32x4*>(Xs + row * XS + 4 * oc);
-                __builtin_amdgcn_raw_buffer_store_b128(v, rd, out_voff + st * out_step, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(v, rd, out_voff + st * out_step, 0, kStoreStream);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         GNM_RSTAMP(6 + 6 * min(tk, 9))
         // the next tile: G and the row-wise X fragments before the weight-gradient product
-        rz_load_g(g, p.G, p.ldg, p.N, t_next, (int)g_voff);                      // past the wave's last tile: empty descriptors, no traffic
+        rz_load_g<kLoadOnce>(g, p.G, p.ldg, p.N, t_next, (int)g_voff);                      // past the wave's last tile: empty descriptors, no traffic
         load_next_x(t_next);
         // ---- dW += dZ^T f(X): both operands from registers, batch rows in the accumulators' order ---------------------
 #pragma unroll
@@ -3091,7 +3093,7 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rz_kernel(const 
     {
         int t = gw;
         load_next_x(t);
-        rz_load_g(g, p.G, p.ldg, p.N, t, (int)g_voff);
+        rz_load_g<kLoadOnce>(g, p.G, p.ldg, p.N, t, (int)g_voff);
         if (t < ntiles) {
             do_tile(t, t + tstride);                  // peeled (see gnm_linear_bwd_pipe_kernel)
             for (t += tstride; t < ntiles; t += tstride) do_tile(t, t + tstride);
@@ -3199,7 +3201,7 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();          // the dZ image has been read
-        rz_load_g(g, p.G, p.ldg, p.N, t_next, (int)g_voff);                      // past the wave's last tile: empty descriptors, no traffic
+        rz_load_g<0>(g, p.G, p.ldg, p.N, t_next, (int)g_voff);                      // past the wave's last tile: empty descriptors, no traffic
         // ---- dW += dZ^T X: both operands from registers, batch rows in the accumulators' order -----------------------
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
@@ -3219,7 +3221,7 @@ __global__ void __launch_bounds__(kRzWaves * 64) gnm_linear_bwd_rzn_kernel(const
     };
     {
         int t = gw;
-        rz_load_g(g, p.G, p.ldg, p.N, t, (int)g_voff);
+        rz_load_g<0>(g, p.G, p.ldg, p.N, t, (int)g_voff);
         if (t < ntiles) {
             do_tile(t, t + tstride);
             for (t += tstride; t < ntiles; t += tstride) do_tile(t, t + tstride);

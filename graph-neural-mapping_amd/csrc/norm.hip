@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(1024) gnm_bn_relu_readout_kernel(
         const float4 sc = *reinterpret_cast<const float4*>(scale + 4 * c4);
         const float4 sh = *reinterpret_cast<const float4*>(shift + 4 * c4);
         for (int r = rg; r < n; r += RP) {
-            float4 v = *reinterpret_cast<const float4*>(Z + (size_t)(row0 + r) * ldz + 4 * c4);
+            float4 v = gnm_load16_once(Z + (size_t)(row0 + r) * ldz + 4 * c4);      // (Z is read once)
             v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
             if (relu) {
                 v.x = gnm_relu(v.x); v.y = gnm_relu(v.y); v.z = gnm_relu(v.z); v.w = gnm_relu(v.w);
