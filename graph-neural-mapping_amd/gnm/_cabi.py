@@ -134,6 +134,11 @@ SIGNATURES = {
     "gnm_states_accumulate": (_i, [_p, _p, _ll, _i, _i, _p, _p, _p]),
     "gnm_states_finish": (_i, [_p, _p, _i, _i, _p, _p]),
     "gnm_states_inertia": (_i, [_p, _p, _ll, _i, _p, _p]),
+    "gnm_topology_max_nodes": (_i, []),
+    "gnm_topology_workspace_bytes": (_ll, [_i, _i, _i]),
+    "gnm_topology_nodes": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                _p, _p]),
+    "gnm_topology_local": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
     "gnm_adam_step":(_i, [_p, _p, _p, _p, _ll, _p, _p, _p]),
 }
 

@@ -34,6 +34,10 @@ Connectivity states, k-means over the window FC matrices (gnm/states.py, re-expo
 
     st = connectivity_states_from_timeseries(ts, k, window, stride)      # centroids, labels, distances, counts, inertia
     stats = state_statistics(st.labels, st.windows, k)                   # occupancy, dwell, transitions per subject
+
+Graph-theoretic measures of registered graphs (gnm/topology.py, re-exported here; csrc/topology.hip):
+
+    m = graph_measures(model_or_arena, graphs)       # degree, clustering, path lengths, efficiencies, components
 """
 import numbers
 
@@ -675,8 +679,15 @@ _STATES = ("ConnectivityStates", "StateStatistics", "connectivity_states", "conn
            "assign_states", "state_statistics", "kmeanspp_draw")
 
 
+# graph-theoretic measures of the registered graphs (gnm/topology.py, csrc/topology.hip), re-exported the same way
+_TOPOLOGY = ("GraphMeasures", "graph_measures", "graph_measures_host")
+
+
 def __getattr__(name):
     if name in _STATES:
         from . import states
         return getattr(states, name)
+    if name in _TOPOLOGY:
+        from . import topology
+        return getattr(topology, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

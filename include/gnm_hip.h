@@ -740,6 +740,43 @@ int gnm_states_accumulate(const double* fc, const int* label, long long W, int n
 int gnm_states_finish(const double* sum, const long long* count, int n, int k, double* cen, void* stream);
 int gnm_states_inertia(const double* dist, const int* label, long long W, int k, double* inertia, void* stream);
 
+/* ---- graph-theoretic measures of the batch's graphs (csrc/topology.hip) ----------
+ * The batch as the aggregation kernels take it (rowptr, col, b_rp_off, b_col_off, node_off, B; the forward CSR of
+ * SYMMETRIC graphs: the measures are those of undirected graphs).  One workgroup per graph stages plain bit rows in LDS
+ * from the CSR (a repeated entry collapses, an entry (u, u) is dropped: the kernels see a simple graph; the bit matrix of
+ * gnm_adj_bits_build is not read) and works on them with AND, OR and popcount; every fp64 output is formed once from
+ * finished integers in a fixed order, so a graph's bytes do not depend on the launch it is part of.
+ * 1 <= n_max <= gnm_topology_max_nodes() (GNM_ERR_UNSUPPORTED above, nothing launched); n_max >= every graph's n (a larger
+ * graph is left unwritten); B = 0 is GNM_OK.
+ *   eff(H, m) = acc = 0.0; for k = 1, 2, ..: if H[k]: acc = acc + (double)H[k] / (double)k;  then acc / (double)m.
+ * gnm_topology_workspace_bytes: bytes of global scratch gnm_topology_local wants for the batch (flags bit 0: local
+ *   efficiency is asked for); 0 -- all scratch is in LDS -- and -1 for arguments the launchers refuse.
+ * gnm_topology_nodes: per node v of graph b, at row node_off[b] + v of arrays of N = node_off[B] entries, with c_k the
+ *   number of nodes at distance k from v: degree d (int32), triangles t (int32: pairs of adjacent neighbours),
+ *   clustering = (2.0 * t) / (double)(d * (d - 1)) (0.0 for d < 2), eccentricity = the last k with c_k > 0 (0 for an
+ *   isolated node), reachable = sum c_k, distance_sum = sum k c_k, component = the smallest node id reached, v included,
+ *   nodal_efficiency = eff(c, n - 1) (0.0 for n = 1).  Per graph, arrays of B: edges (int64), components (int32: the nodes
+ *   with component == self), distance_histogram [B, n_max] (int64: column k the ordered pairs at distance k, column 0 and
+ *   the columns from n on 0), diameter (int32: the largest finite distance), global_efficiency = eff(histogram,
+ *   n (n - 1)) (0.0 for n < 2), characteristic_path_length = (double)(sum k C[k]) / (double)(sum C[k]) (NaN when no pair
+ *   is connected), transitivity = (double)(sum_v t_v) / (double)(sum_v d_v (d_v - 1) / 2) = 3 triangles / connected
+ *   triples (0.0 without triples), mean_clustering = ((0.0 + clustering[0]) + clustering[1]) + .. over the graph's nodes,
+ *   divided by n.
+ * gnm_topology_local: local_efficiency [N] = eff(H_v, d (d - 1)) with H_v[k] the ordered pairs of neighbours of v at
+ *   distance k inside the subgraph the neighbours induce (networkx's local_efficiency term; 0.0 for d < 2), and
+ *   mean_local_efficiency [B], the same sequential mean.  workspace: gnm_topology_workspace_bytes' bytes (may be NULL). */
+int gnm_topology_max_nodes(void);
+long long gnm_topology_workspace_bytes(int B, int n_max, int flags);
+int gnm_topology_nodes(const int32_t* rowptr, const uint16_t* col, const int64_t* b_rp_off, const int64_t* b_col_off,
+                       const int32_t* node_off, int B, int n_max, int32_t* degree, int32_t* triangles,
+                       double* clustering, int32_t* eccentricity, int32_t* reachable, int32_t* distance_sum,
+                       int32_t* component, double* nodal_efficiency, long long* edges, int32_t* components,
+                       long long* distance_histogram, int32_t* diameter, double* global_efficiency,
+                       double* characteristic_path_length, double* transitivity, double* mean_clustering, void* stream);
+int gnm_topology_local(const int32_t* rowptr, const uint16_t* col, const int64_t* b_rp_off, const int64_t* b_col_off,
+                       const int32_t* node_off, int B, int n_max, void* workspace, double* local_efficiency,
+                       double* mean_local_efficiency, void* stream);
+
 /* gnm_adam_step replaces optimizer.step() of optim.Adam(model.parameters(), lr) (main.py:136, 39-41) on a flat
  * fp32 parameter buffer: torch.optim.Adam's default update (no AMSGrad, L2 weight decay).
  * hyper: DEVICE array of 6 doubles {lr, beta1, beta2, eps, weight_decay, grad_scale} (grad is multiplied by
