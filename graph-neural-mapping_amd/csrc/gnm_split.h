@@ -1,6 +1,6 @@
 // The project's "fp32-faithful on the bf16 pipe" arithmetic, in one place: the exact three-plane bf16 split of an fp32
 // value and the six-term matrix product built on it (v_mfma_f32_32x32x16_bf16, 16x the rate of the fp32 instruction).
-// Every kernel that multiplies this way -- the eval kernels through gnm_tile_step, the training kernels of linear.hip
+// Every kernel that multiplies this way -- the eval kernels through gnm_tile_step, the training kernels of linear*.hip
 // through gnm_mma6 / gnm_mma6_planes -- includes this header and issues the product nowhere else; a change here changes
 // all of them together.
 #pragma once

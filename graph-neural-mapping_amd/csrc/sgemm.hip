@@ -31,7 +31,7 @@ __device__ __forceinline__ void sg_fetch(const __amdgpu_buffer_rsrc_t rs, int ld
     const int k0 = 16 * s + 8 * h;
     if constexpr (MODE == 2) {
         // rows past K lie past the end of the operand: the descriptor's range check (which covers the scalar offset on
-        // gfx950, see linear.hip gnm_tile_rsrc) returns zero for them -- one vector offset per fragment, no per-element selects
+        // gfx950, see gnm_linear.h gnm_tile_rsrc) returns zero for them -- one vector offset per fragment, no per-element selects
         const unsigned voff = line < nlines ? (unsigned)((8 * h * ld + line) * 4) : 0x80000000u;   // (past any operand; no wrap with the row offset)
 #pragma unroll
         for (int j = 0; j < 8; ++j)

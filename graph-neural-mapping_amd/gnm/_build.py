@@ -9,7 +9,14 @@ LIB_DIR = os.path.join(PKG_DIR, "lib")
 # GNM_HIP_LIB: load another build of the same C-ABI instead (A/B timing of kernel variants made by
 # tools/build_variant.py); unset in normal use
 LIB_PATH = os.environ.get("GNM_HIP_LIB") or os.path.join(LIB_DIR, "libgnm_hip.so")
-SOURCES = ["agg.hip", "aggm.hip", "maxpool.hip", "linear.hip", "norm.hip", "disc.hip", "head.hip", "tail.hip", "sgemm.hip", "evalfwd.hip", "evallayer.hip", "saliency.hip", "cam.hip", "edgesal.hip", "occlusion.hip", "lesion.hip", "disconnect.hip", "shapley.hip", "intgrad.hip", "connectome.hip", "timeseries.hip", "dynstates.hip", "topology.hip", "host.cpp"]
+
+
+def sources(src_dir):
+    """The translation units of a csrc directory: every *.hip and *.cpp in it, sorted."""
+    return sorted(f for f in os.listdir(src_dir) if f.endswith((".hip", ".cpp")))
+
+
+SOURCES = sources(CSRC)
 
 
 def _hipcc():
@@ -42,7 +49,7 @@ def build(force=False, verbose=False, out=None, defines=(), csrc=None, obj_dir=N
     os.makedirs(obj_dir, exist_ok=True)
     hipcc = _hipcc()
     procs = []
-    for src in SOURCES:
+    for src in sources(src_dir):
         obj = os.path.join(obj_dir, src.rsplit(".", 1)[0] + ".o")
         objs.append(obj)
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(src_dir, src), "-o", obj,

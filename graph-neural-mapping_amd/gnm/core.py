@@ -360,7 +360,7 @@ def linear_bwd_launch(sv, lo, G, coef, W, bias, dW, db, need_dA, N, stream):
                 sv.x_in.stride(0), *pro, W.data_ptr(), W.stride(0), ptr(dA), dA.stride(0) if need_dA else 0, None,
                 dW.stride(0), db.data_ptr(), ws.data_ptr(), N, K, Hk, *los, ptr(lo_part), stream)
         rc = -2
-        # (mirrors gnm_linear_bwd_fused_rz's own decline rules in csrc/linear.hip: a foreign call less per Linear)
+        # (mirrors gnm_linear_bwd_fused_rz's own decline rules in csrc/linear_bwd.hip: a foreign call less per Linear)
         if Hk == 64 and lo_part is None and ((K == 64 and need_dA) or (K <= 16 and not sv.pro)):
             # sv.z = Linear(sv.x_in) as gnm_linear_fwd left it: the pass recomputes it instead of reading it
             rc = lib.gnm_linear_bwd_fused_rz(G.data_ptr(), G.stride(0), bias.data_ptr(), *args)

@@ -26,6 +26,36 @@ def test_library_exports_every_declared_symbol():
     assert _cabi.lib.gnm_version().startswith(b"gnm_hip")
 
 
+def test_build_sources_are_what_the_directory_holds(tmp_path):
+    from gnm import _build
+    for name in ("b.hip", "a.cpp", "c.h", "notes.md"):
+        (tmp_path / name).write_text("")
+    assert _build.sources(str(tmp_path)) == ["a.cpp", "b.hip"]
+    assert _build.SOURCES == _build.sources(_build.CSRC)
+    # the three units of the Linear family, and every unit of the hand-kept list this replaced
+    for name in ("linear.hip", "linear_wgrad.hip", "linear_bwd.hip", "agg.hip", "aggm.hip", "maxpool.hip", "norm.hip",
+                 "disc.hip", "head.hip", "tail.hip", "sgemm.hip", "evalfwd.hip", "evallayer.hip", "saliency.hip", "cam.hip",
+                 "edgesal.hip", "occlusion.hip", "lesion.hip", "disconnect.hip", "shapley.hip", "intgrad.hip",
+                 "connectome.hip", "timeseries.hip", "dynstates.hip", "topology.hip", "host.cpp"):
+        assert name in _build.SOURCES, name
+
+
+def test_kernel_isa_diff_of_the_library_with_itself():
+    """tools/kernel_isa_diff.py: every kernel of the product library is `same` against itself, exit status 0."""
+    import subprocess
+    import sys
+    from gnm import _build
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
+        pytest.skip("llvm-objdump not in this image")
+    lib = _build.build()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_isa_diff.py"), lib, lib],
+                       stdout=subprocess.PIPE, text=True)
+    lines = r.stdout.splitlines()
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert len(lines) > 100 and all(ln.startswith("same ") for ln in lines[:-1])
+    assert "0 differs, 0 only in A, 0 only in B" in lines[-1]
+
+
 def test_product_package_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "graph-neural-mapping_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -173,7 +173,7 @@ def test_declared_route_is_what_the_routing_code_does(case, monkeypatch):
         assert [e for e in log if not e.startswith("gnm_bn_bwd_apply")] == events, ((l, k), log, events)
         assert (r.job is not None) == (code in ("rz", "fused", "fused+sums"))
         assert (r.lo_sums is not None) == (code in ("fused+sums", "generic+masked"))
-        # the entries' own shape rules (csrc/linear.hip)
+        # the entries' own shape rules (csrc/linear_bwd.hip)
         sums = below and need_dA
         rz_takes = H == 64 and not sums and ((K == 64 and need_dA) or (K <= 16 and not pro))
         fused_takes = H in (32, 64) and (K in (32, 64) or (1 <= K < 32 and not sums))
