@@ -21,17 +21,13 @@
 //     eff(H, m) = acc = 0.0; for k = 1, 2, ..: if H[k]: acc = acc + (double)H[k] / (double)k;  acc / (double)m
 // and the two means are sequential sums over the nodes in ascending order followed by one division.  There is no float
 // atomic and no float reduction across lanes; contraction is off.
-#include "gnm_common.h"
+#include "gnm_topology.h"
 
 namespace {
 
-constexpr int kTopoMaxN = 1024;         // 1024 rows of 33 words are 132 KiB; the largest scratch beside them is 16 KiB
 constexpr int kTopoSmallW = 16;         // words a 16-lane group holds: above it the launch runs 32-lane groups
 
 constexpr int topo_threads(int G) { return G == 16 ? 256 : 1024; }      // 16 or 32 groups per workgroup
-
-__host__ __device__ inline int topo_words(int n) { return (n + 31) >> 5; }
-__host__ __device__ inline int topo_stride(int n) { return topo_words(n) | 1; }
 
 template <int G>
 __device__ __forceinline__ int group_sum(int v) {
@@ -51,23 +47,6 @@ template <int G>
 __device__ __forceinline__ uint32_t group_nonzero(uint32_t w, int gshift) {
     const unsigned long long b = __ballot(w != 0u);
     return (uint32_t)(b >> gshift) & (G == 32 ? 0xffffffffu : 0xffffu);
-}
-
-// Zero the rows, then set the bits of the graph's CSR: a wave per row, its lanes over the row's entries.
-__device__ __forceinline__ void topo_stage(uint32_t* rows, int n, int stride, const int32_t* __restrict__ rp,
-                                           const uint16_t* __restrict__ col) {
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    for (int i = tid; i < n * stride; i += nthr) rows[i] = 0u;
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
-    for (int r = wave; r < n; r += nwave) {
-        const int beg = rp[r], end = rp[r + 1];
-        for (int e = beg + lane; e < end; e += 64) {
-            const int c = col[e];
-            if (c != r && c < n) atomicOr(&rows[r * stride + (c >> 5)], 1u << (c & 31));
-        }
-    }
-    __syncthreads();
 }
 
 // One search of a lane group from node src inside the node set `allowed` (this lane's word of it; 0 on a lane past the
@@ -106,22 +85,6 @@ __device__ __forceinline__ uint32_t topo_bfs(const uint32_t* rows, int stride, i
 }
 
 __device__ __forceinline__ double topo_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-struct TopoGraph {
-    const int32_t* rp;
-    const uint16_t* col;
-    int n, row0;
-};
-
-__device__ __forceinline__ TopoGraph topo_graph(const int32_t* rowptr, const uint16_t* col, const int64_t* b_rp_off,
-                                                const int64_t* b_col_off, const int32_t* node_off, int b) {
-    TopoGraph g;
-    g.rp = rowptr + b_rp_off[b];
-    g.col = col + b_col_off[b];
-    g.row0 = node_off[b];
-    g.n = node_off[b + 1] - g.row0;
-    return g;
-}
 
 struct TopoNodeOut {
     int32_t *degree, *triangles, *eccentricity, *reachable, *distance_sum, *component;
@@ -301,12 +264,6 @@ size_t topo_local_lds(int n_max) {
 }
 static_assert((size_t)kTopoMaxN * 8 + (2 * (size_t)kTopoMaxN + 8) * 4 + (size_t)kTopoMaxN * (kTopoMaxN / 32 + 1) * 4
                   <= (size_t)kLdsBudget, "the largest graph's rows and scratch must fit one CU's LDS");
-
-int topo_check(int B, int n_max) {
-    if (B < 0 || n_max < 1) return GNM_ERR_BAD_ARG;
-    if (n_max > kTopoMaxN) return GNM_ERR_UNSUPPORTED;
-    return GNM_OK;
-}
 
 }  // namespace
 

@@ -139,6 +139,10 @@ SIGNATURES = {
     "gnm_topology_nodes": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                 _p, _p]),
     "gnm_topology_local": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "gnm_topology_max_modules": (_i, []),
+    "gnm_topology_betweenness_workspace_bytes": (_ll, [_i, _i]),
+    "gnm_topology_betweenness": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "gnm_topology_modules": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "gnm_adam_step":(_i, [_p, _p, _p, _p, _ll, _p, _p, _p]),
 }
 

@@ -38,6 +38,10 @@ Connectivity states, k-means over the window FC matrices (gnm/states.py, re-expo
 Graph-theoretic measures of registered graphs (gnm/topology.py, re-exported here; csrc/topology.hip):
 
     m = graph_measures(model_or_arena, graphs)       # degree, clustering, path lengths, efficiencies, components
+
+Hub measures of registered graphs (gnm/hubs.py, re-exported here; csrc/hubs.hip):
+
+    h = hub_measures(model_or_arena, graphs, labels)     # betweenness; participation, within-module z, modularity
 """
 import numbers
 
@@ -681,6 +685,8 @@ _STATES = ("ConnectivityStates", "StateStatistics", "connectivity_states", "conn
 
 # graph-theoretic measures of the registered graphs (gnm/topology.py, csrc/topology.hip), re-exported the same way
 _TOPOLOGY = ("GraphMeasures", "graph_measures", "graph_measures_host")
+# betweenness and the module-aware hub measures (gnm/hubs.py, csrc/hubs.hip)
+_HUBS = ("HubMeasures", "hub_measures", "hub_measures_host")
 
 
 def __getattr__(name):
@@ -690,4 +696,7 @@ def __getattr__(name):
     if name in _TOPOLOGY:
         from . import topology
         return getattr(topology, name)
+    if name in _HUBS:
+        from . import hubs
+        return getattr(hubs, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -777,6 +777,38 @@ int gnm_topology_local(const int32_t* rowptr, const uint16_t* col, const int64_t
                        const int32_t* node_off, int B, int n_max, void* workspace, double* local_efficiency,
                        double* mean_local_efficiency, void* stream);
 
+/* ---- hub measures of the batch's graphs: betweenness and module-aware measures (csrc/hubs.hip) ----------
+ * The batch, the staging of a simple undirected graph into LDS bit rows, n_max and B exactly as for gnm_topology_nodes;
+ * one workgroup per graph, a graph's bytes independent of the launch it is part of.  Every floating-point sum below has
+ * a fixed order and no operation is contracted, so the outputs are bitwise gnm.hubs.hub_measures_host's.
+ * gnm_topology_betweenness: Brandes' algorithm.  For the sources s = 0, 1, .. in order: breadth-first levels from s;
+ *   sigma[s] = 1.0 and, for w at level k, sigma[w] = ((0.0 + sigma[v1]) + sigma[v2]) + .. over its neighbours v at level
+ *   k - 1 in ascending v; delta = 0 and, for k from the deepest level - 1 down to 1 and v at level k, delta[v] =
+ *   ((0.0 + t(w1)) + t(w2)) + .. over its neighbours w at level k + 1 in ascending w, t(w) = (sigma[v] / sigma[w]) *
+ *   (1.0 + delta[w]); total[v] = total[v] + delta[v] for v != s.  betweenness [N] = total * 0.5 (the sum over unordered
+ *   pairs {s, t} of sigma_st(v) / sigma_st); betweenness_normalized [N] = betweenness / (double)((n - 1) (n - 2) / 2),
+ *   0.0 for n < 3.  workspace: gnm_topology_betweenness_workspace_bytes' bytes (0: all scratch is in LDS; -1 for
+ *   arguments the launcher refuses; may be NULL).
+ * gnm_topology_modules: label [N] int32 in batch order, -1 for a node of no module, else 0 .. K - 1 (an entry outside
+ *   that range is read as -1); 1 <= K <= gnm_topology_max_modules() (GNM_ERR_BAD_ARG below, GNM_ERR_UNSUPPORTED above).
+ *   module_degree [N, K] int32: k_v,m = the neighbours of v with label m.  participation [N]: with d = sum_m k_v,m,
+ *   acc = 0.0; for m ascending: r = (double)k_v,m / (double)d; acc = acc + r * r; then 1.0 - acc (0.0 for d = 0).
+ *   within_module_z [N]: for v with label m >= 0, over the s nodes u of module m, S1 = sum k_u,m and S2 = sum k_u,m^2:
+ *   (double)(k_v,m s - S1) / sqrt((double)(s S2 - S1^2)), the sqrt correctly rounded; 0.0 when the radicand is 0 or v
+ *   has no module.  module_edges [B, K, K] int64: the edges between modules, symmetric, edges inside a module on the
+ *   diagonal.  modularity [B]: with E the graph's edges, L_m = module_edges[m, m] and D_m the sum of the (full) degrees
+ *   of module m's nodes, acc = 0.0; for m ascending: a = (double)D_m / (double)(2 E);
+ *   acc = acc + ((double)L_m / (double)E - a * a); 0.0 for E = 0. */
+int gnm_topology_max_modules(void);
+long long gnm_topology_betweenness_workspace_bytes(int B, int n_max);
+int gnm_topology_betweenness(const int32_t* rowptr, const uint16_t* col, const int64_t* b_rp_off,
+                             const int64_t* b_col_off, const int32_t* node_off, int B, int n_max, void* workspace,
+                             double* betweenness, double* betweenness_normalized, void* stream);
+int gnm_topology_modules(const int32_t* rowptr, const uint16_t* col, const int64_t* b_rp_off, const int64_t* b_col_off,
+                         const int32_t* node_off, const int32_t* label, int B, int n_max, int K, int32_t* module_degree,
+                         double* participation, double* within_module_z, long long* module_edges, double* modularity,
+                         void* stream);
+
 /* gnm_adam_step replaces optimizer.step() of optim.Adam(model.parameters(), lr) (main.py:136, 39-41) on a flat
  * fp32 parameter buffer: torch.optim.Adam's default update (no AMSGrad, L2 weight decay).
  * hyper: DEVICE array of 6 doubles {lr, beta1, beta2, eps, weight_decay, grad_scale} (grad is multiplied by
